@@ -1,6 +1,7 @@
 """Throughput of the Mimi encode hot path on MI355X: audio-seconds encoded per wall-second (K = 8, 24 kHz).
 
     python bench.py [--gpus N --steps K --warmup W --batch B --seconds S --workload batch|yodas2|mls [--bpe]]
+                    [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 ``--gpus N`` without torchrun's environment launches N ranks itself (``torch.distributed.run`` as a child
@@ -20,10 +21,16 @@ Workloads (one "step" each; per-GPU work is fixed as N grows: weak scaling):
   bit for bit) through the ADDED ``MimiEncoder.encode_audio_chunks`` (ragged batches of 32 -- a caller change),
   host->device and back included.
 
-Printed beside the headline (``batch`` workload at B = 32 x 10 s): ``k32`` = the same batch at K = 32 (the drop-in
-default: every script builds ``MimiEncoder("kyutai/mimi")`` and encodes all 32 levels), ``b1_k8`` = one 10 s clip per
-encode, resident, K = 8, and ``per_utterance_k32`` = the UNCHANGED per-utterance loop -- ``encode_audio_chunk(a,
-24000)`` once per U[10, 20] s utterance from host memory at the default K = 32, the way
+A plain run sets up, warms up, times the K steps and prints the headline line (``value``, ``ms_per_step`` = the
+milliseconds one timed step took); ``--dump-outputs DIR`` also writes the codes the last timed step returned, as
+``DIR/codes.npy`` (the host-fed workloads: the clips' codes joined along T, and ``frames.npy`` = each clip's
+frames).  The inputs are seeded, so two builds run with the same arguments can be compared code for code.
+Everything below that is measured beside the headline takes ``--full``.
+
+With ``--full``, printed beside the headline (``batch`` workload at B = 32 x 10 s): ``k32`` = the same batch at
+K = 32 (the drop-in default: every script builds ``MimiEncoder("kyutai/mimi")`` and encodes all 32 levels),
+``b1_k8`` = one 10 s clip per encode, resident, K = 8, and ``per_utterance_k32`` = the UNCHANGED per-utterance
+loop -- ``encode_audio_chunk(a, 24000)`` once per U[10, 20] s utterance from host memory at the default K = 32, the way
 ``librispeech-mimi/process_librispeech_dev-test.py:136-141`` and ``mls-en-mimi-pretrain/process_shard.py:302-307``
 run (every length differs, so no hipGraph replay).
 
@@ -31,9 +38,9 @@ Weights: the seeded synthetic kyutai/mimi-shaped checkpoint (random init; throug
 values).  The timed region is bracketed by barrier + synchronize; the max over ranks is reported.  Rank 0
 prints ONE JSON line.
 
-roofline: per-kernel device time from HIP events recorded by the engine on its launch stream during the timed
-steps, aggregated per kernel symbol; the dominant kernel's algorithmic FLOPs / its time vs the MFMA peak of the
-arithmetic it runs on (see ``mfma_peak_for``).  cpu_baseline: the oracle (torch CPU restatement of
+roofline (``--full``): per-kernel device time from HIP events recorded by the engine on its launch stream during
+the timed steps, aggregated per kernel symbol; the dominant kernel's algorithmic FLOPs / its time vs the MFMA peak
+of the arithmetic it runs on (see ``mfma_peak_for``).  cpu_baseline (``--full``): the oracle (torch CPU restatement of
 MimiModel.encode) on a bounded sample of the same workload.
 """
 import argparse
@@ -113,7 +120,18 @@ def parse():
                     help="write the engine's per-encode (stage, kernel) launch sequence here (PMC stage keys)")
     ap.add_argument("--pmc-pass", action="store_true",
                     help="counter pass: the timed steps only (no PCIe / f32 / B=64 extras, no CPU baseline)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the per-stage profile and roofline, the PCIe-inclusive, fp32-MFMA, "
+                         "B = 64 and drop-in rates, and the CPU baseline (each still has its own switch above)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the codes of the last timed step (what the caller of the timed path receives) as "
+                         "DIR/<name>.npy, float32 / float64")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_sequence and (not args.full or args.no_profile):
+        ap.error("--dump-sequence needs the profiled pass: add --full (without --no-profile)")
+    return args
 
 
 def self_launch(args) -> int:
@@ -367,6 +385,7 @@ class Workload:
         from mimi_hip.encoder import MimiEncoder
         from mimi_hip.sharding import make_batches, shard_indices
         self.kind = args.workload
+        self._np = np
         K = args.num_quantizers
         B = args.batch
         if self.kind == "batch":
@@ -379,6 +398,7 @@ class Workload:
             self.host_audio = self.audio.cpu().pin_memory()
             self.steps_clips = None
             self.pending = None
+            self.last_out = None  # the codes tensor of the last finished step
 
             def step():
                 # each step is one whole encode, waited (its f16x3 overflow check) one step behind: the next encode is
@@ -404,11 +424,12 @@ class Workload:
         self.clips = [[synthetic.speech_like(lengths[i], 77, i) for i in b] for b in batches[:n_steps]]
         self.step_seconds = [sum(len(a) for a in c) / 24000.0 for c in self.clips]
         self.i = 0
+        self.last_codes = []  # the last finished step's codes, one [K, T_i] array per clip
 
         if self.kind == "yodas2":
             def run(first, count):  # the steps' batches through the pipelined iterator (host staging overlapped)
-                for _ in enc.encode_batches(self.clips[first:first + count], 24000):
-                    pass
+                for out in enc.encode_batches(self.clips[first:first + count], 24000):
+                    self.last_codes = out
             self.desc = (f"YODAS2-style shard (configs[3]): batches of {B} mixed-length clips U[{lo:g}, {hi:g}] s "
                          f"from host memory through MimiEncoder.encode_batches (= encode_audio_batch per batch: "
                          f"pad-to-longest codes, run as a ragged encode at min(Lmax, 1920 ceil(L/1920)) per item; host "
@@ -419,6 +440,8 @@ class Workload:
 
             def run(first, count):  # every utterance of the steps, each encoded alone (ragged batches of 32)
                 out = enc.encode_audio_chunks([a for c in self.clips[first:first + count] for a in c], 24000)
+                if count > 0:
+                    self.last_codes = out[len(out) - len(self.clips[first + count - 1]):]
                 if first >= args.warmup:
                     self.emitted.extend(out)
             self.desc = (f"MLS-style stream (configs[4], encode part): {B} utterances U[{lo:g}, {hi:g}] s per step, "
@@ -433,7 +456,6 @@ class Workload:
             run(self.i, 1)
             self.i += 1
         self.step = step
-        self._np = np
 
     def run_steps(self, first, count):
         """count steps starting at step index first (host-resident workloads pipeline across them)"""
@@ -442,14 +464,47 @@ class Workload:
                 self.step()
             if self.pending is not None:  # the last step's wait
                 self.pending.wait()
+                self.last_out = self.pending.out
                 self.pending = None
         else:
             self.run(first, count)
+
+    def outputs(self):
+        """What the last finished step returned to its caller, as host arrays: ``codes`` [B, K, T] of the resident
+        batch; for the host-fed workloads the clips' [K, T_i] codes joined along T, and ``frames`` = every T_i."""
+        np = self._np
+        if self.kind == "batch":
+            return {"codes": self.last_out.cpu().numpy()}
+        return {"codes": np.concatenate([np.asarray(c) for c in self.last_codes], axis=1),
+                "frames": np.array([c.shape[1] for c in self.last_codes])}
 
     def timed_seconds(self, first, count):
         if self.kind == "batch":
             return self.audio_seconds * count
         return sum(self.step_seconds[first:first + count])
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # of all the files of one --dump-outputs
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """``out_dir/<name>.npy`` (``<name>_rank<r>.npy`` when there are several ranks) for each array: float32, or
+    float64 where float32 would not hold an integer exactly.  An array whose share of DUMP_LIMIT_BYTES is too
+    small for it is written as a fixed sample: its elements at seeded, sorted flat indices (the same ones every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays)) - 4096  # (4096: room for the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.kind == "f":
+            exact32 = a.dtype.itemsize <= 4
+        else:  # integers (codes, frame counts): float32 holds them exactly below 2^24
+            exact32 = a.size == 0 or int(np.abs(a).max()) < (1 << 24)
+        a = a.astype(np.float32 if exact32 else np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
 
 
 def timed_max(fn, n, barrier, reduce_max):
@@ -722,7 +777,8 @@ def main():
 
     wl.run_steps(0, args.warmup)
     torch.cuda.synchronize()
-    profile = not args.no_profile
+    # a plain run times the steps and prints the headline; everything measured beside it belongs to --full
+    profile = args.full and not args.no_profile
     # small batches are launch-bound and replay hipGraphs (engine.cpp graph_encode), which per-stage events
     # would switch off: their timed region runs without events and the stage profile comes from a separate pass;
     # so do the host-fed workloads (their device time per step, beside the wall time, shows what the host costs)
@@ -740,6 +796,8 @@ def main():
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     barrier()
+    if args.dump_outputs:  # (before any later pass encodes into the same buffers)
+        dump_outputs(args.dump_outputs, wl.outputs(), rank, world)
     elapsed = t1 - t0
     audio_s = wl.timed_seconds(args.warmup, args.steps)
     if dist is not None:
@@ -797,7 +855,7 @@ def main():
         result["f16x3"] = {"f16_reruns": model.f16_reruns,
                            "min_headroom": round(tight[1][2], 2) if tight else None,
                            "min_headroom_tensor": tight[0] if tight else None}
-    if wl.kind == "batch" and not args.pmc_pass:
+    if args.full and wl.kind == "batch" and not args.pmc_pass:
         # SURVEY.md §8(d)'s metric as it defines the wall clock (H2D of the f32 input through D2H of the codes),
         # reported beside `value` (the HBM-resident rate, the contract's definition), never as it
         n = max(2, min(args.steps, 20))
@@ -860,7 +918,7 @@ def main():
         result["north_star"] = north_star_groups(prof, args.steps, pmc, pmc_note)
     if args.bpe and wl.kind == "mls":
         result.update(train_bpe_over_codes(args, wl, dist, rank, world, dev.index, elapsed))
-    if rank == 0 and world == 1 and args.cpu_baseline_seconds > 0 and not args.pmc_pass:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline_seconds > 0 and not args.pmc_pass:
         cb_batch = args.batch if wl.kind == "batch" else 1
         result["cpu_baseline"] = cpu_baseline(args.cpu_baseline_seconds, cpu_threads(args.cpu_threads),
                                               args.seconds if wl.kind == "batch" else 15.0, cb_batch)

@@ -171,6 +171,37 @@ def test_bench_north_star_groups(tmp_path):
     assert "quantizer" not in g
 
 
+def test_bench_dump_outputs_and_options(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: int codes land as float32 .npy with every value kept; an array beyond its share of the
+    size limit becomes the same seeded sample on every call; values float32 cannot hold go to float64.  --full is off
+    by default, --steps 0 and --dump-sequence without --full are usage errors."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    codes = np.random.default_rng(1).integers(0, 2048, (3, 8, 7)).astype(np.int32)
+    bench.dump_outputs(str(tmp_path / "a"), {"codes": codes, "frames": np.array([1 << 30, 5])}, 0, 1)
+    got = np.load(tmp_path / "a" / "codes.npy")
+    assert got.dtype == np.float32 and got.shape == codes.shape and np.array_equal(got, codes)
+    fr = np.load(tmp_path / "a" / "frames.npy")
+    assert fr.dtype == np.float64 and fr.tolist() == [1 << 30, 5]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * (4096 + 40))  # 40 bytes = 10 float32 per array
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"codes": codes, "frames": np.array([3, 4])}, 1, 2)
+    s1, s2 = (np.load(tmp_path / d / "codes_rank1.npy") for d in ("b", "c"))
+    assert s1.shape == (10,) and s1.dtype == np.float32 and np.array_equal(s1, s2)
+    assert np.isin(s1, codes).all() and np.load(tmp_path / "b" / "frames_rank1.npy").tolist() == [3, 4]
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return bench.parse()
+    a = parse("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    assert parse("--full", "--dump-outputs", "d").dump_outputs == "d"
+    for bad in (("--steps", "0"), ("--dump-sequence", "x"), ("--full", "--no-profile", "--dump-sequence", "x")):
+        with pytest.raises(SystemExit):
+            parse(*bad)
+
+
 def test_stage_keyed_pmc_alignment(tmp_path):
     """tools/summarize_profile.stage_bytes: counter rows after the spin marker walked against the launch sequence;
     a stage's extra dispatches (RVQ levels, final) summed into it; bookkeeping kernels left out."""

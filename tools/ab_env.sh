@@ -1,6 +1,8 @@
 #!/bin/bash
 # A/B of env-selected variants on one box: bench.py per value of $VAR in $VALS, ROUNDS times each (own time limits)
 set -u
+# (the stage table printed below comes from the profiled pass: --full)
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 mkdir -p gpurun_out
 for i in $(seq 1 ${ROUNDS:-2}); do

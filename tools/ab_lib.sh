@@ -6,6 +6,8 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$R"
 mkdir -p gpurun_out
 BASE_LIB=${BASE_LIB:-tools/bin/libmimi_hip_base.so}
+# (the stage table printed below comes from the profiled pass: --full)
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 for i in $(seq 1 ${ROUNDS:-3}); do
   for v in new base; do
     if [ $v = base ]; then export MIMI_HIP_LIB=$R/$BASE_LIB; else unset MIMI_HIP_LIB; fi

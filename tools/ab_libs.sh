@@ -2,6 +2,8 @@
 # A/B of library builds on one box: bench.py with each of $LIBS ("new" = the in-tree libmimi_hip.so, else
 # ab/libmimi_hip_<name>.so (ab/ travels to the box; tools/bin does not)), alternated ROUNDS times, each run under its own time limit.
 set -u
+# (the stage table printed below comes from the profiled pass: --full)
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$R"
 mkdir -p gpurun_out

@@ -9,7 +9,7 @@ OUT="gpurun_out/$TAG"
 mkdir -p "$OUT"
 run() {
   local name=$1; shift
-  timeout -k 10 300 python bench.py --cpu-baseline-seconds 0 "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
+  timeout -k 10 300 python bench.py --full --cpu-baseline-seconds 0 "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
   local rc=$?
   echo "$name rc=$rc $(python -c "import json,sys; d=json.loads(open('$OUT/$name.json').read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], {k: d.get(k) for k in ('f32_mode_value','pcie_inclusive_value')})" 2>/dev/null)"
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then tail -5 "$OUT/$name.err"; exit $rc; fi

@@ -6,7 +6,7 @@
 # gpurun_out/TAG/.  Steps:
 #   tests            pytest -m gpu (the driver's suite), log pytest_gpu.log, parity_report.json copied
 #   smoke            __graft_entry__.smoke()
-#   bench            the headline bench line (bench.py defaults; BENCH_ARGS appended) -> bench_b32.json
+#   bench            the headline bench line and all beside it (bench.py --full; BENCH_ARGS appended) -> bench_b32.json
 #   profile          rocprofv3 kernel trace + stats and the FETCH_SIZE / WRITE_SIZE PMC passes (tools/profile_round.sh)
 #   sq               the SQ / GRBM counter passes behind tools/sq_table.py (tools/pmc_pass.sh)
 #   drop_in          bench lines for batch 1, batch 4, the YODAS2-style and MLS-style workloads
@@ -32,7 +32,7 @@ fail() { echo "step $1 failed (rc=$2)"; [ -f "$3" ] && tail -20 "$3"; exit 1; }
 
 bench_line() {  # name, args...
   local name=$1; shift
-  timeout -k 10 400 python -u bench.py --cpu-baseline-seconds 0 "$@" --json-out "$O/bench_$name.json" \
+  timeout -k 10 400 python -u bench.py --full --cpu-baseline-seconds 0 "$@" --json-out "$O/bench_$name.json" \
     > "$O/bench_$name.log" 2>&1 || fail "bench $name" $? "$O/bench_$name.log"
   python3 -c "import json; d=json.load(open('$O/bench_$name.json')); print('$name', d['value'], d['ms_per_step'])"
 }
@@ -50,7 +50,7 @@ for step in "$@"; do
         || fail smoke $? "$O/smoke.log"
       tail -1 "$O/smoke.log" ;;
     bench)
-      timeout -k 10 400 python -u bench.py ${BENCH_ARGS:-} --json-out "$O/bench_b32.json" > "$O/bench_b32.log" 2>&1 \
+      timeout -k 10 400 python -u bench.py --full ${BENCH_ARGS:-} --json-out "$O/bench_b32.json" > "$O/bench_b32.log" 2>&1 \
         || fail bench $? "$O/bench_b32.log"
       python3 -c "import json; d=json.load(open('$O/bench_b32.json')); print('b32', d['value'], d['ms_per_step'], d['roofline']['frac'])" ;;
     profile)
@@ -93,7 +93,7 @@ for step in "$@"; do
       rc=$?; grep -c "bitwise equal" "$O/bits_cmp.txt"; grep -v "bitwise equal" "$O/bits_cmp.txt" | head -20
       [ $rc -eq 0 ] || fail bits_cmp $rc "$O/bits_cmp.txt" ;;
     gloo2)
-      MIMI_BENCH_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --gpus 2 --steps 5 --warmup 2 \
+      MIMI_BENCH_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --full --gpus 2 --steps 5 --warmup 2 \
         --cpu-baseline-seconds 0 --no-f32-mode --json-out "$O/bench_gloo2.json" > "$O/bench_gloo2.log" 2>&1 \
         || fail gloo2 $? "$O/bench_gloo2.log"
       python3 -c "import json; d=json.load(open('$O/bench_gloo2.json')); print('gloo2', d['value'], d['dist'], [(r['rank'], r['pci_bus']) for r in d['ranks']])" ;;

@@ -6,6 +6,8 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 STEP_TESTS=${STEP_TESTS:-1}
 STEP_BENCH=${STEP_BENCH:-1}
+# (the bench step records everything bench.py measures: --full)
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 if [ "$STEP_TESTS" = 1 ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -v -p no:cacheprovider --timeout 300 --timeout-method thread -rf > gpurun_out/pytest_gpu.log 2>&1
   rc=$?

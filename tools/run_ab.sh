@@ -3,6 +3,8 @@
 # ROUNDS times; prints audio-s/s, ms per step and the stages named in $STAGES (each run under its own limit;
 # stops at the first failure).
 set -u
+# (the stage table printed below comes from the profiled pass: --full)
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 i=0
