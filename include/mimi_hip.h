@@ -17,6 +17,10 @@
  *       pre-quantizer embedding (used by the bit-exact quantizer parity test)
  *   mimi_encoded_length
  *       replaces ``MimiModel.get_encoded_length`` (TF/modeling_mimi.py:1265-1278)
+ *   mimi_enable_decode / mimi_create_from_dir_flags(MIMI_CREATE_DECODE) + mimi_decode
+ *       replace ``MimiModel.decode(audio_codes).audio_values`` (librispeech-mimi/utils.py:72-81 ``str_to_audio``;
+ *       TF/modeling_mimi.py:1408-1458); mimi_rvq_decode replaces ``MimiSplitResidualVectorQuantizer.decode``
+ *       (TF/modeling_mimi.py:1128-1137)
  *
  * Conventions: plain pointers and sizes, no exceptions, no torch types.  Every function returns a
  * mimi_status; on failure ``mimi_last_error()`` (thread-local) describes it.  Device pointers are HIP
@@ -103,7 +107,8 @@ int mimi_create(const mimi_config* cfg, int device, mimi_engine** out);
 /* Supply one parameter by its HF name, fp32, host memory, copied. */
 int mimi_set_weight(mimi_engine* e, const char* name, const float* host_data, int64_t numel);
 
-/* Read every encode-path parameter from a safetensors file (F32 tensors, HF names). */
+/* Read every encode-path parameter from a safetensors file (F32 tensors, HF names); after mimi_enable_decode the
+ * decode-path parameters too (otherwise the decoder half of a full checkpoint is skipped unread). */
 int mimi_load_safetensors(mimi_engine* e, const char* path);
 
 /* Check all parameters are present, re-lay them out for the kernels and upload them. */
@@ -169,6 +174,63 @@ int mimi_encode_ragged_async(mimi_engine* e, const float* dev_audio, const int64
  */
 int mimi_rvq_encode(mimi_engine* e, const float* dev_embedding, int64_t frames, int32_t num_quantizers,
                     int32_t* dev_codes, void* stream);
+
+/*
+ * ---- decode: codes -> waveform (replaces mimi_model.decode(codes).audio_values of str_to_audio,
+ * librispeech-mimi/utils.py:58-81; MimiModel.decode, TF/modeling_mimi.py:1388-1458) ----
+ *
+ * Decode weights are opt-in, so that encode-only users and partial checkpoints load as before.
+ * mimi_enable_decode (before mimi_finalize) adds the decode-path parameters -- decoder.*, upsample.conv.weight,
+ * decoder_transformer.*, the quantizer's two output_proj.weight -- to the expected set: mimi_load_safetensors then
+ * reads them (F32; weight-norm forms resolved as for encode) and mimi_finalize checks, re-lays out and uploads them
+ * (a missing or mis-shaped one: MIMI_ERR_WEIGHTS naming it).  After mimi_finalize: MIMI_ERR_STATE.
+ * mimi_create_from_dir_flags = mimi_create_from_dir with flags; MIMI_CREATE_DECODE calls mimi_enable_decode.
+ *
+ * ARITHMETIC: decode always runs the fp32-MFMA form of the GEMMs (MIMI_PRECISION_F32) and the fp32 attention and
+ * residual-block kernels, whatever mimi_set_precision says -- no activation scales, hence no calibration, overflow
+ * read-back or fallback.  Not provided: f16x3 decode, hipGraph replay of decode, ragged decode, streaming (KV-cache /
+ * padding-cache) decode.
+ */
+enum { MIMI_CREATE_DECODE = 1 };
+int mimi_enable_decode(mimi_engine* e);
+int mimi_create_from_dir_flags(const char* weights_dir, int device, uint32_t flags, mimi_engine** out);
+
+/* Samples produced for `frames` 12.5 Hz frames: frames x 2 x prod(upsampling_ratios) = 1920 x frames by default
+ * (the length of MimiModel.decode(codes).audio_values, TF/modeling_mimi.py:1388-1406). */
+int64_t mimi_decoded_length(int64_t frames);
+int64_t mimi_decoded_length_cfg(const mimi_config* cfg, int64_t frames);
+
+/*
+ * MimiModel.decode (TF/modeling_mimi.py:1408-1458): dev_codes device int32 [batch][num_quantizers][frames],
+ * 1 <= num_quantizers <= the checkpoint's levels; dev_audio device f32 [batch][mimi_decoded_length(frames)].
+ * Synchronises `stream` once, to read the bounds flag: a code outside [0, codebook_size) is never used as an index
+ * (the kernel substitutes 0) and the call returns MIMI_ERR_INVALID_ARGUMENT ("code outside [0, codebook_size)") with
+ * dev_audio unspecified.  An engine without decode weights: MIMI_ERR_STATE.  Serialised by the engine's mutex like
+ * encode.  Grows a decode workspace of its own (MIMI_ERR_OUT_OF_MEMORY leaves the engine usable).  An item's samples
+ * do not depend on its batch-mates.
+ */
+int mimi_decode(mimi_engine* e, const int32_t* dev_codes, int32_t batch, int64_t frames, int32_t num_quantizers,
+                float* dev_audio, void* stream);
+
+/*
+ * The quantizer's decode alone, the mirror of mimi_rvq_encode (MimiSplitResidualVectorQuantizer.decode,
+ * TF/modeling_mimi.py:1128-1137): dev_codes int32 [num_quantizers][frames] -> dev_embedding f32
+ * [frames][hidden_size] (the reference's [B, 512, T] transposed).  Bounds flag and errors as mimi_decode.
+ */
+int mimi_rvq_decode(mimi_engine* e, const int32_t* dev_codes, int64_t frames, int32_t num_quantizers,
+                    float* dev_embedding, void* stream);
+
+/* Device bytes mimi_decode's workspace needs for (batch, frames); grown on demand. */
+int64_t mimi_decode_workspace_bytes(const mimi_engine* e, int32_t batch, int64_t frames);
+
+/*
+ * Host-only: the weight re-layout that turns a causal MimiConvTranspose1d (kernel 2 ratio, stride ratio, weight
+ * [cin][cout][2 ratio]; TF/modeling_mimi.py:349-405) into a causal k = 2 convolution with ratio x cout phase-major
+ * output channels: out [ratio * cout][2 * cin], out[p cout + co][ci] = w[ci][co][p + ratio] (the x[t - 1] tap),
+ * out[p cout + co][cin + ci] = w[ci][co][p] (the x[t] tap).  What mimi_finalize applies; tests check it against
+ * torch's conv_transpose1d.  No device is touched.
+ */
+int mimi_upconv_relayout(const float* w, int32_t cin, int32_t cout, int32_t ratio, float* out);
 
 /*
  * Arithmetic of the conv / linear GEMMs (the residual VQ distances are always exact fp32):
@@ -313,7 +375,11 @@ int mimi_profile_reset(mimi_engine* e);
  * stage's first dispatch is its named kernel).  Lets a rocprofv3 counter pass key its dispatches by stage. */
 int mimi_profile_sequence(mimi_engine* e, int32_t max_stages, char* names /* max_stages*128 */, int32_t* n_stages);
 
-/* When enabled, mimi_encode keeps a copy of each stage's output (for per-stage parity tests). */
+/* When enabled, mimi_encode keeps a copy of each stage's output (for per-stage parity tests); mimi_decode keeps
+ * "quantized" (after the two output_proj, summed), "upsample", "xfmr7", "dconv0" (raw decoder.layers.0 output), "up0".."up3"
+ * (each transposed conv's raw output), "dres0_elu".."dres3_elu" (ELU of each residual block's output: the form the
+ * fused block stores) and "audio", all [batch][time][channels].  mimi_set_profiling records decode's stages too
+ * (names "dec_..."). */
 int mimi_set_taps(mimi_engine* e, int enable);
 /* Copy tap `name` to host: dst holds cap floats; *numel receives the element count; dims[0..2] the
  * [batch][time][channels] shape.  Synchronises. */

@@ -1,0 +1,156 @@
+// Decode path (MimiModel.decode, TF/modeling_mimi.py:1388-1458): the stages that are not a GEMM.
+//
+//   rvq_decode_kernel    codes -> the two RVQ sums (semantic | acoustic), the gather + add of
+//                        MimiResidualVectorQuantizer.decode (:1070-1078) on the engine's fp32 codebook rows
+//   upsample_dw_kernel   the depthwise causal transposed conv 12.5 -> 25 Hz (MimiModel.upsample, :1208-1216, :399-405)
+//   final_conv_kernel    decoder.layers.14: ELU'd [B][L][64] -> waveform [B][L] (k = 3, causal, Cout = 1)
+//
+// All three are memory-bound streams: 16-byte loads and stores, consecutive lanes on consecutive addresses.  The
+// transposed convs of the SEANet decoder run as GEMMs (gemm.hip ROLE_UPCONV), its residual blocks as the fused
+// blocks of resblock.hip, the transformer as the encoder's launches on the decoder_transformer weights (engine.cpp).
+#include "kernels.h"
+
+namespace mimi {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------------------------------------
+// codes [B][K][T] int32 -> out [B*T][2*D] fp32 = (sum over the semantic levels | sum over the acoustic levels) of
+// cb_rows[level][code][:], each half accumulated in fp32 in level order starting from 0.0 as the reference sums them
+// (quantized_out = 0.0; quantized_out = quantized_out + layer.decode(indices)), so each half holds torch's bits.
+// One wave per (frame, half): lane l holds columns 4l .. 4l+3 (D = 256).  K <= nsem leaves the acoustic half zero.
+// BOUNDS BEFORE LOAD: a code outside [0, ncodes) never forms an address -- the wave raises *flag and gathers row 0
+// (the host then fails the call: the output is unspecified but every access was in bounds).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rvq_decode_kernel(const int32_t* __restrict__ codes, long long frames, int T,
+                                                         int K, int nsem, int ncodes, const float* __restrict__ cb_rows,
+                                                         float* __restrict__ out, unsigned* __restrict__ flag) {
+    constexpr int D = 256;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const long long frame = (long long)blockIdx.x * 2 + (wave >> 1);
+    if (frame >= frames) return;
+    const int half = wave & 1;
+    const long long b = frame / T;
+    const int t = (int)(frame - b * T);
+    const int lv0 = half ? nsem : 0;
+    const int lv1 = half ? K : (K < nsem ? K : nsem);
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    bool bad = false;
+    for (int lv = lv0; lv < lv1; ++lv) {
+        const int32_t code = codes[(b * K + lv) * (long long)T + t];
+        unsigned c = (unsigned)code;
+        if (c >= (unsigned)ncodes) {  // (negative codes wrap above ncodes)
+            bad = true;
+            c = 0u;
+        }
+        const f32x4 v = *reinterpret_cast<const f32x4*>(cb_rows + ((long long)lv * ncodes + c) * D + 4 * lane);
+        acc = acc + v;
+    }
+    if (bad && lane == 0) atomicOr(flag, 1u);
+    *reinterpret_cast<f32x4*>(out + frame * (2 * D) + half * D + 4 * lane) = acc;
+}
+
+hipError_t launch_rvq_decode(const int32_t* codes, long long frames, int frames_per_item, int K, int nsem, int ncodes,
+                             int D, const float* cb_rows, float* out, unsigned* flag, hipStream_t s) {
+    if (D != 256 || frames <= 0 || frames_per_item <= 0 || K < 1 || nsem < 1 || ncodes < 1 || !codes || !cb_rows ||
+        !out || !flag || frames % frames_per_item != 0)
+        return hipErrorInvalidValue;
+    const long long blocks = (frames + 1) / 2;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rvq_decode_kernel, dim3((unsigned)blocks), dim3(256), 0, s, codes, frames, frames_per_item, K,
+                       nsem, ncodes, cb_rows, out, flag);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// x [B][T][C] -> y [B][2T][C], depthwise (groups = C), k = 4, stride 2, no bias, causal (the 2 trailing outputs of
+// conv_transpose1d trimmed): y[2t + p][c] = w[c][p] x[t][c] + w[c][p + 2] x[t - 1][c], x[-1] = 0.
+// One thread per (b, t, 4 channels): two 16-B loads of x, four of w (w[c][0..3] is one float4), two 16-B stores.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void upsample_dw_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                          float* __restrict__ y, long long rows, int T, int C4) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * C4) return;
+    const long long row = i / C4;  // b * T + t
+    const int c4 = (int)(i - row * C4);
+    const int t = (int)(row % T);
+    const int C = C4 * 4;
+    const f32x4 x1 = *reinterpret_cast<const f32x4*>(x + row * C + 4 * c4);
+    f32x4 x0 = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (t > 0) x0 = *reinterpret_cast<const f32x4*>(x + (row - 1) * C + 4 * c4);
+    f32x4 o0, o1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const f32x4 wc = *reinterpret_cast<const f32x4*>(w + (long long)(4 * c4 + e) * 4);
+        o0[e] = wc[0] * x1[e] + wc[2] * x0[e];
+        o1[e] = wc[1] * x1[e] + wc[3] * x0[e];
+    }
+    float* yo = y + (2 * row) * C + 4 * c4;  // item b's rows start at 2 b T: 2 (b T + t) = 2 b T + 2 t
+    *reinterpret_cast<f32x4*>(yo) = o0;
+    *reinterpret_cast<f32x4*>(yo + C) = o1;
+}
+
+hipError_t launch_upsample_dw(const float* x, const float* w, float* y, int batch, long long T, int C, hipStream_t s) {
+    if (batch <= 0 || T <= 0 || T > 0x7fffffffLL || C <= 0 || C % 4 || !x || !w || !y) return hipErrorInvalidValue;
+    const long long n = (long long)batch * T * (C / 4);
+    const long long blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(upsample_dw_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, w, y, (long long)batch * T,
+                       (int)T, C / 4);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// x [B][L][64] (already ELU'd by the last residual block's epilogue) -> y [B][L]:
+//   y[l] = bias + sum_{k < 3} sum_{c < 64} w[k][c] x[l - 2 + k][c],  x[< 0] = 0       (the mirror of conv0)
+// A streaming reduction over 192 values per sample, 256 B of input per sample: HBM-bound.  A workgroup takes a
+// contiguous tile of FC_TILE samples: its FC_TILE + 2 rows go to LDS with 16-B loads, consecutive lanes on
+// consecutive 16 B (a wave reads 1 KiB = 4 whole rows per load); then thread i reads its three rows from LDS (row
+// stride 68 floats: conflict-free ds_read_b128) against the weights (LDS broadcasts) in four running sums.
+// ------------------------------------------------------------------------------------------------
+constexpr int FC_TILE = 128, FC_C = 64, FC_LD = 68;
+
+__global__ __launch_bounds__(FC_TILE) void final_conv_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, float* __restrict__ y,
+                                                             long long L) {
+    __shared__ __attribute__((aligned(16))) float xs[(FC_TILE + 2) * FC_LD];
+    __shared__ __attribute__((aligned(16))) float ws[3 * FC_C];
+    const int tid = threadIdx.x;
+    const long long l0 = (long long)blockIdx.x * FC_TILE;
+    const float* __restrict__ xb = x + (long long)blockIdx.y * L * FC_C;
+    for (int i = tid; i < 3 * FC_C; i += FC_TILE) ws[i] = w[i];
+    for (int idx = tid; idx < (FC_TILE + 2) * (FC_C / 4); idx += FC_TILE) {
+        const int r = idx >> 4, c4 = idx & 15;
+        const long long g = l0 - 2 + r;
+        f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (g >= 0 && g < L) v = *reinterpret_cast<const f32x4*>(xb + g * FC_C + 4 * c4);
+        *reinterpret_cast<f32x4*>(xs + r * FC_LD + 4 * c4) = v;
+    }
+    __syncthreads();
+    const long long l = l0 + tid;
+    if (l >= L) return;
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int c4 = 0; c4 < FC_C / 4; ++c4) {
+            const f32x4 xv = *reinterpret_cast<const f32x4*>(xs + (tid + k) * FC_LD + 4 * c4);
+            const f32x4 wv = *reinterpret_cast<const f32x4*>(ws + k * FC_C + 4 * c4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = __builtin_fmaf(xv[e], wv[e], acc[e]);
+        }
+    y[(long long)blockIdx.y * L + l] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + bias[0];
+}
+
+hipError_t launch_final_conv(const float* x, const float* w, const float* bias, float* y, int batch, long long L, int C,
+                             int ksize, hipStream_t s) {
+    if (C != FC_C || ksize != 3 || batch <= 0 || batch > 65535 || L <= 0 || !x || !w || !bias || !y)
+        return hipErrorInvalidValue;
+    const long long tiles = (L + FC_TILE - 1) / FC_TILE;
+    if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(final_conv_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(FC_TILE), 0, s, x, w, bias, y, L);
+    return hipGetLastError();
+}
+
+}  // namespace mimi

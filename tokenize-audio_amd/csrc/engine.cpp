@@ -1,4 +1,5 @@
-// Mimi encode engine: weights, workspace, stage sequencing and the C ABI of include/mimi_hip.h.
+// Mimi encode engine (and, opt-in, the decode pass: see "decode" below): weights, workspace, stage sequencing and
+// the C ABI of include/mimi_hip.h.
 //
 // Data layout in HBM (all fp32, channels-last so that every conv is a plain GEMM, see gemm.hip):
 //   audio            [B][L]
@@ -375,6 +376,19 @@ struct mimi_engine {
         int64_t dims[3] = {0, 0, 0};
     };
     std::map<std::string, Tap> tapmap;
+
+    // ---- decode path (mimi_enable_decode; see "decode" below).  fp32-MFMA arithmetic whatever `precision` says ----
+    bool decode_enabled = false;  // the decode-path tensors are expected, read and uploaded
+    DevConv dec_first, dec_last;  // decoder.layers.0 (hidden -> 16 x filters, k 7) and the last conv (filters -> 1, k 3)
+    std::vector<DevConv> dec_up;  // transposed convs as causal k = 2 convs with r * Cout phase-major output channels
+    std::vector<DevConv> dec_res3, dec_res1;
+    std::vector<DevXfmr> dxf;     // decoder_transformer (fp32 weights only)
+    float* outproj = nullptr;     // [hidden][2 * vq]: (semantic | acoustic) output_proj side by side along K
+    float* upsample_w = nullptr;  // [hidden][4]
+    void* dws = nullptr;          // decode's own workspace (encode's buffers and captured graphs stay untouched)
+    size_t dws_bytes = 0;
+    unsigned* dec_flag = nullptr;       // device word: a code outside [0, codebook_size) was seen
+    unsigned* dec_flag_host = nullptr;  // pinned
 };
 
 static int dev_alloc(mimi_engine* e, void** p, size_t bytes) {
@@ -583,6 +597,10 @@ extern "C" int mimi_create(const mimi_config* cfg, int device, mimi_engine** out
 // file (default config) -> a finalized engine.  config_json.cpp parses the config and picks the file; on any failure
 // the half-built engine is released and the first error is the one mimi_last_error reports.
 extern "C" int mimi_create_from_dir(const char* weights_dir, int device, mimi_engine** out) {
+    return mimi_create_from_dir_flags(weights_dir, device, 0, out);
+}
+
+extern "C" int mimi_create_from_dir_flags(const char* weights_dir, int device, uint32_t flags, mimi_engine** out) {
     if (!out) return set_err(MIMI_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
     if (!weights_dir) return set_err(MIMI_ERR_INVALID_ARGUMENT, "weights_dir is NULL");
@@ -593,8 +611,10 @@ extern "C" int mimi_create_from_dir(const char* weights_dir, int device, mimi_en
     mimi_config_default(&cfg);
     if (!cfg_path.empty() && (rc = mimi_config_from_json(cfg_path.c_str(), &cfg))) return rc;
     mimi_engine* e = nullptr;
+    if (flags & ~(uint32_t)MIMI_CREATE_DECODE) return set_err(MIMI_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
     if ((rc = mimi_create(&cfg, device, &e))) return rc;
-    if ((rc = mimi_load_safetensors(e, st_path.c_str())) || (rc = mimi_finalize(e))) {
+    if (((flags & MIMI_CREATE_DECODE) && (rc = mimi_enable_decode(e))) ||
+        (rc = mimi_load_safetensors(e, st_path.c_str())) || (rc = mimi_finalize(e))) {
         const std::string msg = g_last_error;
         mimi_destroy(e);
         g_last_error = msg;
@@ -614,13 +634,15 @@ extern "C" int mimi_set_weight(mimi_engine* e, const char* name, const float* da
 
 // Checkpoint files: safetensors.cpp (host-only, bounds-checked; built under ASan/UBSan by tools/asan).  A tensor
 // is read when the encode path needs it (the names build_expected lists, the quantizer's codebooks, weight-norm
-// factors of a conv); the decoder / upsample tensors of a full checkpoint are skipped unread.
+// factors of a conv); the decoder / upsample tensors of a full checkpoint are skipped unread unless
+// mimi_enable_decode has put the decode-path names into `expected`.
 extern "C" int mimi_load_safetensors(mimi_engine* e, const char* path) {
     if (!e || !path) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null argument");
     if (e->finalized) return set_err(MIMI_ERR_STATE, "weights are frozen after mimi_finalize");
     std::lock_guard<std::mutex> lk(e->mu);
     auto wanted = [&](const std::string& name) {
-        if (name.rfind("decoder", 0) == 0 || name.rfind("upsample", 0) == 0) return false;
+        // (the decode half of a checkpoint is read only after mimi_enable_decode: its names are then in `expected`)
+        if (!e->decode_enabled && (name.rfind("decoder", 0) == 0 || name.rfind("upsample", 0) == 0)) return false;
         const bool quant = name.rfind("quantizer.", 0) == 0 &&  // input_proj + codebooks (not output_proj)
                            (name.find(".codebook.") != std::string::npos || name.find("input_proj") != std::string::npos);
         return e->expected.count(name) > 0 || quant ||
@@ -813,6 +835,7 @@ static float torch_sqsum_host(const float* r, int D) {
 }
 
 static int calibrate_scales(mimi_engine* e);
+static int finalize_decode(mimi_engine* e);
 
 extern "C" int mimi_finalize(mimi_engine* e) {
     if (!e) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null engine");
@@ -978,6 +1001,7 @@ extern "C" int mimi_finalize(mimi_engine* e) {
         if ((rc = upload(e, &e->cb_unscale, unsc)) || (rc = upload(e, &e->cb_emax, emax))) return rc;
     }
     e->levels_available = L;
+    if (e->decode_enabled && (rc = finalize_decode(e))) return rc;
     e->host_w.clear();
     e->finalized = true;  // (the f16x3 activation scales are calibrated before the first f16x3 encode)
     return MIMI_OK;
@@ -2524,6 +2548,472 @@ extern "C" int mimi_rvq_encode(mimi_engine* e, const float* emb, int64_t frames,
     return MIMI_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// decode (MimiModel.decode, TF/modeling_mimi.py:1388-1458): codes [B][K][T] -> waveform [B][1920 T]
+// ------------------------------------------------------------------------------------------------
+// The mirror of the encode pass, all activations fp32 channels-last:
+//   codes --rvq_decode_kernel--> (semantic sum | acoustic sum) [B T][2 Dq]
+//         --GEMM, W = [W_sem | W_ac] along K--> embedding [B T][512]      (the two output_proj and their sum, one pass)
+//         --upsample_dw_kernel--> [B][2T][512] --decoder_transformer (the encoder's launches, other weights)-->
+//         --decoder.layers.0 (k 7, bias + ELU)--> [B][2T][1024]
+//         --4 x ( transposed conv as GEMM (ROLE_UPCONV, raw) ; fused residual block + trailing ELU )-->
+//         [B][1920 T][64] --final_conv_kernel--> waveform.
+// A causal MimiConvTranspose1d (kernel 2r, stride r, the k - s extra outputs trimmed on the right, :399-405) is exactly
+// a causal k = 2 convolution with r Cout output channels in phase-major order,
+//   out[t r + p][co] = b[co] + sum_ci ( W[ci][co][p] x[t][ci] + W[ci][co][p + r] x[t - 1][ci] ),   x[-1] = 0,
+// so the channels-last GEMM output [T][r Cout] IS the up-sampled tensor [T r][Cout]: no pixel-shuffle pass.
+// ARITHMETIC: decode always runs the fp32-MFMA GEMMs and the fp32 attention / residual-block kernels (PREC_F32),
+// whatever mimi_set_precision says: no activation scales, so no calibration, no overflow read-back, no fallback.
+// Not built here: f16x3 decode, hipGraph capture of decode, ragged decode, KV-cache / streaming decode.
+
+static int64_t decode_upsampling(const mimi_config& c) {
+    int64_t f = 2;  // upsample: 12.5 -> 25 Hz
+    for (int i = 0; i < c.num_ratios; ++i) f *= c.upsampling_ratios[i];
+    return f;
+}
+
+extern "C" int64_t mimi_decoded_length_cfg(const mimi_config* cfg, int64_t frames) {
+    mimi_config d;
+    if (!cfg) {
+        mimi_config_default(&d);
+        cfg = &d;
+    }
+    if (frames < 0) return -1;
+    return frames * decode_upsampling(*cfg);
+}
+
+extern "C" int64_t mimi_decoded_length(int64_t frames) { return mimi_decoded_length_cfg(nullptr, frames); }
+
+// W [Cin][Cout][2r] (ConvTranspose1d layout) -> W'[p Cout + co][tap Cin + ci]: tap 0 multiplies x[t - 1] and holds
+// W[ci][co][p + r], tap 1 multiplies x[t] and holds W[ci][co][p]
+static void relayout_upconv(const float* w, int cin, int cout, int r, float* o) {
+    for (int p = 0; p < r; ++p)
+        for (int co = 0; co < cout; ++co) {
+            float* row = o + ((size_t)p * cout + co) * 2 * cin;
+            for (int ci = 0; ci < cin; ++ci) {
+                const float* src = w + ((size_t)ci * cout + co) * 2 * r;
+                row[ci] = src[p + r];
+                row[cin + ci] = src[p];
+            }
+        }
+}
+
+extern "C" int mimi_upconv_relayout(const float* w, int32_t cin, int32_t cout, int32_t ratio, float* out) {
+    if (!w || !out || cin < 1 || cout < 1 || ratio < 1) return set_err(MIMI_ERR_INVALID_ARGUMENT, "mimi_upconv_relayout: bad arguments");
+    relayout_upconv(w, cin, cout, ratio, out);
+    return MIMI_OK;
+}
+
+static void build_expected_decode(mimi_engine* e) {
+    const mimi_config& c = e->cfg;
+    auto& ex = e->expected;
+    const int h = c.hidden_size;
+    int C = c.num_filters << c.num_ratios;
+    ex["decoder.layers.0.conv.weight"] = {C, h, c.kernel_size};
+    ex["decoder.layers.0.conv.bias"] = {C};
+    int idx = 1;
+    for (int s = 0; s < c.num_ratios; ++s) {
+        const int r = c.upsampling_ratios[s];
+        idx += 1;  // ELU
+        const std::string u = "decoder.layers." + std::to_string(idx) + ".conv.";
+        ex[u + "weight"] = {C, C / 2, 2 * r};
+        ex[u + "bias"] = {C / 2};
+        idx += 1;
+        C /= 2;
+        const std::string p = "decoder.layers." + std::to_string(idx) + ".block.";
+        ex[p + "1.conv.weight"] = {C / c.compress, C, c.residual_kernel_size};
+        ex[p + "1.conv.bias"] = {C / c.compress};
+        ex[p + "3.conv.weight"] = {C, C / c.compress, 1};
+        ex[p + "3.conv.bias"] = {C};
+        idx += 1;
+    }
+    idx += 1;  // ELU
+    const std::string f = "decoder.layers." + std::to_string(idx) + ".conv.";
+    ex[f + "weight"] = {c.audio_channels, C, c.last_kernel_size};
+    ex[f + "bias"] = {c.audio_channels};
+    ex["upsample.conv.weight"] = {h, 1, c.downsample_kernel};
+    for (int l = 0; l < c.num_hidden_layers; ++l) {
+        const std::string p = "decoder_transformer.layers." + std::to_string(l) + ".";
+        for (const char* n : {"q_proj", "k_proj", "v_proj"})
+            ex[p + "self_attn." + n + ".weight"] = {c.num_attention_heads * c.head_dim, h};
+        ex[p + "self_attn.o_proj.weight"] = {h, c.num_attention_heads * c.head_dim};
+        ex[p + "mlp.fc1.weight"] = {c.intermediate_size, h};
+        ex[p + "mlp.fc2.weight"] = {h, c.intermediate_size};
+        for (const char* n : {"input_layernorm", "post_attention_layernorm"}) {
+            ex[p + n + ".weight"] = {h};
+            ex[p + n + ".bias"] = {h};
+        }
+        ex[p + "self_attn_layer_scale.scale"] = {h};
+        ex[p + "mlp_layer_scale.scale"] = {h};
+    }
+    for (const char* q : {"semantic", "acoustic"})
+        ex[std::string("quantizer.") + q + "_residual_vector_quantizer.output_proj.weight"] = {h, c.vq_hidden_dim, 1};
+}
+
+extern "C" int mimi_enable_decode(mimi_engine* e) {
+    if (!e) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null engine");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->decode_enabled) return MIMI_OK;
+    if (e->finalized) return set_err(MIMI_ERR_STATE, "mimi_enable_decode must come before mimi_finalize");
+    const mimi_config& c = e->cfg;
+    // the kernels behind the decode pass: fused residual blocks at C = 64 .. 512, the 64 -> 1 k = 3 last conv, the
+    // k = 4 stride-2 depthwise upsample
+    if (c.num_ratios > 4 || c.num_filters != 64 || c.last_kernel_size != 3 || c.audio_channels != 1 ||
+        c.residual_kernel_size != 3 || c.compress != 2 || c.downsample_kernel != 4 || c.downsample_stride != 2)
+        return set_err(MIMI_ERR_UNSUPPORTED, "decode: config outside the kyutai/mimi decoder family");
+    build_expected_decode(e);
+    e->decode_enabled = true;
+    return MIMI_OK;
+}
+
+static int finalize_decode(mimi_engine* e) {
+    const mimi_config& c = e->cfg;
+    const int h = c.hidden_size, n = c.num_ratios;
+    int rc;
+    int C = c.num_filters << n;
+    if ((rc = make_conv(e, e->dec_first, "decoder.layers.0.conv.", h, C, c.kernel_size, 1, true))) return rc;
+    e->dec_up.resize(n);
+    e->dec_res3.resize(n);
+    e->dec_res1.resize(n);
+    int idx = 1;
+    for (int s = 0; s < n; ++s) {
+        const int r = c.upsampling_ratios[s];
+        idx += 1;
+        const std::string u = "decoder.layers." + std::to_string(idx) + ".conv.";
+        std::vector<float>*w, *b;
+        if ((rc = get_w(e, u + "weight", &w)) || (rc = get_w(e, u + "bias", &b))) return rc;
+        const int cin = C, cout = C / 2;
+        std::vector<float> wl((size_t)r * cout * 2 * cin), bl((size_t)r * cout);
+        relayout_upconv(w->data(), cin, cout, r, wl.data());
+        for (int p = 0; p < r; ++p)
+            for (int co = 0; co < cout; ++co) bl[(size_t)p * cout + co] = (*b)[co];
+        DevConv& dc = e->dec_up[s];
+        dc.cin = cin;
+        dc.cout = r * cout;
+        dc.k = 2;
+        dc.stride = 1;
+        if ((rc = upload(e, &dc.w, wl)) || (rc = upload(e, &dc.b, bl))) return rc;
+        idx += 1;
+        C = cout;
+        const std::string p = "decoder.layers." + std::to_string(idx) + ".block.";
+        if ((rc = make_conv(e, e->dec_res3[s], p + "1.conv.", C, C / c.compress, c.residual_kernel_size, 1, true))) return rc;
+        if ((rc = make_conv(e, e->dec_res1[s], p + "3.conv.", C / c.compress, C, 1, 1, true))) return rc;
+        idx += 1;
+    }
+    idx += 1;
+    if ((rc = make_conv(e, e->dec_last, "decoder.layers." + std::to_string(idx) + ".conv.", C, 1, c.last_kernel_size, 1, true)))
+        return rc;
+    std::vector<float>* t;
+    if ((rc = get_w(e, "upsample.conv.weight", &t)) || (rc = upload(e, &e->upsample_w, *t))) return rc;
+    e->dxf.resize(c.num_hidden_layers);
+    for (int l = 0; l < c.num_hidden_layers; ++l) {
+        const std::string p = "decoder_transformer.layers." + std::to_string(l) + ".";
+        DevXfmr& x = e->dxf[l];
+        std::vector<float>*q, *k, *v;
+        if ((rc = get_w(e, p + "self_attn.q_proj.weight", &q)) || (rc = get_w(e, p + "self_attn.k_proj.weight", &k)) ||
+            (rc = get_w(e, p + "self_attn.v_proj.weight", &v)))
+            return rc;
+        std::vector<float> qkv(*q);
+        qkv.insert(qkv.end(), k->begin(), k->end());
+        qkv.insert(qkv.end(), v->begin(), v->end());
+        if ((rc = upload(e, &x.wqkv, qkv))) return rc;
+        struct {
+            const char* n;
+            float** d;
+        } simple[] = {{"self_attn.o_proj.weight", &x.wo},
+                      {"mlp.fc1.weight", &x.w1},
+                      {"mlp.fc2.weight", &x.w2},
+                      {"input_layernorm.weight", &x.ln1_w},
+                      {"input_layernorm.bias", &x.ln1_b},
+                      {"post_attention_layernorm.weight", &x.ln2_w},
+                      {"post_attention_layernorm.bias", &x.ln2_b},
+                      {"self_attn_layer_scale.scale", &x.ls1},
+                      {"mlp_layer_scale.scale", &x.ls2}};
+        for (auto& sp : simple)
+            if ((rc = get_w(e, p + sp.n, &t)) || (rc = upload(e, sp.d, *t))) return rc;
+    }
+    {
+        // [W_sem | W_ac] along K: one GEMM computes output_proj_sem(sem) + output_proj_ac(ac)
+        std::vector<float>*ps, *pa;
+        if ((rc = get_w(e, "quantizer.semantic_residual_vector_quantizer.output_proj.weight", &ps)) ||
+            (rc = get_w(e, "quantizer.acoustic_residual_vector_quantizer.output_proj.weight", &pa)))
+            return rc;
+        const int Dq = c.vq_hidden_dim;
+        std::vector<float> both((size_t)h * 2 * Dq);
+        for (int o = 0; o < h; ++o)
+            for (int d = 0; d < Dq; ++d) {
+                both[(size_t)o * 2 * Dq + d] = (*ps)[(size_t)o * Dq + d];
+                both[(size_t)o * 2 * Dq + Dq + d] = (*pa)[(size_t)o * Dq + d];
+            }
+        if ((rc = upload(e, &e->outproj, both))) return rc;
+    }
+    if ((rc = dev_alloc(e, reinterpret_cast<void**>(&e->dec_flag), 256))) return rc;
+    HIP_TRY(hipMemset(e->dec_flag, 0, 256));
+    HIP_TRY(hipHostMalloc(&e->dec_flag_host, sizeof(unsigned), hipHostMallocDefault));
+    return MIMI_OK;
+}
+
+// decode's workspace: two ping-pong regions (P: RVQ sums + embedding, then the SEANet's ELU'd tensors; Q: the
+// transformer's buffers, then the raw up-conv outputs) and, with taps on, the raw decoder.layers.0 output
+struct DecodeWs {
+    float *p, *q, *tap;
+    size_t bytes;
+};
+static DecodeWs decode_ws_layout(const mimi_engine* e, int B, int64_t T, bool taps) {
+    const mimi_config& c = e->cfg;
+    const size_t h = c.hidden_size, T2 = 2 * (size_t)T;
+    size_t C = (size_t)c.num_filters << c.num_ratios, len = T2;
+    size_t pmax = std::max((size_t)T * (h + 2 * c.vq_hidden_dim), T2 * C);
+    size_t qmax = T2 * (3 * h + 3 * (size_t)c.num_attention_heads * c.head_dim + c.intermediate_size);
+    for (int s = 0; s < c.num_ratios; ++s) {
+        len *= c.upsampling_ratios[s];
+        C /= 2;
+        pmax = std::max(pmax, len * C);
+        qmax = std::max(qmax, len * C);
+    }
+    auto pad = [](size_t floats) { return (floats * sizeof(float) + 255) / 256 * 256; };
+    DecodeWs w{};
+    char* base = reinterpret_cast<char*>(e->dws);
+    size_t off = 0;
+    w.p = reinterpret_cast<float*>(base + off);
+    off += pad(pmax * B);
+    w.q = reinterpret_cast<float*>(base + off);
+    off += pad(qmax * B);
+    w.tap = reinterpret_cast<float*>(base + off);
+    if (taps) off += pad(T2 * ((size_t)c.num_filters << c.num_ratios) * B);
+    w.bytes = off;
+    return w;
+}
+
+static int ensure_dws(mimi_engine* e, size_t bytes) {
+    if (bytes <= e->dws_bytes) return MIMI_OK;
+    // (every decode synchronises its stream before it returns: nothing reads the old buffer)
+    if (e->dws) {
+        HIP_TRY(hipFree(e->dws));
+        e->dws = nullptr;
+        e->dws_bytes = 0;
+    }
+    hipError_t err = hipMalloc(&e->dws, bytes);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        e->dws = nullptr;
+        return set_err(err == hipErrorOutOfMemory ? MIMI_ERR_OUT_OF_MEMORY : MIMI_ERR_HIP,
+                       "decode workspace hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(err));
+    }
+    e->dws_bytes = bytes;
+    return MIMI_OK;
+}
+
+extern "C" int64_t mimi_decode_workspace_bytes(const mimi_engine* e, int32_t batch, int64_t frames) {
+    if (!e || batch <= 0 || frames <= 0) return -1;
+    return (int64_t)decode_ws_layout(e, batch, frames, e->taps).bytes;
+}
+
+// codes -> (semantic | acoustic) sums in `sums` -> embedding [frames][hidden] in `emb`
+static int run_dequantize(mimi_engine* e, const int32_t* codes, int64_t frames, int frames_per_item, int K, float* sums,
+                          float* emb, hipStream_t s, Recorder& rec) {
+    const mimi_config& c = e->cfg;
+    const int Dq = c.vq_hidden_dim;
+    LAUNCH_TRY(launch_rvq_decode(codes, frames, frames_per_item, K, c.num_semantic_quantizers, c.codebook_size,
+                                 c.codebook_dim, e->cb_rows, sums, e->dec_flag, s),
+               "rvq_decode");
+    rec.mark("dec_rvq", (double)frames * K * Dq, (double)frames * (K * Dq + 2 * Dq) * 4, "mimi::rvq_decode_kernel");
+    GemmArgs ap = linear_args(sums, frames, 2 * Dq, e->outproj, c.hidden_size, emb);
+    const char* kname = "?";
+    LAUNCH_TRY(launch_gemm(ROLE_INPROJ, ap, s, &kname, PREC_F32), "output_proj");
+    rec.mark("dec_output_proj", 2.0 * frames * 2 * Dq * c.hidden_size, (double)frames * (2 * Dq + c.hidden_size) * 4, kname);
+    return MIMI_OK;
+}
+
+// the bounds flag of the decode just enqueued on s (synchronises s)
+static int read_decode_flag(mimi_engine* e, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(e->dec_flag_host, e->dec_flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (*e->dec_flag_host)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "code outside [0, codebook_size): [0, %d)", e->cfg.codebook_size);
+    return MIMI_OK;
+}
+
+static int check_decode_state(mimi_engine* e, int32_t K) {
+    if (!e->finalized) return set_err(MIMI_ERR_STATE, "mimi_finalize has not been called");
+    if (!e->decode_enabled)
+        return set_err(MIMI_ERR_STATE, "engine was built without the decode weights (mimi_enable_decode / MIMI_CREATE_DECODE)");
+    if (K < 1 || K > e->levels_available)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "num_quantizers %d outside [1, %d]", K, e->levels_available);
+    return MIMI_OK;
+}
+
+extern "C" int mimi_rvq_decode(mimi_engine* e, const int32_t* dev_codes, int64_t frames, int32_t K, float* dev_embedding,
+                               void* stream) {
+    if (!e) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null engine");
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = check_decode_state(e, K);
+    if (rc) return rc;
+    if (frames <= 0 || frames > 0x7fffffffLL || !dev_codes || !dev_embedding)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "frames=%lld", (long long)frames);
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if ((rc = ensure_dws(e, ((size_t)frames * 2 * e->cfg.vq_hidden_dim * sizeof(float) + 255) / 256 * 256))) return rc;
+    HIP_TRY(hipMemsetAsync(e->dec_flag, 0, sizeof(unsigned), s));
+    Recorder rec{e, s};
+    rec.begin();
+    if ((rc = run_dequantize(e, dev_codes, frames, (int)frames, K, reinterpret_cast<float*>(e->dws), dev_embedding, s, rec)))
+        return rc;
+    return read_decode_flag(e, s);
+}
+
+// The decoder transformer: the encoder's fp32 launches (LayerNorm, q/k/v + RoPE, attention, o_proj, fc1, fc2) on the
+// weight set xf over B items of T rows, residual stream in t0 (in place)
+static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, int B, int64_t T, float* t0, float* t1,
+                               float* qkv, float* att, float* ff, hipStream_t s, Recorder& rec, const char* stage_prefix) {
+    const mimi_config& c = e->cfg;
+    const int Hd = c.hidden_size, H = c.num_attention_heads, Dh = c.head_dim;
+    const int64_t rows = (int64_t)B * T;
+    const std::string sp = stage_prefix;
+    const char* kname = "?";
+    double att_flops = 0;
+    for (int64_t i = 0; i < T; ++i) att_flops += 4.0 * Dh * std::min<int64_t>(i + 1, c.sliding_window);
+    att_flops *= (double)H * B;
+    auto fl = [](const GemmArgs& a) { return 2.0 * a.batch * (double)a.M * a.N * a.K; };
+    auto by = [](const GemmArgs& a, bool res) {
+        return ((double)a.batch * a.M * (a.K + a.N * (res ? 2 : 1)) + (double)a.N * a.K) * 4;
+    };
+    for (size_t l = 0; l < xf.size(); ++l) {
+        const DevXfmr& x = xf[l];
+        LAUNCH_TRY(launch_layernorm(t0, x.ln1_w, x.ln1_b, t1, rows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f, nullptr,
+                                    nullptr, 0, e->ln_rpw),
+                   "ln1");
+        rec.mark(sp + "layernorm", 0, 2.0 * rows * Hd * 4, ln_kname(e->ln_rpw));
+        GemmArgs aq = linear_args(t1, T, Hd, x.wqkv, 3 * H * Dh, qkv);
+        aq.batch = B;
+        aq.a_bstride = T * Hd;
+        aq.c_bstride = T * 3 * H * Dh;
+        aq.rope_cos = e->rope_cos;
+        aq.rope_sin = e->rope_sin;
+        aq.rope_cols = 2 * H * Dh;
+        LAUNCH_TRY(launch_gemm(ROLE_QKV, aq, s, &kname, PREC_F32), "qkv");
+        rec.mark(sp + "qkv", fl(aq), by(aq, false), kname);
+        const char* akn = T <= 256 ? "mimi::attention_t256_kernel" : "mimi::attention_kernel";
+        LAUNCH_TRY(launch_attention(qkv, att, B, (int)T, H, Dh, c.sliding_window, 1.0f / std::sqrt((float)Dh), s, att,
+                                    rows * Hd, 0, 0.0f, nullptr, false, nullptr, 0, 0, nullptr, &akn, e->attn_band_split),
+                   "attention");
+        rec.mark(sp + "attention", att_flops, (double)rows * 4 * Hd * 4, akn);
+        GemmArgs ao = linear_args(att, rows, H * Dh, x.wo, Hd, t0);
+        ao.R = t0;
+        ao.scale = x.ls1;
+        LAUNCH_TRY(launch_gemm(ROLE_OPROJ, ao, s, &kname, PREC_F32), "o_proj");
+        rec.mark(sp + "o_proj", fl(ao), by(ao, true), kname);
+        LAUNCH_TRY(launch_layernorm(t0, x.ln2_w, x.ln2_b, t1, rows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f, nullptr,
+                                    nullptr, 0, e->ln_rpw),
+                   "ln2");
+        rec.mark(sp + "layernorm", 0, 2.0 * rows * Hd * 4, ln_kname(e->ln_rpw));
+        GemmArgs a1 = linear_args(t1, rows, Hd, x.w1, c.intermediate_size, ff);
+        LAUNCH_TRY(launch_gemm(ROLE_FC1, a1, s, &kname, PREC_F32), "fc1");
+        rec.mark(sp + "fc1", fl(a1), by(a1, false), kname);
+        GemmArgs a2 = linear_args(ff, rows, c.intermediate_size, x.w2, Hd, t0);
+        a2.R = t0;
+        a2.scale = x.ls2;
+        LAUNCH_TRY(launch_gemm(ROLE_FC2, a2, s, &kname, PREC_F32), "fc2");
+        rec.mark(sp + "fc2", fl(a2), by(a2, true), kname);
+    }
+    return MIMI_OK;
+}
+
+extern "C" int mimi_decode(mimi_engine* e, const int32_t* dev_codes, int32_t batch, int64_t frames, int32_t K,
+                           float* dev_audio, void* stream) {
+    if (!e) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null engine");
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = check_decode_state(e, K);
+    if (rc) return rc;
+    const mimi_config& c = e->cfg;
+    const int64_t up = decode_upsampling(c);
+    if (batch <= 0 || batch > 65535 || frames <= 0 || !dev_codes || !dev_audio)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "batch=%d frames=%lld", batch, (long long)frames);
+    // the GEMMs index an item's rows with 32-bit M and the rvq kernel B * T frames with 32-bit blocks
+    if (frames * up > 0x7fffffffLL || (int64_t)batch * frames > 0x7fffffffLL)
+        return set_err(MIMI_ERR_UNSUPPORTED, "decode of %lld frames per item exceeds the 32-bit row range", (long long)frames);
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int B = batch;
+    const int64_t T = frames, T2 = 2 * frames;
+    if ((rc = ensure_dws(e, decode_ws_layout(e, B, T, e->taps).bytes))) return rc;
+    const DecodeWs w = decode_ws_layout(e, B, T, e->taps);
+    if ((rc = ensure_rope(e, T2))) return rc;
+    const int Hd = c.hidden_size, Dq = c.vq_hidden_dim;
+    HIP_TRY(hipMemsetAsync(e->dec_flag, 0, sizeof(unsigned), s));
+    Recorder rec{e, s};
+    rec.begin();
+    const char* kname = "?";
+    auto fl = [](const GemmArgs& a) { return 2.0 * a.batch * (double)a.M * a.N * a.K; };
+    auto by = [](const GemmArgs& a) { return ((double)a.batch * a.M * (a.a_rs + a.N) + (double)a.N * a.K) * 4; };
+
+    // ---- quantizer.decode + upsample ----
+    float* sums = w.p;
+    float* emb = w.p + (size_t)B * T * 2 * Dq;
+    if ((rc = run_dequantize(e, dev_codes, (int64_t)B * T, (int)T, K, sums, emb, s, rec))) return rc;
+    if ((rc = save_tap(e, "quantized", emb, B, T, Hd, s))) return rc;
+    float* t0 = w.q;
+    float* t1 = t0 + (size_t)B * T2 * Hd;
+    float* qkv = t1 + (size_t)B * T2 * Hd;
+    float* att = qkv + (size_t)B * T2 * 3 * c.num_attention_heads * c.head_dim;
+    float* ff = att + (size_t)B * T2 * Hd;
+    LAUNCH_TRY(launch_upsample_dw(emb, e->upsample_w, t0, B, T, Hd, s), "upsample");
+    rec.mark("dec_upsample", 4.0 * B * T2 * Hd, 3.0 * B * T * Hd * 4, "mimi::upsample_dw_kernel");
+    if ((rc = save_tap(e, "upsample", t0, B, T2, Hd, s))) return rc;
+
+    // ---- decoder transformer ----
+    if ((rc = run_transformer_f32(e, e->dxf, B, T2, t0, t1, qkv, att, ff, s, rec, "dec_"))) return rc;
+    char nm[64];
+    snprintf(nm, sizeof nm, "xfmr%d", c.num_hidden_layers - 1);
+    if ((rc = save_tap(e, nm, t0, B, T2, Hd, s))) return rc;
+
+    // ---- SEANet decoder ----
+    int C = c.num_filters << c.num_ratios;
+    if (e->taps) {  // the raw layer-0 output (the pass itself only needs its ELU)
+        GemmArgs at = conv_args(e->dec_first, t0, T2, w.tap, T2, B);
+        LAUNCH_TRY(launch_gemm(ROLE_DOWN, at, s, &kname, PREC_F32), "decoder conv 0 (tap)");
+        if ((rc = save_tap(e, "dconv0", w.tap, B, T2, C, s))) return rc;
+    }
+    float* xe = w.p;  // ELU'd input of the next up conv
+    GemmArgs a0 = conv_args(e->dec_first, t0, T2, xe, T2, B);
+    LAUNCH_TRY(launch_gemm(ROLE_DOWN_ELU, a0, s, &kname, PREC_F32), "decoder conv 0");
+    rec.mark("dec_conv0", fl(a0), by(a0), kname);
+    int64_t len = T2;
+    for (int si = 0; si < c.num_ratios; ++si) {
+        const int r = c.upsampling_ratios[si];
+        const DevConv& uc = e->dec_up[si];
+        // [len][C] -> [len][r * C/2] = [len * r][C/2]
+        GemmArgs au = conv_args(uc, xe, len, w.q, len, B);
+        LAUNCH_TRY(launch_gemm(ROLE_UPCONV, au, s, &kname, PREC_F32), "up conv");
+        snprintf(nm, sizeof nm, "dec_up_s%d", si);
+        rec.mark(nm, fl(au), by(au), kname);
+        len *= r;
+        C /= 2;
+        snprintf(nm, sizeof nm, "up%d", si);
+        if ((rc = save_tap(e, nm, w.q, B, len, C, s))) return rc;
+        ResArgs ra{};
+        ra.x = w.q;
+        ra.T = len;
+        ra.batch = B;
+        ra.w3 = e->dec_res3[si].w;
+        ra.b3 = e->dec_res3[si].b;
+        ra.w1 = e->dec_res1[si].w;
+        ra.b1 = e->dec_res1[si].b;
+        ra.y = xe;
+        LAUNCH_TRY(launch_resblock(C, ra, s, &kname), "decoder resblock");
+        snprintf(nm, sizeof nm, "dec_res_s%d", si);
+        const double Hh = C / c.compress;
+        rec.mark(nm, 2.0 * B * len * (3.0 * C * Hh + Hh * C), (double)B * len * 2 * C * 4, kname);
+        snprintf(nm, sizeof nm, "dres%d_elu", si);
+        if ((rc = save_tap(e, nm, xe, B, len, C, s))) return rc;
+    }
+    LAUNCH_TRY(launch_final_conv(xe, e->dec_last.w, e->dec_last.b, dev_audio, B, len, C, c.last_kernel_size, s),
+               "final conv");
+    rec.mark("dec_final", 2.0 * B * len * C * c.last_kernel_size, (double)B * len * (C + 1) * 4, "mimi::final_conv_kernel");
+    if ((rc = save_tap(e, "audio", dev_audio, B, len, 1, s))) return rc;
+    return read_decode_flag(e, s);
+}
+
 extern "C" void mimi_destroy(mimi_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
@@ -2544,6 +3034,8 @@ extern "C" void mimi_destroy(mimi_engine* e) {
     if (e->amax_dev) (void)hipFree(e->amax_dev);
     if (e->amax_host) (void)hipHostFree(e->amax_host);
     if (e->item_codes) (void)hipFree(e->item_codes);
+    if (e->dws) (void)hipFree(e->dws);
+    if (e->dec_flag_host) (void)hipHostFree(e->dec_flag_host);
     for (auto& q : e->pend) {
         if (q.done) (void)hipEventDestroy(q.done);
         if (q.amax) (void)hipHostFree(q.amax);

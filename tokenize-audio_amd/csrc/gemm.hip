@@ -448,6 +448,7 @@ static hipError_t dispatch(int role, const GemmArgs& a, hipStream_t s) {
                 return run_split<64, 64, 1, 2, 3, false, PAD_REPLICATE, EPI_NONE, 9>(a, s);
             return run_prec<false, PAD_REPLICATE, EPI_NONE, 9>(a, s, g_prec);
         case ROLE_INPROJ: return run_auto<false, PAD_ZERO, EPI_NONE, 10>(a, s);
+        case ROLE_UPCONV: return run_auto<false, PAD_ZERO, EPI_BIAS, 14>(a, s);  // decode: fp32 MFMA whatever the mode
         default: return hipErrorInvalidValue;
     }
 }

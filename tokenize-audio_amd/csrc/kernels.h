@@ -271,6 +271,8 @@ enum GemmRole : int {
     ROLE_DOWN_XE,    // planes path: bias, fp32 out (the residual skip) + ELU(out) planes (the next conv3 input)
     ROLE_RES3P,      // planes path, unfused residual block: k3 conv, bias + ELU -> h planes
     ROLE_RES1P,      // planes path, unfused residual block: k1 conv, bias + skip + ELU -> y planes
+    ROLE_UPCONV,     // decode: a transposed conv (k = 2r, stride r) as a causal k = 2 conv with r * Cout phase-major
+                     // output channels; bias, raw fp32 output (the next residual block's skip); fp32 activations in
     ROLE_COUNT
 };
 // Arithmetic of the GEMMs: fp32 MFMA, or fp32 emulated on the bf16 matrix cores with 3 (6 products) or
@@ -450,6 +452,17 @@ size_t rvq_work_bytes(long long frames);
 // bytes from *chain_flag the caller zeroes before every launch (a captured graph's replays: set_io_kernel)
 hipError_t launch_rvq(const RvqArgs& a, hipStream_t s, const char** kname = nullptr, unsigned** chain_flag = nullptr,
                       size_t* clear_bytes = nullptr);
+
+// Decode path (decode.hip).  launch_rvq_decode: codes [B][K][T] (frames = B * T, frames_per_item = T) -> out
+// [frames][2 * D] = (semantic sum | acoustic sum) of cb_rows ([level][ncodes][D]) in level order; a code outside
+// [0, ncodes) is never used as an index: it raises *flag (device word, zeroed by the caller) and row 0 is read.
+hipError_t launch_rvq_decode(const int32_t* codes, long long frames, int frames_per_item, int K, int nsem, int ncodes,
+                             int D, const float* cb_rows, float* out, unsigned* flag, hipStream_t s);
+// depthwise causal transposed conv (k = 4, stride 2, no bias): x [B][T][C] -> y [B][2T][C]; w [C][4]
+hipError_t launch_upsample_dw(const float* x, const float* w, float* y, int batch, long long T, int C, hipStream_t s);
+// the decoder's last conv (k = 3, causal, 64 -> 1): x [B][L][64] already ELU'd, w [3][64] tap-major, y [B][L]
+hipError_t launch_final_conv(const float* x, const float* w, const float* bias, float* y, int batch, long long L, int C,
+                             int ksize, hipStream_t s);
 
 // polyphase resampler (resample.hip): clips packed at in_off / out_off (device int64 arrays), one launch
 hipError_t launch_resample_poly(const float* x, const long long* in_off, const long long* in_len, int nclips,

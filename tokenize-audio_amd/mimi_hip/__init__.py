@@ -3,18 +3,19 @@
     from mimi_hip import MimiEncoder                 # replaces the scripts' `class MimiEncoder`
     from mimi_hip import MimiHipModel                # replaces transformers.MimiModel for .encode
     from mimi_hip import codes_to_chars              # replaces utils.codes_to_chars
+    from mimi_hip import audio_to_str, str_to_audio  # replace utils.audio_to_str / utils.str_to_audio (decode=True)
 
 torch is imported lazily by the model modules; ``mimi_hip.config`` / ``mimi_hip.synthetic`` / ``mimi_hip.codes``
 need only numpy.
 """
 from .config import MimiConfig, encoded_length  # noqa: F401
 
-__all__ = ["MimiConfig", "encoded_length", "MimiHipModel", "MimiEncoderOutput", "MimiEncoder",
-           "MimiFeatureExtractor", "codes_to_chars", "chars_to_codes", "audio_to_str"]
+__all__ = ["MimiConfig", "encoded_length", "MimiHipModel", "MimiEncoderOutput", "MimiDecoderOutput",
+           "MimiEncoder", "MimiFeatureExtractor", "codes_to_chars", "chars_to_codes", "audio_to_str", "str_to_audio"]
 
 
 def __getattr__(name):
-    if name in ("MimiHipModel", "MimiEncoderOutput"):
+    if name in ("MimiHipModel", "MimiEncoderOutput", "MimiDecoderOutput"):
         from . import model
         return getattr(model, name)
     if name == "MimiEncoder":
@@ -23,7 +24,7 @@ def __getattr__(name):
     if name == "MimiFeatureExtractor":
         from .feature_extraction import MimiFeatureExtractor
         return MimiFeatureExtractor
-    if name in ("codes_to_chars", "chars_to_codes", "audio_to_str"):
+    if name in ("codes_to_chars", "chars_to_codes", "audio_to_str", "str_to_audio"):
         from . import codes
         return getattr(codes, name)
     raise AttributeError(name)

@@ -30,7 +30,10 @@ EXPORTED_SYMBOLS = (
     "mimi_profile_reset", "mimi_profile_sequence", "mimi_set_taps", "mimi_get_tap", "mimi_resample_poly",
     "mimi_bpe_create", "mimi_bpe_best", "mimi_bpe_merge", "mimi_bpe_destroy", "mimi_flac_info", "mimi_flac_decode",
     "mimi_split_check", "mimi_gelu_check",
+    "mimi_enable_decode", "mimi_create_from_dir_flags", "mimi_decoded_length", "mimi_decoded_length_cfg", "mimi_decode",
+    "mimi_rvq_decode", "mimi_decode_workspace_bytes", "mimi_upconv_relayout",
 )
+CREATE_DECODE = 1  # MIMI_CREATE_DECODE
 RESAMPLE_MAX_TAPS = 65536  # MIMI_RESAMPLE_MAX_TAPS
 
 
@@ -123,6 +126,14 @@ def _declare(lib):
         "mimi_flac_decode": (c.c_int, [vp, c.c_int64, vp, c.c_int64, c.POINTER(c.c_int64)]),
         "mimi_split_check": (c.c_int, [vp, c.c_int64, c.c_float, vp, vp]),
         "mimi_gelu_check": (c.c_int, [vp, c.c_int64, vp, vp]),
+        "mimi_enable_decode": (c.c_int, [vp]),
+        "mimi_create_from_dir_flags": (c.c_int, [c.c_char_p, c.c_int, c.c_uint32, c.POINTER(vp)]),
+        "mimi_decoded_length": (c.c_int64, [c.c_int64]),
+        "mimi_decoded_length_cfg": (c.c_int64, [c.POINTER(MimiConfigC), c.c_int64]),
+        "mimi_decode": (c.c_int, [vp, vp, c.c_int32, c.c_int64, c.c_int32, vp, vp]),
+        "mimi_rvq_decode": (c.c_int, [vp, vp, c.c_int64, c.c_int32, vp, vp]),
+        "mimi_decode_workspace_bytes": (c.c_int64, [vp, c.c_int32, c.c_int64]),
+        "mimi_upconv_relayout": (c.c_int, [vp, c.c_int32, c.c_int32, c.c_int32, vp]),
         "mimi_resample_poly": (c.c_int, [vp, vp, vp, c.c_int32, vp, vp, vp, c.c_int64, vp, c.c_int32, c.c_int32,
                                          c.c_int32, c.c_int64, vp]),
     }

@@ -73,3 +73,14 @@ def audio_to_str(audio_numpy: np.ndarray, mimi_model, device: str) -> str:
     codes = audio_codes[0][0].cpu()
     codes = codes[:NUM_CODEBOOKS, :]
     return codes_to_chars(codes, codebook_size=CODEBOOK_SIZE)
+
+
+def str_to_audio(audio_str: str, mimi_model, device: str) -> np.ndarray:
+    """``utils.str_to_audio`` (``librispeech-mimi/utils.py:72-81``) over the HIP model (built with ``decode=True``):
+    the string's code points back to codes ``[1, 8, T]``, decoded; returns the ``[1, 1920 T]`` float32 array the
+    reference returns (``.audio_values[0]``)."""
+    codes = chars_to_codes(audio_str, num_codebooks=NUM_CODEBOOKS, codebook_size=CODEBOOK_SIZE, return_tensors="pt")
+    codes = codes.to(device).unsqueeze(0)
+    with torch.no_grad():
+        audio_decoded = mimi_model.decode(codes).audio_values[0]
+    return audio_decoded.cpu().numpy()

@@ -1,4 +1,4 @@
-"""``MimiHipModel``: the ``MimiModel.encode`` drop-in over the HIP engine.
+"""``MimiHipModel``: the ``MimiModel.encode`` / ``MimiModel.decode`` drop-in over the HIP engine.
 
 Mirrors the model-level API every reference wrapper calls:
 
@@ -8,6 +8,9 @@ Mirrors the model-level API every reference wrapper calls:
   ``TF/modeling_mimi.py:1297-1386``: K defaults to ``config.num_quantizers`` (32), ``ValueError`` for
   K > 32 and for channels not in {1, 2}; ``padding_mask`` is accepted and ignored exactly as there
   (``:1244, :1247``).
+* ``model.decode(audio_codes[B, K, T], padding_mask=None)`` (models built with ``decode=True``) ->
+  ``MimiDecoderOutput`` with ``.audio_values`` float32 ``[B, 1, 1920 T]`` on the model's device
+  (``TF/modeling_mimi.py:1408-1458``; ``librispeech-mimi/utils.py:72-81`` does ``.audio_values[0]``).
 * ``.to(device)``, ``.eval()``, ``get_encoded_length``, ``from_pretrained(local_dir | "kyutai/mimi")``.
 
 The arithmetic runs in ``libmimi_hip.so`` (HIP kernels for gfx950); torch only supplies device memory and
@@ -39,6 +42,27 @@ class MimiEncoderOutput:
     def to_tuple(self):
         return tuple(v for v in (self.audio_codes, self.encoder_past_key_values, self.padding_cache)
                      if v is not None)
+
+    def __getitem__(self, i):
+        if isinstance(i, str):
+            return getattr(self, i)
+        return self.to_tuple()[i]
+
+    def __iter__(self):
+        return iter(self.to_tuple())
+
+    def __len__(self):
+        return len(self.to_tuple())
+
+
+@dataclass
+class MimiDecoderOutput:
+    """Same fields as ``transformers`` ``MimiDecoderOutput`` (``TF/modeling_mimi.py:190-207``)."""
+    audio_values: torch.Tensor
+    decoder_past_key_values: Optional[object] = None
+
+    def to_tuple(self):
+        return tuple(v for v in (self.audio_values, self.decoder_past_key_values) if v is not None)
 
     def __getitem__(self, i):
         if isinstance(i, str):
@@ -104,10 +128,13 @@ class EncodeTicket:
 
 
 class MimiHipModel:
-    """Encode-only Mimi on MI355X."""
+    """Mimi on MI355X: encode always; decode (codes -> waveform) when built with ``decode=True``, which makes the
+    decoder half of the checkpoint (``decoder*``, ``upsample*``, ``decoder_transformer*``, ``output_proj``) required.
+    Decode runs in fp32-MFMA arithmetic whatever ``set_precision`` says."""
 
     def __init__(self, state_dict: Optional[Dict[str, np.ndarray]] = None, config: Optional[MimiConfig] = None,
-                 device: Union[str, torch.device] = "cuda", safetensors_path: Optional[str] = None):
+                 device: Union[str, torch.device] = "cuda", safetensors_path: Optional[str] = None,
+                 decode: bool = False):
         self.config = config or MimiConfig()
         self.config.validate_supported()
         self._lib = _lib.load()
@@ -118,12 +145,15 @@ class MimiHipModel:
         self._h = handle
         self._lock = threading.Lock()
         self._src = (state_dict, config, safetensors_path)  # for clone()
+        self.decode_enabled = bool(decode)
         try:
+            if decode:
+                _lib.check(self._lib.mimi_enable_decode(self._h))
             if safetensors_path is not None:
                 _lib.check(self._lib.mimi_load_safetensors(self._h, safetensors_path.encode()))
             if state_dict is not None:
                 for name, value in state_dict.items():
-                    if name.startswith(("decoder", "upsample")):
+                    if not decode and name.startswith(("decoder", "upsample")):
                         continue
                     arr = value.detach().cpu().numpy() if torch.is_tensor(value) else np.asarray(value)
                     arr = np.ascontiguousarray(arr, dtype=np.float32)
@@ -135,11 +165,15 @@ class MimiHipModel:
 
     # ---- construction helpers -------------------------------------------------------------------
     @classmethod
-    def from_pretrained(cls, name_or_path: str = "kyutai/mimi", device="cuda", **kw) -> "MimiHipModel":
+    def from_pretrained(cls, name_or_path: str = "kyutai/mimi", device="cuda", decode: bool = False,
+                        **kw) -> "MimiHipModel":
         if name_or_path.startswith("synthetic"):
             from . import synthetic
             seed = int(name_or_path.split(":", 1)[1]) if ":" in name_or_path else 0
-            return cls(synthetic.make_state_dict(seed=seed), device=device)
+            sd = synthetic.make_state_dict(seed=seed)
+            if decode:
+                sd.update(synthetic.make_decoder_state_dict(seed=seed))
+            return cls(sd, device=device, decode=decode)
         path = resolve_checkpoint(name_or_path)
         cfg = MimiConfig()
         if os.path.isdir(path):
@@ -149,13 +183,14 @@ class MimiHipModel:
             if not files:
                 raise FileNotFoundError(f"no .safetensors file in {path}")
             path = files[0]
-        return cls(config=cfg, device=device, safetensors_path=path, **kw)
+        return cls(config=cfg, device=device, safetensors_path=path, decode=decode, **kw)
 
     def clone(self, device: Union[str, torch.device, None] = None) -> "MimiHipModel":
         """Another engine with the same weights and config (its own workspace; same calibration, so the same codes):
         independent encodes on several engines run concurrently (``MimiEncoder.encode_audio_chunks``)."""
         sd, cfg, path = self._src
-        m = MimiHipModel(sd, config=cfg or self.config, device=device or self.device, safetensors_path=path)
+        m = MimiHipModel(sd, config=cfg or self.config, device=device or self.device, safetensors_path=path,
+                         decode=self.decode_enabled)
         m.set_precision(self.precision)
         return m
 
@@ -324,6 +359,69 @@ class MimiHipModel:
             _lib.check(self._lib.mimi_rvq_encode(self._h, ctypes.c_void_p(emb.data_ptr()), B * T, num_quantizers,
                                                  ctypes.c_void_p(codes.data_ptr()), self._stream()))
         return codes.view(num_quantizers, B, T).permute(1, 0, 2).long()
+
+    # ---- decode --------------------------------------------------------------------------------
+    def get_decoded_length(self, frames: int) -> int:
+        n = 2 * int(frames)
+        for r in self.config.upsampling_ratios:
+            n *= r
+        return n
+
+    def _require_decode(self):
+        if not self.decode_enabled:
+            raise RuntimeError("this MimiHipModel holds the encode path only: construct it with decode=True "
+                               "(MimiHipModel(..., decode=True) / from_pretrained(..., decode=True)) to decode")
+
+    def decode(self, audio_codes: torch.Tensor, padding_mask: Optional[torch.Tensor] = None,
+               decoder_past_key_values=None, return_dict: Optional[bool] = None):
+        """``MimiModel.decode`` (``TF/modeling_mimi.py:1408-1458``): int64 / int32 codes ``[B, K, T]`` on any device
+        -> ``MimiDecoderOutput(audio_values [B, 1, 1920 T] float32 on the model's device, None)``; truncated to
+        ``padding_mask.shape[-1]`` when that is shorter (``:1446-1447``)."""
+        self._require_decode()
+        if decoder_past_key_values is not None:
+            raise NotImplementedError("streaming decode (KV cache) is not on the batch path")
+        if not torch.is_tensor(audio_codes):
+            audio_codes = torch.as_tensor(np.asarray(audio_codes))
+        if audio_codes.dim() != 3:
+            raise ValueError(f"audio_codes must be [batch, num_quantizers, frames], got {tuple(audio_codes.shape)}")
+        B, K, T = audio_codes.shape
+        if K > self.config.num_quantizers or K < 1:
+            raise ValueError(f"The number of quantizers (i.e codebooks) must be in [1, {self.config.num_quantizers}], "
+                             f"but is currently {K}.")
+        audio = torch.empty((B, 1, self.get_decoded_length(T)), dtype=torch.float32, device=self.device)
+        if B and T:
+            codes = audio_codes.to(device=self.device, dtype=torch.int32).contiguous()
+            try:
+                _lib.check(self._lib.mimi_decode(self._h, ctypes.c_void_p(codes.data_ptr()), B, T, K,
+                                                 ctypes.c_void_p(audio.data_ptr()), self._stream()))
+            except _lib.MimiHipError as err:
+                if err.status == 1:  # MIMI_ERR_INVALID_ARGUMENT: a code outside [0, codebook_size), K over the levels
+                    raise ValueError(str(err)) from None
+                raise
+        if padding_mask is not None and padding_mask.shape[-1] < audio.shape[-1]:
+            audio = audio[..., : padding_mask.shape[-1]]
+        if return_dict is False:
+            return (audio, None)
+        return MimiDecoderOutput(audio)
+
+    def dequantize(self, codes: torch.Tensor) -> torch.Tensor:
+        """Quantizer decode alone (``mimi_rvq_decode``): codes [B, K, T] -> float32 embedding [B, 512, T], the mirror
+        of ``quantize``."""
+        self._require_decode()
+        B, K, T = codes.shape
+        if K > self.config.num_quantizers or K < 1:
+            raise ValueError(f"The number of quantizers (i.e codebooks) must be in [1, {self.config.num_quantizers}], "
+                             f"but is currently {K}.")
+        c = codes.to(device=self.device, dtype=torch.int32).permute(1, 0, 2).contiguous()  # [K][B * T]
+        emb = torch.empty((B * T, self.config.hidden_size), dtype=torch.float32, device=self.device)
+        try:
+            _lib.check(self._lib.mimi_rvq_decode(self._h, ctypes.c_void_p(c.data_ptr()), B * T, K,
+                                                 ctypes.c_void_p(emb.data_ptr()), self._stream()))
+        except _lib.MimiHipError as err:
+            if err.status == 1:
+                raise ValueError(str(err)) from None
+            raise
+        return emb.view(B, T, -1).permute(0, 2, 1)
 
     # ---- instrumentation ------------------------------------------------------------------------
     def set_precision(self, mode: str):

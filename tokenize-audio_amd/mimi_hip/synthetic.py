@@ -193,6 +193,73 @@ def make_state_dict(cfg: Optional[MimiConfig] = None, seed: int = 0,
     return sd
 
 
+def decoder_conv_specs(cfg: MimiConfig) -> List[dict]:
+    """The SEANet decoder convs in layer order with their HF parameter prefixes (``TF/modeling_mimi.py:931-961``):
+    layer 0 (hidden -> 16 x filters, k = 7), then per ratio ELU, a transposed conv (k = 2r, stride r, weight
+    ``[Cin][Cout][2r]``) and one residual block, then ELU and the last conv (filters -> 1, k = 3)."""
+    specs = []
+    scaling = 2 ** len(cfg.upsampling_ratios)
+    specs.append(dict(name="decoder.layers.0.conv", cin=cfg.hidden_size, cout=scaling * cfg.num_filters,
+                      k=cfg.kernel_size, kind="first"))
+    idx = 1
+    for ratio in cfg.upsampling_ratios:
+        c = scaling * cfg.num_filters
+        idx += 1  # ELU
+        specs.append(dict(name=f"decoder.layers.{idx}.conv", cin=c, cout=c // 2, k=2 * ratio, stride=ratio, kind="up"))
+        idx += 1
+        hidden = (c // 2) // cfg.compress
+        specs.append(dict(name=f"decoder.layers.{idx}.block.1.conv", cin=c // 2, cout=hidden,
+                          k=cfg.residual_kernel_size, kind="res3"))
+        specs.append(dict(name=f"decoder.layers.{idx}.block.3.conv", cin=hidden, cout=c // 2, k=1, kind="res1"))
+        idx += 1
+        scaling //= 2
+    idx += 1  # ELU
+    specs.append(dict(name=f"decoder.layers.{idx}.conv", cin=cfg.num_filters, cout=cfg.audio_channels,
+                      k=cfg.last_kernel_size, kind="last"))
+    return specs
+
+
+def make_decoder_state_dict(cfg: Optional[MimiConfig] = None, seed: int = 0) -> Dict[str, np.ndarray]:
+    """The decode-only parameters (``MimiModel.decode``: quantizer ``output_proj``, ``upsample``,
+    ``decoder_transformer``, ``decoder``) under their HF names and shapes, float32 numpy arrays; together with
+    ``make_state_dict`` (which holds the codebooks) a full ``MimiModel`` state dict.  The same counter-based
+    generators and He-style scales as the encode half: a transposed conv of stride r and kernel 2r sums 2 taps
+    per output step, so its fan-in is 2 Cin; the depthwise upsample's is 2."""
+    cfg = cfg or MimiConfig()
+    sd: Dict[str, np.ndarray] = {}
+    for s in decoder_conv_specs(cfg):
+        if s["kind"] == "up":
+            fan_in = 2 * s["cin"]
+            shape = (s["cin"], s["cout"], s["k"])
+        else:
+            fan_in = s["cin"] * s["k"]
+            shape = (s["cout"], s["cin"], s["k"])
+        gain = 1.0 if s["kind"] == "last" else 2.0
+        sd[s["name"] + ".weight"] = _uniform_std(shape, np.sqrt(gain / fan_in), seed, s["name"], "w")
+        sd[s["name"] + ".bias"] = _uniform_std((s["cout"],), 0.5 / np.sqrt(fan_in), seed, s["name"], "b")
+    h, inter = cfg.hidden_size, cfg.intermediate_size
+    us_k = 2 * int(cfg.encodec_frame_rate / cfg.frame_rate)
+    sd["upsample.conv.weight"] = _uniform_std((h, 1, us_k), np.sqrt(0.5), seed, "us")
+    for l in range(cfg.num_hidden_layers):
+        p = f"decoder_transformer.layers.{l}."
+        for nm in ("q_proj", "k_proj", "v_proj", "o_proj"):
+            sd[p + f"self_attn.{nm}.weight"] = _uniform_std((h, h), 1.0 / np.sqrt(h), seed, p, nm)
+        sd[p + "mlp.fc1.weight"] = _uniform_std((inter, h), 1.0 / np.sqrt(h), seed, p, "fc1")
+        sd[p + "mlp.fc2.weight"] = _uniform_std((h, inter), 1.0 / np.sqrt(inter), seed, p, "fc2")
+        for ln in ("input_layernorm", "post_attention_layernorm"):
+            sd[p + ln + ".weight"] = np.float32(1.0) + uniform_pm1(h, seed, p, ln, "w") * np.float32(0.2)
+            sd[p + ln + ".bias"] = uniform_pm1(h, seed, p, ln, "b") * np.float32(0.1)
+        for ls in ("self_attn_layer_scale", "mlp_layer_scale"):
+            u = uniform_pm1(h, seed, p, ls)
+            sd[p + ls + ".scale"] = np.float32(0.15) + u * np.float32(0.1)
+    vqd = cfg.vector_quantization_hidden_dimension
+    for q in ("semantic", "acoustic"):
+        pre = f"quantizer.{q}_residual_vector_quantizer."
+        # (the data-fitted codebook sums are ~16 in magnitude: 1/16 brings the decoder's input to O(1))
+        sd[pre + "output_proj.weight"] = _uniform_std((h, vqd, 1), 0.0625 / np.sqrt(vqd), seed, pre, "oproj")
+    return sd
+
+
 def state_dict_sha256(sd: Dict[str, np.ndarray]) -> str:
     h = hashlib.sha256()
     for k in sorted(sd):
