@@ -260,9 +260,11 @@ int64_t mimi_f16_reruns(const mimi_engine* e);
 int64_t mimi_rvq_chain_reruns(const mimi_engine* e);
 /* hipGraph replay of MIMI_PRECISION_F16X3 encodes (default on): the second encode of a (batch, length, K) shape
  * captures the whole pass into a graph, later ones replay it (same kernels and arguments: identical codes).
- * Never used while profiling or taps are on.  enable = 0 drops the captured graphs.  Replays so far: */
+ * Never used while profiling or taps are on.  enable = 0 drops the captured graphs.  Replays so far, and graphs
+ * captured so far (a graph retired by a workspace or RoPE-table reallocation is captured again: diagnostic): */
 int mimi_set_graphs(mimi_engine* e, int32_t enable);
 int64_t mimi_graph_replays(const mimi_engine* e);
+int64_t mimi_graph_captures(const mimi_engine* e);
 /* Kernel-variant options (tuning / A-B checks; every setting gives identical codes).  key "stage0_fused":
  * 0 = stage-0 residual block and down conv 0 as two kernels (y through HBM), 1 = one fused kernel (y stays on
  * chip; default).  key "ln_fused": on small grids (batch 1-4) 0 = LayerNorm launches before q/k/v and fc1, 1 = fc1
@@ -376,7 +378,8 @@ int mimi_profile_reset(mimi_engine* e);
 int mimi_profile_sequence(mimi_engine* e, int32_t max_stages, char* names /* max_stages*128 */, int32_t* n_stages);
 
 /* When enabled, mimi_encode keeps a copy of each stage's output (for per-stage parity tests); mimi_decode keeps
- * "quantized" (after the two output_proj, summed), "upsample", "xfmr7", "dconv0" (raw decoder.layers.0 output), "up0".."up3"
+ * "quantized" (after the two output_proj, summed), "upsample", "xfmr7", "dconv0" (raw decoder.layers.0 output, from a
+ * launch of its own that only taps make), "dconv0_elu" (the bias + ELU output the pass itself computes), "up0".."up3"
  * (each transposed conv's raw output), "dres0_elu".."dres3_elu" (ELU of each residual block's output: the form the
  * fused block stores) and "audio", all [batch][time][channels].  mimi_set_profiling records decode's stages too
  * (names "dec_..."). */

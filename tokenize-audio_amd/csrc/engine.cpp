@@ -331,7 +331,7 @@ struct mimi_engine {
     hipStream_t cap_stream = nullptr;
     int ws_gen = 0, rope_gen = 0;
     uint64_t graph_clock = 0;
-    int64_t graph_replays = 0;
+    int64_t graph_replays = 0, graph_captures = 0;
 
     bool taps = false;
     int stage0_fused = 1;  // 0: stage-0 block + down conv 0 as two kernels; 1: one fused kernel
@@ -2096,6 +2096,7 @@ static mimi_engine::Graph* capture_graph(mimi_engine* e, const float* audio, int
     ng.chain_flag = e->chain_flag;
     ng.chain_clear = e->chain_flag ? e->cap_chain_clear : 0;
     e->graphs.push_back(ng);
+    ++e->graph_captures;
     return &e->graphs.back();
 }
 
@@ -2972,12 +2973,14 @@ extern "C" int mimi_decode(mimi_engine* e, const int32_t* dev_codes, int32_t bat
     if (e->taps) {  // the raw layer-0 output (the pass itself only needs its ELU)
         GemmArgs at = conv_args(e->dec_first, t0, T2, w.tap, T2, B);
         LAUNCH_TRY(launch_gemm(ROLE_DOWN, at, s, &kname, PREC_F32), "decoder conv 0 (tap)");
+        rec.mark("dec_conv0_tap", fl(at), by(at), kname);
         if ((rc = save_tap(e, "dconv0", w.tap, B, T2, C, s))) return rc;
     }
     float* xe = w.p;  // ELU'd input of the next up conv
     GemmArgs a0 = conv_args(e->dec_first, t0, T2, xe, T2, B);
     LAUNCH_TRY(launch_gemm(ROLE_DOWN_ELU, a0, s, &kname, PREC_F32), "decoder conv 0");
     rec.mark("dec_conv0", fl(a0), by(a0), kname);
+    if ((rc = save_tap(e, "dconv0_elu", xe, B, T2, C, s))) return rc;  // what the pass itself computes and up conv 0 reads
     int64_t len = T2;
     for (int si = 0; si < c.num_ratios; ++si) {
         const int r = c.upsampling_ratios[si];
@@ -3080,6 +3083,8 @@ extern "C" int mimi_set_graphs(mimi_engine* e, int32_t enable) {
 }
 
 extern "C" int64_t mimi_graph_replays(const mimi_engine* e) { return e ? e->graph_replays : -1; }
+
+extern "C" int64_t mimi_graph_captures(const mimi_engine* e) { return e ? e->graph_captures : -1; }
 
 // mimi_set_option keys: engine field, allowed values (bit v of `allowed` set: value v accepted), what they select.
 // Every key changes the kernel sequence (never the bits an encode produces), so a change drops captured graphs.

@@ -367,6 +367,10 @@ class MimiHipModel:
             n *= r
         return n
 
+    def decode_workspace_bytes(self, batch: int, frames: int) -> int:
+        """Bytes of decode's workspace for this shape at the current taps setting (``mimi_decode_workspace_bytes``)."""
+        return int(self._lib.mimi_decode_workspace_bytes(self._h, int(batch), int(frames)))
+
     def _require_decode(self):
         if not self.decode_enabled:
             raise RuntimeError("this MimiHipModel holds the encode path only: construct it with decode=True "
@@ -455,6 +459,11 @@ class MimiHipModel:
     @property
     def graph_replays(self) -> int:
         return int(self._lib.mimi_graph_replays(self._h))
+
+    @property
+    def graph_captures(self) -> int:
+        """Graphs captured so far (a graph retired by a workspace or RoPE-table reallocation is captured again)."""
+        return int(self._lib.mimi_graph_captures(self._h))
 
     def set_option(self, key: str, value: int):
         """Kernel-variant option (identical codes either way): "stage0_fused" 0 = stage-0 block and down conv 0 as
