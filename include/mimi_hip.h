@@ -280,7 +280,9 @@ int64_t mimi_graph_captures(const mimi_engine* e);
  * residual conv as the streaming kernel with register-resident weights: 1 stage 2 (default), 2 stages 2 and 3 (stage 3
  * uniform batches; measured slower there), 0 off), "attn_band_split" 0/1/2 (items
  * over 256 frames: the banded attention as 128-query workgroups, by grid size (default), or one 32-query tile per
- * workgroup).  Unknown keys and values:
+ * workgroup), "gemm256" 0-7 (uniform f16x3 batches: the 256 x 256 staggered planes-GEMM tile for bit 0 fc1, bit 1 the
+ * k = 2s down convs with fp32 output, each from 256 such tiles up; bit 2 (tests) both on any grid; default 3).
+ * Unknown keys and values:
  * MIMI_ERR_INVALID_ARGUMENT.  A change drops the captured graphs. */
 int mimi_set_option(mimi_engine* e, const char* key, int64_t value);
 /* MIMI_PRECISION_F16X3 diagnostics: per plane tensor (64-char names), its fixed activation scale and the max|x|

@@ -362,6 +362,9 @@ struct mimi_engine {
     // same bits): each XCD re-serves 1 / fc1_cg of W1 from its L2.  (A/B r4y: 2 groups cut fc1's fetch 85 -> 54 MB per
     // launch but not its time, 0.59-0.60 vs 0.61-0.62 ms per step; profiles/r4y_ab_fc1_cg.txt)
     int fc1_cg = 1;
+    // 256 x 256 staggered planes-GEMM tile (gemm_planes256.h; mimi_set_option "gemm256", launch_gemm's g256; same bits):
+    // bit 0 fc1, bit 1 the k = 2s down convs, bit 2 (tests) both on any grid
+    int gemm256 = 3;  // (A/B per role at B = 32 x 10 s: profiles/g256_ab_roles.txt)
     // stage-1 fp16 block form (resblock.hip resblock128_h16_kernel; mimi_set_option "res1_form"; same bits): 0 one
     // 8-wave workgroup per CU, 1 two 4-wave workgroups per CU (each wave both 16-step tiles of its M tile; their block
     // chains interleave on the SIMDs: 0.59 -> 0.555 ms per B = 32 step, profiles/r4aa_ab_res1_form.txt)
@@ -1588,7 +1591,7 @@ static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int
             ad.a_rows = dT[si];
             ad.m_rows = dT[si + 1];
         }
-        LAUNCH_TRY(launch_gemm(role, ad, s, &kname, prec), "down");
+        LAUNCH_TRY(launch_gemm(role, ad, s, &kname, prec, rg ? 0 : e->gemm256), "down");
         snprintf(nm, sizeof nm, "down_s%d", si);
         rec.mark(nm, gemm_flops(ad) * rows_of(si + 1, (double)B * p.T[si + 1]) / ((double)B * p.T[si + 1]),
                  gemm_bytes(ad, false), kname);
@@ -1641,7 +1644,7 @@ static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int
         // LayerNorm + fc1 (ln_fused >= 1) / q/k/v (ln_fused 2): on small grids one launch whose tiles compute their
         // rows' LayerNorm (the same bits as the LayerNorm kernel's planes, gemm_planes.h FL_LNA)
         auto ln_into = [&](GemmArgs& g, int role, const float* lw, const float* lb, const Act& act) {
-            if (!h16 || e->ln_fused < (role == ROLE_QKV ? 2 : 1) || !gemm_ln_prologue_ok(role, g, prec)) return false;
+            if (!h16 || e->ln_fused < (role == ROLE_QKV ? 2 : 1) || !gemm_ln_prologue_ok(role, g, prec, rg ? 0 : e->gemm256)) return false;
             if (role == ROLE_QKV) g.ln_tile = e->ln_fused - 2;  // (2: 16x64, 3: 32x64, 4: 16x128 tiles)
             g.ln_x = w.t0;
             g.ln_g = lw;
@@ -1754,7 +1757,7 @@ static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int
         }
         a1.sc1 = (e->sc1_out & 2) != 0;
         a1.ncg = e->fc1_cg;
-        LAUNCH_TRY(launch_gemm(ROLE_FC1, a1, s, &kname, prec), "fc1");
+        LAUNCH_TRY(launch_gemm(ROLE_FC1, a1, s, &kname, prec, rg ? 0 : e->gemm256), "fc1");
         rec.mark("fc1", gemm_flops(a1), gemm_bytes(a1, false), kname);
         if ((rc = save_tap_planes(e, nmf("ff%d", l).c_str(), w.ff, ns, tapB, tapT, c.intermediate_size, s, ffa.scale)))
             return rc;
@@ -3107,6 +3110,7 @@ static const EngineOption kEngineOptions[] = {
     {"qkv_attn_xcd", &mimi_engine::qkv_attn_xcd, 0x3u, "0 or 1"},
     {"attn_band_split", &mimi_engine::attn_band_split, 0x7u, "0, 1 or 2"},
     {"fc1_cg", &mimi_engine::fc1_cg, 0x17u, "0, 1, 2 or 4"},
+    {"gemm256", &mimi_engine::gemm256, 0xffu, "0..7"},
     {"res1_form", &mimi_engine::res1_form, 0x3u, "0 or 1"},
     {"res1_stream", &mimi_engine::res1_stream, 0x7u, "0, 1 or 2"},
 };

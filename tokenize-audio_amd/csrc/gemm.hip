@@ -20,6 +20,7 @@
 
 
 #include "gemm_planes.h"
+#include "gemm_planes256.h"
 
 #ifndef MIMI_QKV_V
 #define MIMI_QKV_V 1
@@ -126,6 +127,44 @@ static hipError_t run_planes(const GemmArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+static bool pair_ok(const GemmArgs& a);
+static long long tiles(const GemmArgs& a, int bm, int bn);
+
+// gemm_planes256_kernel (gemm_planes256.h): uniform f16x3 batches only.  planes256_ok: the shapes it takes.
+static bool planes256_ok(const GemmArgs& a) {
+    return a.Ap && a.Wsplit && !a.ln_x && !a.m_rows && !a.a_rows && !a.a_boff && !a.c_boff && !a.R && a.K % 32 == 0 &&
+           a.K >= 64 && 2LL * a.N * a.K < 0x7fffffffLL && a.a_len * 2 <= 0x7fffffffLL && a.N % 8 == 0 && a.ldc % 8 == 0 &&
+           a.c_bstride % 8 == 0 && a.c_pstride % 8 == 0;
+}
+template <int EPI, int OUTP, int TAG, int FL>
+static hipError_t run_planes256(const GemmArgs& a, hipStream_t s) {
+    static thread_local char name[96];
+    if (!name[0]) snprintf(name, sizeof(name), "mimi::gemm_planes256_kernel<%d, %d, %d, %d>", EPI, OUTP, TAG, FL);
+    g_last_kernel = name;
+    if (!planes256_ok(a) || ((OUTP & 7) && (!a.Cp || a.out_scale <= 0.0f)) || (!(OUTP & 7) && !a.C) || ((OUTP & 8) && !a.C))
+        return hipErrorInvalidValue;
+    if ((FL & FL_PAIR) && !pair_ok(a)) return hipErrorInvalidValue;
+    const long long nwg = tiles(a, 256, 256);
+    if (nwg > 0x7fffffffLL) return hipErrorInvalidValue;
+    if constexpr ((FL & FL_SC1OUT) != 0) {  // 32-bit byte offsets from an item's output base, as run_planes
+        const long long rows = a.M;
+        if ((rows * a.ldc + a.N) * 4 > 0x7fffffffLL || ((OUTP & 7) && (a.c_pstride + rows * a.ldc) * 2 > 0x7fffffffLL))
+            return run_planes256<EPI, OUTP, TAG, FL & ~FL_SC1OUT>(a, s);
+    }
+    long long grid = nwg;
+    if (FL & FL_PERSIST) {  // one workgroup per CU (144 KiB of LDS), a multiple of the 8 XCDs
+        static const int slots = [] {
+            int dev = 0, ncu = 256;
+            (void)hipGetDevice(&dev);
+            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+            return std::max(8, ncu / 8 * 8);
+        }();
+        grid = std::min<long long>(nwg, slots);
+    }
+    hipLaunchKernelGGL((gemm_planes256_kernel<EPI, OUTP, TAG, FL>), dim3((unsigned)grid), dim3(512), 0, s, a);
+    return hipGetLastError();
+}
+
 // Tiles of the planes kernel (tools/gemm_bench.hip; profiles/r1_gemm_bench_planes*.log, r1_gemm_bench_ws.log,
 // r1_gemm_bench_f16.log):
 //   big:    256x128, 8 compute waves, 2 stages (NS = 3; 3 at NS = 2), 144 KiB LDS: down convs, k3 convs, fc1
@@ -184,6 +223,7 @@ static hipError_t run_auto(const GemmArgs& a, hipStream_t s) {
 static hipError_t dispatch(int role, const GemmArgs& a, hipStream_t s);
 
 static thread_local int g_prec = PREC_F32;
+static thread_local int g_g256 = 0;  // launch_gemm's g256 (engine option gemm256)
 
 template <bool ELU_IN, int PAD, int EPI, int TAG>
 static hipError_t run_prec(const GemmArgs& a, hipStream_t s, int prec) {
@@ -206,12 +246,13 @@ hipError_t launch_gelu_check(const float* in, long long n, float* out, hipStream
     return hipGetLastError();
 }
 
-hipError_t launch_gemm(int role, const GemmArgs& a, hipStream_t s, const char** kname, int precision) {
+hipError_t launch_gemm(int role, const GemmArgs& a, hipStream_t s, const char** kname, int precision, int g256) {
     if (a.K % 32 != 0 || a.a_cin % 4 != 0 || a.a_rs % 4 != 0 || a.M <= 0 || a.N <= 0 || a.batch <= 0)
         return hipErrorInvalidValue;
     if (a.Ap && (a.a_cin % 8 != 0 || a.a_rs % 8 != 0 || a.a_off % 8 != 0)) return hipErrorInvalidValue;  // 16-B chunks
     g_last_kernel = nullptr;
     g_prec = precision;
+    g_g256 = g256;
     hipError_t e = dispatch(role, a, s);
     if (kname) *kname = g_last_kernel ? g_last_kernel : "?";
     return e;
@@ -233,6 +274,7 @@ static bool pair_ok(const GemmArgs& a) {
 // utterance's codes do not depend on the batch it is encoded in (test_full_size_batch_properties compares B = 1
 // against B = 32 bitwise).
 constexpr long long kSmallGrid = 128;
+constexpr long long kGrid256 = 256;  // 256 x 256 tiles from which gemm_planes256_kernel runs: one per CU
 static long long tiles(const GemmArgs& a, int bm, int bn) {
     return (long long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn) * a.batch;
 }
@@ -292,7 +334,8 @@ static hipError_t run_small_h16(const GemmArgs& a, hipStream_t s) {
 // The LayerNorm prologue (FL_LNA, gemm_planes.h) replaces the LayerNorm launch in front of q/k/v and fc1 on the
 // small grids: every tile recomputes its rows' LayerNorm (N / BN times per row), cheap beside a launch when the
 // rows are few (batch 1-4), and its A image (BM x 2 KiB) fits beside the ring for the 16-64-row tiles.
-bool gemm_ln_prologue_ok(int role, const GemmArgs& a, int precision) {
+bool gemm_ln_prologue_ok(int role, const GemmArgs& a, int precision, int g256) {
+    if (role == ROLE_FC1 && (g256 & 4)) return false;  // (tests) fc1 forced onto the 256 x 256 tile
     return precision == PREC_F16X3 && (role == ROLE_QKV || role == ROLE_FC1) && a.K == 512 && a.a_rs == 512 &&
            a.a_off == 0 && !a.a_rows && !a.m_rows && !a.a_boff && tiles(a, 128, 128) < kSmallGrid;
 }
@@ -313,6 +356,21 @@ static hipError_t dispatch_planes(int role, const GemmArgs& a, hipStream_t s) {
         // (16 x 64 tiles at batch 1 measured slower: fc1 0.142 -> 0.188 ms per encode, gpurun_out/r6f/ab.log)
         if (tiles(a, 32, 64) >= 256) return run_planes<32, 64, 2, 2, 2, MIMI_LNA_ST, EPI_GELU, 2, 7, 4, 32, 16, FL_LNA, true>(a, s);
         return run_planes<16, 64, 1, 2, 2, MIMI_LNA_ST, EPI_GELU, 2, 7, 4, 32, 16, FL_LNA, true>(a, s);
+    }
+    // 256 x 256 staggered tiles (gemm_planes256.h; engine option gemm256 -> launch_gemm's g256): bit 0 fc1, bit 1 the
+    // k = 2s down convs that write fp32 (ROLE_DOWN, ROLE_DOWN_XE), from kGrid256 tiles up and N >= 256; bit 2 (tests):
+    // both, on any grid.  Ragged batches, the LayerNorm prologue and the other precision modes never get here.
+    if (prec == PREC_F16X3 && g_g256 && planes256_ok(a)) {
+        const bool force = (g_g256 & 4) != 0;
+        const bool grid_ok = force || (tiles(a, 256, 256) >= kGrid256 && a.N >= 256);
+        if (role == ROLE_FC1 && (force || (g_g256 & 1)) && grid_ok && a.Cp) {
+            if (a.sc1) return run_planes256<EPI_GELU, 2, 7, FL_SC1OUT>(a, s);
+            return run_planes256<EPI_GELU, 2, 7, 0>(a, s);
+        }
+        if ((role == ROLE_DOWN || role == ROLE_DOWN_XE) && (force || (g_g256 & 2)) && grid_ok && pair_ok(a)) {
+            if (role == ROLE_DOWN) return run_planes256<EPI_BIAS, 0, 2, FL_PAIR | FL_PERSIST>(a, s);
+            return run_planes256<EPI_BIAS, 2 | 8, 11, FL_PAIR | FL_PERSIST>(a, s);
+        }
     }
 #ifndef MIMI_SMALL_ROLES
 #define MIMI_SMALL_ROLES 1

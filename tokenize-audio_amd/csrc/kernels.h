@@ -253,7 +253,8 @@ struct GemmArgs {
 bool res1_stream_ok(const GemmArgs& a);
 hipError_t launch_res1_stream(const GemmArgs& a, hipStream_t s, const char** kname);
 // true when launch_gemm(role, a, precision) runs a tile with the LayerNorm prologue (a.ln_* then feed A)
-bool gemm_ln_prologue_ok(int role, const GemmArgs& a, int precision);
+// (g256: the engine option gemm256, as for launch_gemm)
+bool gemm_ln_prologue_ok(int role, const GemmArgs& a, int precision, int g256 = 0);
 
 // Launch the GEMM for a given conv/linear role (the role picks tile shape and template flags).
 enum GemmRole : int {
@@ -281,8 +282,10 @@ enum GemmRole : int {
 enum Precision : int { PREC_F32 = 0, PREC_BF16X6 = 1, PREC_BF16X3 = 2, PREC_F16X3 = 3 };
 
 // *kname (optional) receives the kernel symbol as rocprofv3 prints it, for per-kernel profile aggregation.
+// g256: engine option gemm256 (the 256 x 256 staggered planes tile, gemm_planes256.h; the same bits either way): bit 0
+// fc1, bit 1 the k = 2s down convs, bit 2 both on any grid.
 hipError_t launch_gemm(int role, const GemmArgs& a, hipStream_t s, const char** kname = nullptr,
-                       int precision = PREC_F32);
+                       int precision = PREC_F32, int g256 = 0);
 
 // Fused residual block + trailing ELU: y = ELU(x + b1 + W1 . ELU(b3 + W3 (*) ELU(x))), [B][T][C].
 struct ResArgs {

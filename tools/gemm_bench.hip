@@ -1,7 +1,9 @@
 // Microbenchmark of planes-GEMM variants on the encode's real GEMM shapes (tuning aid, not shipped).
 //   hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -I tokenize-audio_amd/csrc -I tools \
 //     tools/gemm_bench.hip -o tools/bin/gemm_bench
-//   tools/bin/gemm_bench REPS down_s0,down_s1,...   (shape names, comma-separated)
+//   tools/bin/gemm_bench REPS down_s0,down_s1,... ["variant|variant" [cold]]   (shape names, comma-separated; variant
+//   name substrings -- keep the two references in the list, every other variant is compared with them bit for bit
+//   (`diff` = outputs whose bits differ); cold: a second timing with the operands flushed out of the caches)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "gemm_planes.h"
+#include "gemm_planes256.h"
 #include "gemm_stream_proto.h"
 
 using namespace mimi;
@@ -72,6 +75,14 @@ void launch_pl(const GemmArgs& a, hipStream_t s) {
     }
     hipLaunchKernelGGL((gemm_planes_kernel<BM, BN, WM, WN, NS, ST, EPI_BIAS, 0, 0, LW, BK, MF, FL, F16>), dim3(nwg),
                        dim3((WM * WN + LW) * 64), 0, s, a);
+}
+
+// gemm_planes256_kernel (256 x 256 staggered tile): one workgroup per tile, or per CU with FL_PERSIST
+template <int FL>
+void launch_256(const GemmArgs& a, hipStream_t s) {
+    int nwg = ((a.M + 255) / 256) * ((a.N + 255) / 256) * a.batch;
+    if (FL & FL_PERSIST) nwg = std::min(nwg, 256);
+    hipLaunchKernelGGL((gemm_planes256_kernel<EPI_BIAS, 0, 0, FL>), dim3(nwg), dim3(512), 0, s, a);
 }
 
 __global__ void split_planes(const float* x, __bf16* out, long long n) {
@@ -204,6 +215,15 @@ int main(int argc, char** argv) {
         {"B1 16x64 1w+4ld s16 KG4", launch_pl<16, 64, 1, 1, 2, 16, 4, 32, 16, FL_KG4, true>, 32, 12},
         {"B1 32x32 2w+4ld s12 KG2", launch_pl<32, 32, 2, 1, 2, 12, 4, 32, 16, FL_KG2, true>, 32, 12},
         {"B1 16x32 1w+4ld s6 KG2 (fc2)", launch_pl<16, 32, 1, 1, 2, 6, 4, 32, 16, FL_KG2, true>, 32, 12},
+        // 256 x 256 staggered tile (gemm_planes256.h) next to the tiles it would replace: fc1 vs "128x128 8w s2", the
+        // down convs vs "pair PERSIST 8w+4ld s2"; bits must equal the reference's (diff = 0)
+        {"S256 stagger", launch_256<0>, 32, 12},
+        {"S256 stagger PERSIST", launch_256<FL_PERSIST>, 32, 12},
+        {"S256 stagger DIAG nodma", launch_256<FL_DIAG_NODMA>, 32, 12},
+        {"S256 stagger DIAG nomma", launch_256<FL_DIAG_NOMMA>, 32, 12},
+        {"pair S256 stagger PERSIST", launch_256<FL_PAIR | FL_PERSIST>, 64, 12, true},
+        {"pair S256 stagger PERSIST DIAG nodma", launch_256<FL_PAIR | FL_PERSIST | FL_DIAG_NODMA>, 64, 12, true},
+        {"pair S256 stagger PERSIST DIAG nomma", launch_256<FL_PAIR | FL_PERSIST | FL_DIAG_NOMMA>, 64, 12, true},
         // interleaved-plane timing probe (FL_DIAG_ILV: 8 rows x 128 B pieces; results garbage)
         {"pair PERSIST 8w+4ld s2 ILV", launch_pl<256, 128, 4, 2, 2, 2, 4, 32, 16, FL_PAIR | FL_PERSIST | FL_DIAG_ILV, true>, 64, 12, true},
         {"pair PERSIST DIAG nomma ILV", launch_pl<256, 128, 4, 2, 2, 2, 4, 32, 16, FL_PAIR | FL_PERSIST | FL_DIAG_NOMMA | FL_DIAG_ILV, true>, 64, 12, true},
@@ -339,7 +359,25 @@ int main(int argc, char** argv) {
                 best = fminf(best, ms);
                 tot += ms;
             }
+            // cold operands (argv[4] = "cold"): a 1-GiB fill between the launches pushes A and W out of L2 and MALL
+            float cold = 0;
+            if (argc > 4 && !strcmp(argv[4], "cold")) {
+                static void* flush = nullptr;
+                if (!flush) CK(hipMalloc(&flush, 1ull << 30));
+                cold = 1e30f;
+                for (int r = 0; r < std::min(reps, 5); ++r) {
+                    CK(hipMemsetAsync(flush, r, 1ull << 30, st));
+                    CK(hipEventRecord(e0, st));
+                    vars[v].fn(a, st);
+                    CK(hipEventRecord(e1, st));
+                    CK(hipEventSynchronize(e1));
+                    float ms;
+                    CK(hipEventElapsedTime(&ms, e0, e1));
+                    cold = fminf(cold, ms);
+                }
+            }
             double maxrel = 0;
+            size_t ndiff = 0;  // outputs whose bits differ from the reference's
             if (v > 1) {
                 CK(hipMemcpy(out.data(), C, nC * 4, hipMemcpyDeviceToHost));
                 CK(hipMemcpy(ref.data(), vars[v].pair ? Cref2 : Cref, nC * 4, hipMemcpyDeviceToHost));
@@ -347,11 +385,12 @@ int main(int argc, char** argv) {
                 for (size_t i = 0; i < nC; ++i) {
                     mx = fmax(mx, fabs((double)ref[i]));
                     md = fmax(md, fabs((double)out[i] - (double)ref[i]));
+                    ndiff += memcmp(&out[i], &ref[i], 4) != 0;
                 }
                 maxrel = md / (mx + 1e-30);
             }
-            printf("%-8s %-22s best %8.3f ms  mean %8.3f ms  %7.1f TF/s(f32-equiv)  max|d|/max|ref| %.2e\n", sh.name,
-                   vars[v].name, best, tot / reps, flops / (best * 1e-3) / 1e12, maxrel);
+            printf("%-8s %-22s best %8.3f ms  mean %8.3f ms  cold %8.3f ms  %7.1f TF/s(f32-equiv)  max|d|/max|ref| %.2e"
+                   "  diff %zu\n", sh.name, vars[v].name, best, tot / reps, cold, flops / (best * 1e-3) / 1e12, maxrel, ndiff);
             fflush(stdout);
         }
         CK(hipFree(A)); CK(hipFree(Apl)); CK(hipFree(W)); CK(hipFree(Wp)); CK(hipFree(bias)); CK(hipFree(C)); CK(hipFree(Cref)); CK(hipFree(Cref2));
