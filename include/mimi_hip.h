@@ -131,6 +131,13 @@ int mimi_encode(mimi_engine* e, const float* dev_audio, int32_t batch, int64_t l
  * wait returns; dev_audio and dev_codes must stay allocated, and dev_audio unmodified, until then (the wait may
  * re-encode from dev_audio: a fixed f16x3 scale overflowed, or the persistent RVQ chain gave up).  At most 16 encodes per engine may be
  * in flight; each ticket is waited exactly once.  mimi_encode = mimi_encode_async + mimi_encode_wait.
+ *
+ * The encode runs on a stream of the engine's, ordered after `stream` at the call (everything enqueued on `stream`
+ * before the call is visible to it), or on `stream` itself; nothing enqueued on `stream` AFTER the call is ordered
+ * behind the encode.  Only mimi_encode_wait orders anything behind it: read dev_codes, and reuse dev_audio, after the
+ * wait has returned.  Two encodes kept in flight (enqueue the next, then wait for the previous) run side by side in the
+ * engine's two lanes -- each lane its own workspace, maxima, captured graphs and stream -- so the second workspace
+ * exists only for callers that overlap encodes (option "lanes" below; mimi_lane_encodes counts per lane).
  */
 int mimi_encode_async(mimi_engine* e, const float* dev_audio, int32_t batch, int64_t length, int32_t num_quantizers,
                       int32_t* dev_codes, void* stream, int64_t* ticket);
@@ -282,9 +289,15 @@ int64_t mimi_graph_captures(const mimi_engine* e);
  * over 256 frames: the banded attention as 128-query workgroups, by grid size (default), or one 32-query tile per
  * workgroup), "gemm256" 0-7 (uniform f16x3 batches: the 256 x 256 staggered planes-GEMM tile for bit 0 fc1, bit 1 the
  * k = 2s down convs with fp32 output, each from 256 such tiles up; bit 2 (tests) both on any grid; default 3).
+ * "lanes" 0/1/2 (which encodes run on a lane's own stream, see mimi_encode_async: 0 none -- every encode on the
+ * caller's stream in one workspace; 1 (default) f16x3 uniform batches whose RVQ runs the per-level kernels; 2 ragged
+ * batches and encodes that may launch the persistent RVQ chain too.  mimi_encode_host, mimi_rvq_encode, decode,
+ * calibration, taps and profiling level 1 never take one).
  * Unknown keys and values:
- * MIMI_ERR_INVALID_ARGUMENT.  A change drops the captured graphs. */
+ * MIMI_ERR_INVALID_ARGUMENT.  A call waits for the encodes in flight; a change drops the captured graphs. */
 int mimi_set_option(mimi_engine* e, const char* key, int64_t value);
+/* Encodes submitted to lane 0 / 1 so far (diagnostic; -1: no such lane).  Encodes that take no lane count in lane 0. */
+int64_t mimi_lane_encodes(const mimi_engine* e, int32_t lane);
 /* MIMI_PRECISION_F16X3 diagnostics: per plane tensor (64-char names), its fixed activation scale and the max|x|
  * of the last waited encode (-1: not produced by it); an overflow is max * scale >= 2^15. */
 int mimi_act_scales(mimi_engine* e, int32_t max_n, char* names, float* scales, float* last_max, int32_t* n);

@@ -246,10 +246,7 @@ struct mimi_engine {
     float* rope_sin = nullptr;
     int64_t rope_T = 0;
 
-    void* ws = nullptr;
-    size_t ws_bytes = 0;
-
-    hipEvent_t ws_free = nullptr;  // recorded at the end of every encode: the next one (any stream) waits on it
+    // (the workspace, its ws_free event and the maxima buffers are per lane: see Lane below)
 
     // PREC_F16X3 activation scales (see "activation scales" above calibrate_scales): plane-format tensor `name`
     // is stored as fp16 planes of x * act_scale[slot_of[name]], a power of two fixed at mimi_finalize from a
@@ -260,9 +257,7 @@ struct mimi_engine {
     bool calibrating = false;
     bool calibrated = false;         // calibrate_scales has run (lazily, before the first f16x3 encode)
     bool uncalibrated_slot = false;  // the current encode named a tensor the calibration did not see (reset per encode)
-    unsigned* amax_dev = nullptr;   // [kMaxActSlots][AMAX_SLOT_WORDS] sub-slots, then [kMaxActSlots] reduced
-    unsigned* amax_red = nullptr;
-    unsigned* amax_host = nullptr;  // pinned
+    unsigned* amax_host = nullptr;  // pinned (read_amax: filled and read under the lock, behind a stream sync)
     int32_t* item_codes = nullptr;  // one item's codes (per-item overflow fallback)
     // encodes enqueued by mimi_encode_async and not yet waited (see encode_async_locked)
     struct Pending {
@@ -276,7 +271,8 @@ struct mimi_engine {
         int B = 0, K = 0;
         int64_t L = 0;
         int32_t* codes = nullptr;
-        hipStream_t s = nullptr;
+        hipStream_t s = nullptr;      // the stream it ran on: its lane's own, or the caller's
+        int lane = 0;                 // the lane whose workspace it ran in (re-runs at the wait go through it)
         bool ragged = false;          // a ragged batch (lens: the items' lengths, for the overflow fallback)
         std::vector<int64_t> lens;
         int* rg_pinned = nullptr;     // pinned image of its RaggedTable (read by the encode's async upload)
@@ -322,14 +318,37 @@ struct mimi_engine {
         size_t chain_clear = 0;          // bytes from chain_flag zeroed before each replay (set_io_kernel)
     };
     static constexpr int kMaxGraphs = 8;
-    std::vector<Graph> graphs;
-    std::map<std::tuple<int, int64_t, int>, int> graph_seen;  // eager encodes per shape (capture on the 2nd)
+    // A lane: everything one encode mutates, so that two encodes in two lanes run side by side (the second one's
+    // kernels fill the CUs the first one's ring fills, epilogues and kernel boundaries leave idle).  Weights, scales,
+    // rope tables, tickets and counters are shared.  Lane 0 exists from mimi_create and serves every encode that runs
+    // on the caller's stream; a lane's stream and lane 1's buffers are made on first use (lane_prepare).
+    struct Lane {
+        void* ws = nullptr;
+        size_t ws_bytes = 0;
+        int ws_gen = 0;
+        hipEvent_t ws_free = nullptr;  // recorded at the end of every encode in this lane: the next one (any stream) waits on it
+        unsigned* amax_dev = nullptr;  // [kMaxActSlots][AMAX_SLOT_WORDS] sub-slots, then [kMaxActSlots] reduced
+        unsigned* amax_red = nullptr;
+        void** io_dev = nullptr;  // [audio, codes, pinned maxima, pinned give-up word] of the replay
+        std::vector<Graph> graphs;
+        std::map<std::tuple<int, int64_t, int>, int> graph_seen;  // eager encodes per shape (capture on the 2nd)
+        hipStream_t stream = nullptr;   // non-blocking: the encodes that take the lane run here, not on the caller's
+        hipEvent_t in_ready = nullptr;  // recorded on the caller's stream at submit: the inputs are ready
+        int tickets = 0;                // encodes submitted to this lane and not yet waited
+        int64_t encodes = 0;            // encodes submitted to this lane (mimi_lane_encodes)
+        bool excl = false;              // its last encode may hold the persistent RVQ chain (wants the GPU to itself)
+    };
+    static constexpr int kLanes = 2;
+    Lane lanes[kLanes];
+    Lane* ln = &lanes[0];  // the lane of the submission / wait in progress (set under mu, lane 0 otherwise)
+    // which encodes take a lane (mimi_set_option "lanes"): 0 none (every encode on the caller's stream in lane 0), 1 f16x3
+    // uniform batches on the per-level RVQ kernels, 2 ragged and chain-eligible encodes too
+    int lanes_opt = 1;
     bool graphs_enabled = true;
     bool capturing = false;
-    void** io_dev = nullptr;  // [audio, codes, pinned maxima, pinned give-up word] of the replay
     size_t cap_chain_clear = 0;  // (capture) the captured chain's flag + granule bytes
     hipStream_t cap_stream = nullptr;
-    int ws_gen = 0, rope_gen = 0;
+    int rope_gen = 0;
     uint64_t graph_clock = 0;
     int64_t graph_replays = 0, graph_captures = 0;
 
@@ -585,10 +604,10 @@ extern "C" int mimi_create(const mimi_config* cfg, int device, mimi_engine** out
     if (device < 0 || device >= ndev) return set_err(MIMI_ERR_INVALID_ARGUMENT, "device %d of %d", device, ndev);
     e->device = device;
     HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipEventCreateWithFlags(&e->ws_free, hipEventDisableTiming));
-    HIP_TRY(hipMalloc(&e->amax_dev, ((size_t)kMaxActSlots * AMAX_SLOT_WORDS + kMaxActSlots) * sizeof(unsigned)));
-    e->amax_red = e->amax_dev + (size_t)kMaxActSlots * AMAX_SLOT_WORDS;
-    HIP_TRY(hipMemset(e->amax_dev, 0, ((size_t)kMaxActSlots * AMAX_SLOT_WORDS + kMaxActSlots) * sizeof(unsigned)));
+    HIP_TRY(hipEventCreateWithFlags(&e->ln->ws_free, hipEventDisableTiming));
+    HIP_TRY(hipMalloc(&e->ln->amax_dev, ((size_t)kMaxActSlots * AMAX_SLOT_WORDS + kMaxActSlots) * sizeof(unsigned)));
+    e->ln->amax_red = e->ln->amax_dev + (size_t)kMaxActSlots * AMAX_SLOT_WORDS;
+    HIP_TRY(hipMemset(e->ln->amax_dev, 0, ((size_t)kMaxActSlots * AMAX_SLOT_WORDS + kMaxActSlots) * sizeof(unsigned)));
     HIP_TRY(hipHostMalloc(&e->amax_host, kMaxActSlots * sizeof(unsigned), hipHostMallocDefault));
     build_expected(e.get());
     *out = e.release();
@@ -1116,7 +1135,7 @@ static size_t ws_layout(const mimi_engine* e, int B, const StagePlan& p, Workspa
     float* rgp = nullptr;
     float** ptrs[] = {&w->x, &w->y, &w->t0, &w->t1, &w->qkv, &w->att, &w->ff, &w->dsout, &w->proj, &w->rvq,
                       &w->xe, &w->h, &rgp};
-    char* base = reinterpret_cast<char*>(e->ws);
+    char* base = reinterpret_cast<char*>(e->ln->ws);
     for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) {
         if (w) *ptrs[i] = reinterpret_cast<float*>(base + off);
         off += ((sizes[i] * sizeof(float) + 255) / 256) * 256;
@@ -1130,23 +1149,31 @@ extern "C" int64_t mimi_workspace_bytes(const mimi_engine* e, int32_t batch, int
     return (int64_t)ws_layout(e, batch, plan_lengths(e->cfg, length), nullptr, e->precision);
 }
 
+// every lane's work done (each encode ends with its lane's ws_free, on whichever stream it ran)
+static void drain_lanes(mimi_engine* e) {
+    for (auto& l : e->lanes)
+        if (l.ws_free) (void)hipEventSynchronize(l.ws_free);
+}
+
+// the active lane's workspace (the other lane's encodes, workspace and graphs are untouched by a regrow)
 static int ensure_ws(mimi_engine* e, size_t bytes, hipStream_t s) {
-    if (bytes <= e->ws_bytes) return MIMI_OK;
+    if (bytes <= e->ln->ws_bytes) return MIMI_OK;
     HIP_TRY(hipStreamSynchronize(s));
-    if (e->ws) {
-        HIP_TRY(hipFree(e->ws));
-        e->ws = nullptr;
-        e->ws_bytes = 0;
+    HIP_TRY(hipEventSynchronize(e->ln->ws_free));  // (the lane's last encode may have run on another stream)
+    if (e->ln->ws) {
+        HIP_TRY(hipFree(e->ln->ws));
+        e->ln->ws = nullptr;
+        e->ln->ws_bytes = 0;
     }
-    hipError_t err = hipMalloc(&e->ws, bytes);
+    hipError_t err = hipMalloc(&e->ln->ws, bytes);
     if (err != hipSuccess) {
         (void)hipGetLastError();  // clear it: the launch checks (hipGetLastError) must not see this failure
-        e->ws = nullptr;
+        e->ln->ws = nullptr;
         return set_err(err == hipErrorOutOfMemory ? MIMI_ERR_OUT_OF_MEMORY : MIMI_ERR_HIP,
                        "workspace hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(err));
     }
-    e->ws_bytes = bytes;
-    ++e->ws_gen;  // captured graphs address the old workspace
+    e->ln->ws_bytes = bytes;
+    ++e->ln->ws_gen;  // captured graphs address the old workspace
     return MIMI_OK;
 }
 
@@ -1167,6 +1194,7 @@ static int ensure_rope(mimi_engine* e, int64_t T) {
         }
     }
     if (e->rope_cos) {
+        drain_lanes(e);  // the tables are shared: an encode in flight in either lane may still read them
         HIP_TRY(hipFree(e->rope_cos));
         HIP_TRY(hipFree(e->rope_sin));
     }
@@ -1324,7 +1352,7 @@ static int run_rvq(mimi_engine* e, const float* proj, int64_t frames, int K, int
     r.cb_unscale = e->cb_unscale;
     r.cb_emax = e->cb_emax;
     r.codes = codes;
-    r.codes_ref = e->capturing ? reinterpret_cast<int32_t* const*>(e->io_dev + 1) : nullptr;
+    r.codes_ref = e->capturing ? reinterpret_cast<int32_t* const*>(e->ln->io_dev + 1) : nullptr;
     r.frames_per_item = frames_per_item;
     r.form = e->rvq_form;
     r.chain = e->rvq_chain;
@@ -1376,7 +1404,7 @@ static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int
             e->act_scale.resize(slot + 1, 1.0f);
         }
         a.scale = e->act_scale[slot];
-        a.amax = e->amax_dev + (size_t)slot * AMAX_SLOT_WORDS;
+        a.amax = e->ln->amax_dev + (size_t)slot * AMAX_SLOT_WORDS;
         return a;
     };
     // a LayerNorm output whose bound (DevXfmr::ln*_bound) times its scale stays under half the fp16 plane limit
@@ -1396,7 +1424,7 @@ static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int
     };
     Recorder rec{e, s};
     const char* kname = "?";
-    if (!e->capturing) HIP_TRY(hipStreamWaitEvent(s, e->ws_free, 0));  // (a replay waits outside the graph)
+    if (!e->capturing) HIP_TRY(hipStreamWaitEvent(s, e->ln->ws_free, 0));  // (a replay waits outside the graph)
     // ragged batches: the length table (pinned host image, alive until the encode is waited) -> workspace
     const int* dT[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     const int *dT25 = nullptr, *dF = nullptr;
@@ -1447,7 +1475,7 @@ static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int
             ra.x = w.x;
             if (si == 0) {
                 ra.audio = audio;
-                ra.audio_ref = e->capturing ? const_cast<const float* const*>(reinterpret_cast<float**>(e->io_dev)) : nullptr;
+                ra.audio_ref = e->capturing ? const_cast<const float* const*>(reinterpret_cast<float**>(e->ln->io_dev)) : nullptr;
                 ra.w0 = e->conv0.w;
                 ra.b0 = e->conv0.b;
                 ra.w3frag = e->res3[0].wfrag;
@@ -1825,7 +1853,7 @@ static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int
     rec.mark("input_proj", gemm_flops(ap) * rF, gemm_bytes(ap, false), kname);
     if ((rc = save_tap(e, "proj", w.proj, B, T2, 2 * Dq, s))) return rc;
     if ((rc = run_rvq(e, w.proj, (int64_t)B * T2, K, codes, (int)T2, w.rvq, s, rec, rg ? dF : nullptr, rF))) return rc;
-    if (!e->capturing) HIP_TRY(hipEventRecord(e->ws_free, s));
+    if (!e->capturing) HIP_TRY(hipEventRecord(e->ln->ws_free, s));
     return MIMI_OK;
 }
 
@@ -1847,8 +1875,8 @@ static int read_amax(mimi_engine* e, hipStream_t s, int* n) {
     const int ns = (int)e->slot_of.size();
     *n = ns;
     if (ns == 0) return MIMI_OK;
-    LAUNCH_TRY(launch_amax_reduce(e->amax_dev, ns, e->amax_red, s), "amax_reduce");
-    HIP_TRY(hipMemcpyAsync(e->amax_host, e->amax_red, ns * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    LAUNCH_TRY(launch_amax_reduce(e->ln->amax_dev, ns, e->ln->amax_red, s), "amax_reduce");
+    HIP_TRY(hipMemcpyAsync(e->amax_host, e->ln->amax_red, ns * sizeof(unsigned), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return MIMI_OK;
 }
@@ -1864,8 +1892,8 @@ static float slot_amax(const mimi_engine* e, int i) {
 static int f16_pass(mimi_engine* e, const float* audio, int B, int64_t L, int K, int32_t* codes, hipStream_t s,
                     bool* overflow) {
     *overflow = false;
-    HIP_TRY(hipStreamWaitEvent(s, e->ws_free, 0));  // encodes enqueued on other streams use amax_dev too
-    HIP_TRY(hipMemsetAsync(e->amax_dev, 0, (size_t)kMaxActSlots * AMAX_SLOT_WORDS * sizeof(unsigned), s));
+    HIP_TRY(hipStreamWaitEvent(s, e->ln->ws_free, 0));  // encodes enqueued on other streams use amax_dev too
+    HIP_TRY(hipMemsetAsync(e->ln->amax_dev, 0, (size_t)kMaxActSlots * AMAX_SLOT_WORDS * sizeof(unsigned), s));
     e->uncalibrated_slot = false;
     int rc = encode_pass(e, audio, B, L, K, codes, s, PREC_F16X3);
     if (rc) return rc;
@@ -1925,7 +1953,7 @@ static int calibrate_scales(mimi_engine* e) {
     }
     e->calibrating = true;
     for (int it = 0; rc == MIMI_OK && it < 8; ++it) {
-        if (hipMemsetAsync(e->amax_dev, 0, (size_t)kMaxActSlots * AMAX_SLOT_WORDS * sizeof(unsigned), s) != hipSuccess) {
+        if (hipMemsetAsync(e->ln->amax_dev, 0, (size_t)kMaxActSlots * AMAX_SLOT_WORDS * sizeof(unsigned), s) != hipSuccess) {
             rc = set_err(MIMI_ERR_HIP, "calibration memset");
             break;
         }
@@ -2036,18 +2064,23 @@ static void destroy_graph(mimi_engine::Graph& g) {
     g.g = nullptr;
 }
 
-static void drop_graphs(mimi_engine* e) {
-    for (auto& g : e->graphs) destroy_graph(g);
-    e->graphs.clear();
+// Every lane's graphs, once nothing replays them any more.  clear_seen: the shapes' eager counts too.
+static void drop_graphs(mimi_engine* e, bool clear_seen = false) {
+    drain_lanes(e);
+    for (auto& l : e->lanes) {
+        for (auto& g : l.graphs) destroy_graph(g);
+        l.graphs.clear();
+        if (clear_seen) l.graph_seen.clear();
+    }
 }
 
 // Captures the f16x3 pass of (B, L, K) into a new graph.  On any failure the capture is abandoned and the
 // caller runs the eager pass (the error is cleared: a graph is an optimisation, never a requirement).
 static mimi_engine::Graph* capture_graph(mimi_engine* e, const float* audio, int B, int64_t L, int K,
                                           int32_t* codes) {
-    if (!e->io_dev && hipMalloc(&e->io_dev, 4 * sizeof(void*)) != hipSuccess) {
+    if (!e->ln->io_dev && hipMalloc(&e->ln->io_dev, 4 * sizeof(void*)) != hipSuccess) {
         (void)hipGetLastError();
-        e->io_dev = nullptr;
+        e->ln->io_dev = nullptr;
         return nullptr;
     }
     if (!e->cap_stream && hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking) != hipSuccess) {
@@ -2068,8 +2101,8 @@ static mimi_engine::Graph* capture_graph(mimi_engine* e, const float* audio, int
     // from the zeros the previous encode's fold left behind)
     rc = encode_pass(e, audio, B, L, K, codes, cs, PREC_F16X3);
     // (+ the ticket's host words from inside the graph: destinations through io_dev, set before each replay)
-    if (!rc && launch_amax_reduce(e->amax_dev, (int)e->slot_of.size(), e->amax_red, cs, nullptr, e->chain_flag, nullptr,
-                                  e->io_dev) != hipSuccess)
+    if (!rc && launch_amax_reduce(e->ln->amax_dev, (int)e->slot_of.size(), e->ln->amax_red, cs, nullptr, e->chain_flag, nullptr,
+                                  e->ln->io_dev) != hipSuccess)
         rc = MIMI_ERR_HIP;
     e->capturing = false;
     hipGraph_t g = nullptr;
@@ -2081,26 +2114,26 @@ static mimi_engine::Graph* capture_graph(mimi_engine* e, const float* audio, int
         if (g) (void)hipGraphDestroy(g);
         return nullptr;
     }
-    if ((int)e->graphs.size() >= mimi_engine::kMaxGraphs) {  // evict the least recently used
+    if ((int)e->ln->graphs.size() >= mimi_engine::kMaxGraphs) {  // evict the least recently used
         size_t lru = 0;
-        for (size_t i = 1; i < e->graphs.size(); ++i)
-            if (e->graphs[i].used < e->graphs[lru].used) lru = i;
-        destroy_graph(e->graphs[lru]);
-        e->graphs.erase(e->graphs.begin() + (long)lru);
+        for (size_t i = 1; i < e->ln->graphs.size(); ++i)
+            if (e->ln->graphs[i].used < e->ln->graphs[lru].used) lru = i;
+        destroy_graph(e->ln->graphs[lru]);
+        e->ln->graphs.erase(e->ln->graphs.begin() + (long)lru);
     }
     mimi_engine::Graph ng;
     ng.B = B;
     ng.L = L;
     ng.K = K;
-    ng.ws_gen = e->ws_gen;
+    ng.ws_gen = e->ln->ws_gen;
     ng.rope_gen = e->rope_gen;
     ng.g = g;
     ng.x = x;
     ng.chain_flag = e->chain_flag;
     ng.chain_clear = e->chain_flag ? e->cap_chain_clear : 0;
-    e->graphs.push_back(ng);
+    e->ln->graphs.push_back(ng);
     ++e->graph_captures;
-    return &e->graphs.back();
+    return &e->ln->graphs.back();
 }
 
 // Runs the f16x3 pass of (B, L, K) as a graph replay on s when it can (*replayed = true); otherwise leaves
@@ -2116,10 +2149,10 @@ static int graph_encode(mimi_engine* e, const float* audio, int B, int64_t L, in
     if (rc) return rc;
     if ((rc = ensure_rope(e, p.frames25))) return rc;
     mimi_engine::Graph* gr = nullptr;
-    for (auto it = e->graphs.begin(); it != e->graphs.end();) {
-        if (it->ws_gen != e->ws_gen || it->rope_gen != e->rope_gen) {
+    for (auto it = e->ln->graphs.begin(); it != e->ln->graphs.end();) {
+        if (it->ws_gen != e->ln->ws_gen || it->rope_gen != e->rope_gen) {
             destroy_graph(*it);
-            it = e->graphs.erase(it);
+            it = e->ln->graphs.erase(it);
             continue;
         }
         if (it->B == B && it->L == L && it->K == K) gr = &*it;
@@ -2127,8 +2160,8 @@ static int graph_encode(mimi_engine* e, const float* audio, int B, int64_t L, in
     }
     if (!gr) {
         const auto key = std::make_tuple(B, L, K);
-        if (e->graph_seen.size() > 256) e->graph_seen.clear();
-        if (++e->graph_seen[key] < 2) return MIMI_OK;  // a shape seen once runs eagerly
+        if (e->ln->graph_seen.size() > 256) e->ln->graph_seen.clear();
+        if (++e->ln->graph_seen[key] < 2) return MIMI_OK;  // a shape seen once runs eagerly
         gr = capture_graph(e, audio, B, L, K, codes);
         if (!gr) {
             e->graphs_enabled = false;  // capture unsupported here: stay eager from now on
@@ -2136,8 +2169,8 @@ static int graph_encode(mimi_engine* e, const float* audio, int B, int64_t L, in
         }
     }
     gr->used = ++e->graph_clock;
-    HIP_TRY(hipStreamWaitEvent(s, e->ws_free, 0));
-    LAUNCH_TRY(launch_set_io(e->io_dev, audio, codes, s, host_amax, host_flag, gr->chain_flag, gr->chain_clear),
+    HIP_TRY(hipStreamWaitEvent(s, e->ln->ws_free, 0));
+    LAUNCH_TRY(launch_set_io(e->ln->io_dev, audio, codes, s, host_amax, host_flag, gr->chain_flag, gr->chain_clear),
                "set_io");
     HIP_TRY(hipGraphLaunch(gr->x, s));
     ++e->graph_replays;
@@ -2146,10 +2179,61 @@ static int graph_encode(mimi_engine* e, const float* audio, int B, int64_t L, in
     return MIMI_OK;
 }
 
-// Enqueues one encode on s and returns its ticket without waiting.  In f16x3 the per-tensor maxima are folded
+// ---- lanes.  An encode is ~80 dependent launches; behind every one-tile-per-CU kernel all CUs fill their rings
+// together and later run their epilogues together, and nothing else is resident.  Callers that keep two encodes
+// enqueued (mimi_encode_async, waited one behind) get the second one's kernels into those phases: an encode that
+// takes a lane runs on the lane's own stream, ordered after the caller's stream at the call, in the lane's own
+// workspace; mimi_encode_wait synchronises the host on it.  Nothing is enqueued on the caller's stream behind it
+// (that would order the next encode's inputs behind this encode and serialise the lanes again).
+
+// Makes lane li usable on its own stream (first use: lane 1's buffers and event, the lane's stream).  false: it cannot
+// be (the error is cleared) -- the encode then runs where it would have without lanes.
+static bool lane_prepare(mimi_engine* e, int li) {
+    mimi_engine::Lane& l = e->lanes[li];
+    bool ok = true;
+    if (!l.stream) ok = hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking) == hipSuccess;
+    if (ok && !l.in_ready) ok = hipEventCreateWithFlags(&l.in_ready, hipEventDisableTiming) == hipSuccess;
+    if (ok && !l.ws_free) ok = hipEventCreateWithFlags(&l.ws_free, hipEventDisableTiming) == hipSuccess;
+    if (ok && !l.amax_dev) {
+        const size_t bytes = ((size_t)kMaxActSlots * AMAX_SLOT_WORDS + kMaxActSlots) * sizeof(unsigned);
+        ok = hipMalloc(&l.amax_dev, bytes) == hipSuccess;
+        if (ok) {
+            l.amax_red = l.amax_dev + (size_t)kMaxActSlots * AMAX_SLOT_WORDS;
+            // (on the lane's stream: everything that touches these words runs there, behind this)
+            ok = hipMemsetAsync(l.amax_dev, 0, bytes, l.stream) == hipSuccess;
+        } else {
+            l.amax_dev = nullptr;
+        }
+    }
+    if (!ok) (void)hipGetLastError();
+    return ok;
+}
+
+// The lane of a new encode that may take one: the lowest-numbered lane with no un-waited ticket, else the one with
+// fewer tickets.  A caller that never overlaps encodes therefore stays in lane 0: one workspace, one graph per shape.
+static int choose_lane(const mimi_engine* e) {
+    for (int i = 0; i < mimi_engine::kLanes; ++i)
+        if (e->lanes[i].tickets == 0) return i;
+    int best = 0;
+    for (int i = 1; i < mimi_engine::kLanes; ++i)
+        if (e->lanes[i].tickets < e->lanes[best].tickets) best = i;
+    return best;
+}
+
+// the active lane is lane 0 whenever no submission or wait is in progress
+struct LaneScope {
+    mimi_engine* e;
+    LaneScope(mimi_engine* x, int li) : e(x) { set(li); }
+    ~LaneScope() { set(0); }
+    void set(int li) { e->ln = &e->lanes[li]; }
+};
+
+// Enqueues one encode and returns its ticket without waiting: on its lane's stream behind the caller's stream s when
+// it takes a lane (may_lane and the "lanes" rule), else on s in lane 0.  In f16x3 the per-tensor maxima are folded
 // and copied to this ticket's pinned slot behind the encode; mimi_encode_wait checks them.
 static int encode_async_locked(mimi_engine* e, const float* audio, int B, int64_t L, int K, int32_t* codes,
-                               hipStream_t s, int64_t* ticket, const int64_t* lengths = nullptr) {
+                               hipStream_t s, int64_t* ticket, const int64_t* lengths = nullptr,
+                               bool may_lane = false) {
     mimi_engine::Pending* P = nullptr;
     for (auto& q : e->pend)
         if (q.id == 0) {
@@ -2180,6 +2264,10 @@ static int encode_async_locked(mimi_engine* e, const float* audio, int B, int64_
         if (!batched) {  // item by item, synchronously (the ticket's event is then already complete)
             if ((rc = ragged_item_by_item(e, audio, B, L, lengths, K, codes, s, prec))) return rc;
             HIP_TRY(hipEventRecord(P->done, s));
+            P->lane = 0;
+            ++e->lanes[0].tickets;
+            ++e->lanes[0].encodes;
+            e->lanes[0].excl = false;
             P->nslots = 0;
             P->h16 = false;
             P->ragged = false;
@@ -2214,6 +2302,44 @@ static int encode_async_locked(mimi_engine* e, const float* audio, int B, int64_
         }
         rt.fill(P->rg_pinned);
     }
+    // ---- the lane.  By default only what gains: f16x3 uniform batches on the per-level RVQ kernels (large grids).
+    // The persistent RVQ chain's slice workgroups spin on their peers and need the whole grid resident; another lane's
+    // LDS-heavy kernels on the same CUs would push it into give-ups and re-runs, so an encode that may launch it stays on
+    // the caller's stream in lane 0 and runs with the other lane idle.  Taps, per-stage profiling and every caller that
+    // goes on using s behind the call (may_lane false) stay there too.
+    const int64_t rvq_frames = (int64_t)B * plan_lengths(e->cfg, L).frames12;
+    const bool chain_el = h16 && e->rvq_chain != 0 && (rvq_frames + 31) / 32 * 8 < 256;  // (launch_rvq's small grids)
+    bool laned = may_lane && e->lanes_opt > 0 && h16 && !e->taps && e->profiling != 1 &&
+                 (e->lanes_opt == 2 || (!lengths && !chain_el));
+    int li = laned ? choose_lane(e) : 0;
+    LaneScope lane_scope(e, li);
+    if (laned && !lane_prepare(e, li)) {
+        if (li != 0 && lane_prepare(e, 0)) {
+            lane_scope.set(li = 0);
+        } else {
+            laned = false;
+            lane_scope.set(li = 0);
+        }
+    }
+    if (laned && li != 0) {  // lane 1's workspace, on its first use and when it grows: never at the encode's cost
+        const size_t need = ws_layout(e, B, plan_lengths(e->cfg, L), nullptr, PREC_F16X3, lengths != nullptr);
+        if (ensure_ws(e, need, e->ln->stream) != MIMI_OK) {
+            (void)hipGetLastError();
+            lane_scope.set(li = 0);
+            if (!lane_prepare(e, 0)) laned = false;
+        }
+    }
+    mimi_engine::Lane& lane = *e->ln;
+    if (laned) {  // the whole encode on the lane's stream, behind everything enqueued on the caller's so far
+        HIP_TRY(hipEventRecord(lane.in_ready, s));
+        s = lane.stream;
+        HIP_TRY(hipStreamWaitEvent(s, lane.in_ready, 0));
+    }
+    // an encode that may hold the chain wants the GPU to itself: it waits for the other lane, and the other lane's next
+    // encode waits for it
+    const bool excl = chain_el && !laned && e->lanes_opt > 0;
+    for (auto& o : e->lanes)
+        if (&o != &lane && o.ws_free && (excl || o.excl)) HIP_TRY(hipStreamWaitEvent(s, o.ws_free, 0));
     if (h16) {
         bool replayed = false;
         unsigned* cflag = nullptr;
@@ -2227,8 +2353,8 @@ static int encode_async_locked(mimi_engine* e, const float* audio, int B, int64_
             return rc;
         n = (int)e->slot_of.size();
         if (!replayed) {
-            HIP_TRY(hipStreamWaitEvent(s, e->ws_free, 0));  // the maxima buffers are part of the workspace
-            HIP_TRY(hipMemsetAsync(e->amax_dev, 0, (size_t)kMaxActSlots * AMAX_SLOT_WORDS * sizeof(unsigned), s));
+            HIP_TRY(hipStreamWaitEvent(s, e->ln->ws_free, 0));  // the maxima buffers are part of the workspace
+            HIP_TRY(hipMemsetAsync(e->ln->amax_dev, 0, (size_t)kMaxActSlots * AMAX_SLOT_WORDS * sizeof(unsigned), s));
             e->uncalibrated_slot = false;
             if ((rc = encode_pass(e, audio, B, L, K, codes, s, PREC_F16X3, lengths ? &rt : nullptr, P->rg_pinned)))
                 return rc;
@@ -2239,15 +2365,19 @@ static int encode_async_locked(mimi_engine* e, const float* audio, int B, int64_
             cflag = e->chain_flag;
             // the maxima and (chain) the give-up flag also into the ticket's pinned words, before ws_free (the next
             // encode's memset node zeroes the flag); a replay's graph ends with the same kernel (capture_graph)
-            LAUNCH_TRY(launch_amax_reduce(e->amax_dev, n, e->amax_red, s, P->amax, cflag, cflag ? P->chain_word : nullptr),
+            LAUNCH_TRY(launch_amax_reduce(e->ln->amax_dev, n, e->ln->amax_red, s, P->amax, cflag, cflag ? P->chain_word : nullptr),
                        "amax_reduce");
         }
         P->chain = cflag != nullptr;
-        HIP_TRY(hipEventRecord(e->ws_free, s));
+        HIP_TRY(hipEventRecord(e->ln->ws_free, s));
     } else if ((rc = encode_pass(e, audio, B, L, K, codes, s, prec))) {
         return rc;
     }
     HIP_TRY(hipEventRecord(P->done, s));
+    P->lane = li;
+    ++lane.tickets;
+    ++lane.encodes;
+    lane.excl = excl;
     P->nslots = n;
     P->h16 = h16;
     P->audio = audio;
@@ -2298,6 +2428,8 @@ static int encode_wait(mimi_engine* e, int64_t ticket) {
     }
     P->claimed = false;
     P->id = 0;
+    --e->lanes[q.lane].tickets;
+    LaneScope lane_scope(e, q.lane);  // the re-runs below: on the encode's stream, in its lane's workspace
     if (se != hipSuccess)
         return set_err(se == hipErrorOutOfMemory ? MIMI_ERR_OUT_OF_MEMORY : MIMI_ERR_HIP, "hipEventSynchronize: %s",
                        hipGetErrorString(se));
@@ -2349,7 +2481,8 @@ extern "C" int mimi_encode_async(mimi_engine* e, const float* audio, int32_t bat
     std::lock_guard<std::mutex> lk(e->mu);
     HIP_TRY(hipSetDevice(e->device));
     (void)hipGetLastError();  // a failure left by an unrelated earlier call must not fail this encode's launches
-    return encode_async_locked(e, audio, batch, length, K, codes, reinterpret_cast<hipStream_t>(stream), ticket);
+    return encode_async_locked(e, audio, batch, length, K, codes, reinterpret_cast<hipStream_t>(stream), ticket,
+                               nullptr, true);
 }
 
 static int check_ragged(mimi_engine* e, const int64_t* lengths, int32_t batch, int64_t max_length) {
@@ -2371,7 +2504,7 @@ extern "C" int mimi_encode_ragged_async(mimi_engine* e, const float* audio, cons
     HIP_TRY(hipSetDevice(e->device));
     (void)hipGetLastError();
     return encode_async_locked(e, audio, batch, max_length, K, codes, reinterpret_cast<hipStream_t>(stream), ticket,
-                               lengths);
+                               lengths, true);
 }
 
 extern "C" int mimi_encode_ragged(mimi_engine* e, const float* audio, const int64_t* lengths, int32_t batch,
@@ -2397,8 +2530,12 @@ extern "C" int mimi_encode(mimi_engine* e, const float* audio, int32_t batch, in
         HIP_TRY(hipSetDevice(e->device));
         (void)hipGetLastError();  // a failure left by an unrelated earlier call must not fail this encode's launches
         // NULL stream = the HIP null stream, as in every HIP API
+        // (a lane's stream only beside another encode in flight, another thread's: alone, this call runs on the
+        // caller's stream as it always did -- it is waited right here, so there is nothing to overlap it with)
+        bool others = false;
+        for (const auto& l : e->lanes) others = others || l.tickets > 0;
         if ((rc = encode_async_locked(e, audio, batch, length, K, codes, reinterpret_cast<hipStream_t>(stream),
-                                      &ticket)))
+                                      &ticket, nullptr, others)))
             return rc;
     }
     return encode_wait(e, ticket);
@@ -2524,10 +2661,10 @@ extern "C" int mimi_rvq_encode(mimi_engine* e, const float* emb, int64_t frames,
     const int Hd = e->cfg.hidden_size, Dq = e->cfg.vq_hidden_dim;
     const size_t projb = ((size_t)frames * 2 * Dq * sizeof(float) + 255) / 256 * 256;
     const size_t need = projb + rvq_work_bytes(frames);
-    int rc = ensure_ws(e, std::max(need, e->ws_bytes), s);
+    int rc = ensure_ws(e, std::max(need, e->ln->ws_bytes), s);
     if (rc) return rc;
-    float* proj = reinterpret_cast<float*>(e->ws);
-    HIP_TRY(hipStreamWaitEvent(s, e->ws_free, 0));
+    float* proj = reinterpret_cast<float*>(e->ln->ws);
+    HIP_TRY(hipStreamWaitEvent(s, e->ln->ws_free, 0));
     Recorder rec{e, s};
     rec.begin();
     GemmArgs ap = linear_args(emb, frames, Hd, e->inproj, 2 * Dq, proj);
@@ -2535,7 +2672,7 @@ extern "C" int mimi_rvq_encode(mimi_engine* e, const float* emb, int64_t frames,
     LAUNCH_TRY(launch_gemm(ROLE_INPROJ, ap, s, &kname), "input_proj");
     rec.mark("input_proj", 2.0 * frames * Hd * 2 * Dq, 0, kname);
     e->chain_ok = true;  // (checked right here: a give-up re-runs the levels on the per-level kernels)
-    rc = run_rvq(e, proj, frames, K, codes, 0, reinterpret_cast<char*>(e->ws) + projb, s, rec);
+    rc = run_rvq(e, proj, frames, K, codes, 0, reinterpret_cast<char*>(e->ln->ws) + projb, s, rec);
     e->chain_ok = false;
     if (rc) return rc;
     if (e->chain_flag) {
@@ -2545,10 +2682,10 @@ extern "C" int mimi_rvq_encode(mimi_engine* e, const float* emb, int64_t frames,
         e->chain_flag = nullptr;
         if (flag) {
             ++e->chain_reruns;
-            if ((rc = run_rvq(e, proj, frames, K, codes, 0, reinterpret_cast<char*>(e->ws) + projb, s, rec))) return rc;
+            if ((rc = run_rvq(e, proj, frames, K, codes, 0, reinterpret_cast<char*>(e->ln->ws) + projb, s, rec))) return rc;
         }
     }
-    HIP_TRY(hipEventRecord(e->ws_free, s));
+    HIP_TRY(hipEventRecord(e->ln->ws_free, s));
     return MIMI_OK;
 }
 
@@ -3025,19 +3162,16 @@ extern "C" void mimi_destroy(mimi_engine* e) {
     (void)hipSetDevice(e->device);
     // this engine's work only (every encode ends with ws_free on its stream; a device-wide sync would wait for
     // other engines and is refused while one of them captures a graph)
-    if (e->ws_free) (void)hipEventSynchronize(e->ws_free);
+    drain_lanes(e);
     for (auto& q : e->pend)
         if (q.id && q.done) (void)hipEventSynchronize(q.done);
     for (void* p : e->allocations) (void)hipFree(p);
-    if (e->ws) (void)hipFree(e->ws);
     if (e->rope_cos) (void)hipFree(e->rope_cos);
     if (e->rope_sin) (void)hipFree(e->rope_sin);
     for (auto& kv : e->tapmap)
         if (kv.second.d) (void)hipFree(kv.second.d);
     for (auto& pe : e->pending) (void)hipEventDestroy(pe.ev);
     for (auto ev : e->event_pool) (void)hipEventDestroy(ev);
-    if (e->ws_free) (void)hipEventDestroy(e->ws_free);
-    if (e->amax_dev) (void)hipFree(e->amax_dev);
     if (e->amax_host) (void)hipHostFree(e->amax_host);
     if (e->item_codes) (void)hipFree(e->item_codes);
     if (e->dws) (void)hipFree(e->dws);
@@ -3056,7 +3190,14 @@ extern "C" void mimi_destroy(mimi_engine* e) {
         if (h.h_codes) (void)hipHostFree(h.h_codes);
     }
     drop_graphs(e);
-    if (e->io_dev) (void)hipFree(e->io_dev);
+    for (auto& l : e->lanes) {
+        if (l.ws) (void)hipFree(l.ws);
+        if (l.amax_dev) (void)hipFree(l.amax_dev);
+        if (l.io_dev) (void)hipFree(l.io_dev);
+        if (l.ws_free) (void)hipEventDestroy(l.ws_free);
+        if (l.in_ready) (void)hipEventDestroy(l.in_ready);
+        if (l.stream) (void)hipStreamDestroy(l.stream);
+    }
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
     delete e;
 }
@@ -3069,6 +3210,10 @@ extern "C" int mimi_set_precision(mimi_engine* e, int32_t mode) {
     if (mode < MIMI_PRECISION_F32 || mode > MIMI_PRECISION_F16X3)
         return set_err(MIMI_ERR_INVALID_ARGUMENT, "precision mode %d", mode);
     std::lock_guard<std::mutex> lk(e->mu);
+    if (e->precision != mode) {  // (the encodes in flight in either lane finish in the mode they were submitted in)
+        HIP_TRY(hipSetDevice(e->device));
+        drain_lanes(e);
+    }
     e->precision = mode;
     return MIMI_OK;
 }
@@ -3078,16 +3223,17 @@ extern "C" int mimi_set_graphs(mimi_engine* e, int32_t enable) {
     std::lock_guard<std::mutex> lk(e->mu);
     HIP_TRY(hipSetDevice(e->device));
     e->graphs_enabled = enable != 0;
-    if (!enable) {
-        drop_graphs(e);
-        e->graph_seen.clear();
-    }
+    if (!enable) drop_graphs(e, true);
     return MIMI_OK;
 }
 
 extern "C" int64_t mimi_graph_replays(const mimi_engine* e) { return e ? e->graph_replays : -1; }
 
 extern "C" int64_t mimi_graph_captures(const mimi_engine* e) { return e ? e->graph_captures : -1; }
+
+extern "C" int64_t mimi_lane_encodes(const mimi_engine* e, int32_t lane) {
+    return e && lane >= 0 && lane < mimi_engine::kLanes ? e->lanes[lane].encodes : -1;
+}
 
 // mimi_set_option keys: engine field, allowed values (bit v of `allowed` set: value v accepted), what they select.
 // Every key changes the kernel sequence (never the bits an encode produces), so a change drops captured graphs.
@@ -3113,6 +3259,7 @@ static const EngineOption kEngineOptions[] = {
     {"gemm256", &mimi_engine::gemm256, 0xffu, "0..7"},
     {"res1_form", &mimi_engine::res1_form, 0x3u, "0 or 1"},
     {"res1_stream", &mimi_engine::res1_stream, 0x7u, "0, 1 or 2"},
+    {"lanes", &mimi_engine::lanes_opt, 0x7u, "0, 1 or 2"},
 };
 
 extern "C" int mimi_set_option(mimi_engine* e, const char* key, int64_t value) {
@@ -3123,10 +3270,9 @@ extern "C" int mimi_set_option(mimi_engine* e, const char* key, int64_t value) {
         if (value < 0 || value > 31 || !((o.allowed >> value) & 1u))
             return set_err(MIMI_ERR_INVALID_ARGUMENT, "%s %lld (%s)", key, (long long)value, o.values);
         HIP_TRY(hipSetDevice(e->device));
-        if (e->*o.field != (int)value) {  // captured graphs hold the other kernel sequence
-            drop_graphs(e);
-            e->graph_seen.clear();
-        }
+        drain_lanes(e);
+        // captured graphs hold the other kernel sequence (both lanes drained first: drop_graphs)
+        if (e->*o.field != (int)value) drop_graphs(e, true);
         e->*o.field = (int)value;
         return MIMI_OK;
     }
@@ -3277,7 +3423,7 @@ extern "C" int mimi_get_tap(mimi_engine* e, const char* name, float* dst, int64_
         HIP_TRY(hipSetDevice(e->device));
         // the taps were copied inside the last encode: wait for it alone (a device-wide sync is refused while any
         // other engine in the process captures a graph)
-        HIP_TRY(hipEventSynchronize(e->ws_free));
+        drain_lanes(e);
         if (!e->cap_stream) HIP_TRY(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
         HIP_TRY(hipMemcpyWithStream(dst, tp.d, n * 4, hipMemcpyDeviceToHost, e->cap_stream));
     }

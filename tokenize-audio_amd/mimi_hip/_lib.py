@@ -24,7 +24,7 @@ STATUS_NAMES = {
 # every symbol include/mimi_hip.h declares (tests check the library exports exactly these)
 EXPORTED_SYMBOLS = (
     "mimi_config_default", "mimi_config_from_json", "mimi_create_from_dir", "mimi_create", "mimi_set_weight", "mimi_load_safetensors", "mimi_finalize",
-    "mimi_encode", "mimi_encode_async", "mimi_encode_wait", "mimi_encode_host", "mimi_encode_ragged", "mimi_encode_ragged_async", "mimi_rvq_encode", "mimi_set_precision", "mimi_get_precision", "mimi_calibrate", "mimi_f16_reruns", "mimi_rvq_chain_reruns", "mimi_set_graphs", "mimi_graph_replays", "mimi_graph_captures", "mimi_set_option", "mimi_act_scales", "mimi_encoded_length",
+    "mimi_encode", "mimi_encode_async", "mimi_encode_wait", "mimi_encode_host", "mimi_encode_ragged", "mimi_encode_ragged_async", "mimi_rvq_encode", "mimi_set_precision", "mimi_get_precision", "mimi_calibrate", "mimi_f16_reruns", "mimi_rvq_chain_reruns", "mimi_set_graphs", "mimi_graph_replays", "mimi_graph_captures", "mimi_lane_encodes", "mimi_set_option", "mimi_act_scales", "mimi_encoded_length",
     "mimi_encoded_length_cfg",
     "mimi_workspace_bytes", "mimi_destroy", "mimi_last_error", "mimi_set_profiling", "mimi_profile_read",
     "mimi_profile_reset", "mimi_profile_sequence", "mimi_set_taps", "mimi_get_tap", "mimi_resample_poly",
@@ -102,6 +102,7 @@ def _declare(lib):
         "mimi_set_graphs": (c.c_int, [vp, c.c_int32]),
         "mimi_graph_replays": (c.c_int64, [vp]),
         "mimi_graph_captures": (c.c_int64, [vp]),
+        "mimi_lane_encodes": (c.c_int64, [vp, c.c_int32]),
         "mimi_set_option": (c.c_int, [vp, c.c_char_p, c.c_int64]),
         "mimi_act_scales": (c.c_int, [vp, c.c_int32, c.c_char_p, c.POINTER(c.c_float), c.POINTER(c.c_float),
                                       c.POINTER(c.c_int32)]),

@@ -465,6 +465,11 @@ class MimiHipModel:
         """Graphs captured so far (a graph retired by a workspace or RoPE-table reallocation is captured again)."""
         return int(self._lib.mimi_graph_captures(self._h))
 
+    @property
+    def lane_encodes(self):
+        """Encodes submitted to each of the engine's two lanes (encodes that take no lane count in lane 0)."""
+        return tuple(int(self._lib.mimi_lane_encodes(self._h, i)) for i in range(2))
+
     def set_option(self, key: str, value: int):
         """Kernel-variant option (identical codes either way): "stage0_fused" 0 = stage-0 block and down conv 0 as
         two kernels, 1 = one fused kernel (default); "ln_fused" 0 = LayerNorm launches before q/k/v and fc1, on small
