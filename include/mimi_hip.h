@@ -195,8 +195,8 @@ int mimi_rvq_encode(mimi_engine* e, const float* dev_embedding, int64_t frames, 
  *
  * ARITHMETIC: decode always runs the fp32-MFMA form of the GEMMs (MIMI_PRECISION_F32) and the fp32 attention and
  * residual-block kernels, whatever mimi_set_precision says -- no activation scales, hence no calibration, overflow
- * read-back or fallback.  Not provided: f16x3 decode, hipGraph replay of decode, ragged decode, streaming (KV-cache /
- * padding-cache) decode.
+ * read-back or fallback.  Mixed-length batches: mimi_decode_ragged.  Not provided: f16x3 decode, hipGraph replay of
+ * decode, streaming (KV-cache / padding-cache) decode.
  */
 enum { MIMI_CREATE_DECODE = 1 };
 int mimi_enable_decode(mimi_engine* e);
@@ -229,6 +229,30 @@ int mimi_rvq_decode(mimi_engine* e, const int32_t* dev_codes, int64_t frames, in
 
 /* Device bytes mimi_decode's workspace needs for (batch, frames); grown on demand. */
 int64_t mimi_decode_workspace_bytes(const mimi_engine* e, int32_t batch, int64_t frames);
+
+/*
+ * Ragged decode: a mixed-length batch of codes in one pass, the mirror of mimi_encode_ragged.  dev_codes device int32
+ * [batch][num_quantizers][max_frames], item b's codes being [:, :frame_lengths[b]]; codes past an item's length are
+ * NEVER READ (any bit pattern there neither raises the bounds flag nor changes a sample).  dev_audio device f32
+ * [batch][mimi_decoded_length(max_frames)]: item b's samples are the first mimi_decoded_length(frame_lengths[b]) of its
+ * row, the rest of the row is left untouched.  frame_lengths: host, [batch], each in [1, max_frames] (else
+ * MIMI_ERR_INVALID_ARGUMENT, nothing launched); it need not outlive the call.
+ * CONTRACT: item b's samples are bitwise those of mimi_decode on that item alone at its own length, whatever its
+ * batch-mates, their lengths, the batch size and the engine's history.  Every stage works on packed rows (item b's
+ * rows of a stage at rate factor f start at row f x sum(frame_lengths[:b])): the number of launches does not depend on
+ * batch, no stage touches rows past an item's length, and every item gets the attention kernel it would run alone.
+ * State, num_quantizers, bad-code (inside an item's length), MIMI_ERR_UNSUPPORTED (a row index past 32 bits, at any
+ * rate, over the sum of the lengths) and MIMI_ERR_OUT_OF_MEMORY behaviour as mimi_decode; synchronous, serialised by
+ * the engine's mutex, fp32 MFMA always, no lane, no graph; shares mimi_decode's workspace.  Taps are stored packed,
+ * [1][f x sum of lengths][channels]; profiling records mimi_decode's stages (with items on both sides of the
+ * 256-row attention threshold, two dec_attention records per layer).
+ */
+int mimi_decode_ragged(mimi_engine* e, const int32_t* dev_codes, const int64_t* frame_lengths /* host, [batch] */,
+                       int32_t batch, int64_t max_frames, int32_t num_quantizers, float* dev_audio, void* stream);
+
+/* Device bytes mimi_decode_ragged's workspace needs: mimi_decode_workspace_bytes(e, 1, sum of frame_lengths) plus the
+ * int tables (under 4096 + 256 x batch bytes).  -1 on a NULL argument, batch <= 0 or a length < 1. */
+int64_t mimi_decode_ragged_workspace_bytes(const mimi_engine* e, const int64_t* frame_lengths, int32_t batch);
 
 /*
  * Host-only: the weight re-layout that turns a causal MimiConvTranspose1d (kernel 2 ratio, stride ratio, weight

@@ -153,4 +153,141 @@ hipError_t launch_final_conv(const float* x, const float* w, const float* bias, 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Ragged forms (mimi_decode_ragged): item b = blockIdx.y has tlen[b] rows of this stage starting at row toff[b] of the
+// packed tensor (the stage's own table: lengths and offsets already times its rate factor).  The grid covers the
+// longest item; a workgroup (or wave) whose rows start at or past its item's length exits before any load, so nothing
+// past an item's length is read, computed or stored.  Per row the arithmetic is the uniform kernel's, statement for
+// statement: an item's values are the bits of its own launch.
+// ------------------------------------------------------------------------------------------------
+// codes [B][K][Ts] (Ts = the padded row stride; columns >= tlen[b] are never read) -> out [sum tlen][2*D]
+__global__ __launch_bounds__(256) void rvq_decode_ragged_kernel(const int32_t* __restrict__ codes, int Ts, int K, int nsem,
+                                                                int ncodes, const float* __restrict__ cb_rows,
+                                                                float* __restrict__ out, unsigned* __restrict__ flag,
+                                                                const int* __restrict__ tlen,
+                                                                const int* __restrict__ toff) {
+    constexpr int D = 256;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const long long b = blockIdx.y;
+    const int t = (int)blockIdx.x * 2 + (wave >> 1);
+    if (t >= tlen[b]) return;
+    const long long frame = (long long)toff[b] + t;
+    const int half = wave & 1;
+    const int lv0 = half ? nsem : 0;
+    const int lv1 = half ? K : (K < nsem ? K : nsem);
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    bool bad = false;
+    for (int lv = lv0; lv < lv1; ++lv) {
+        const int32_t code = codes[(b * K + lv) * (long long)Ts + t];
+        unsigned c = (unsigned)code;
+        if (c >= (unsigned)ncodes) {  // (negative codes wrap above ncodes)
+            bad = true;
+            c = 0u;
+        }
+        const f32x4 v = *reinterpret_cast<const f32x4*>(cb_rows + ((long long)lv * ncodes + c) * D + 4 * lane);
+        acc = acc + v;
+    }
+    if (bad && lane == 0) atomicOr(flag, 1u);
+    *reinterpret_cast<f32x4*>(out + frame * (2 * D) + half * D + 4 * lane) = acc;
+}
+
+hipError_t launch_rvq_decode_ragged(const int32_t* codes, int batch, int Ts, int max_tlen, int K, int nsem, int ncodes,
+                                    int D, const float* cb_rows, float* out, unsigned* flag, const int* tlen,
+                                    const int* toff, hipStream_t s) {
+    if (D != 256 || batch <= 0 || batch > 65535 || max_tlen <= 0 || max_tlen > Ts || K < 1 || nsem < 1 || ncodes < 1 ||
+        !codes || !cb_rows || !out || !flag || !tlen || !toff)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rvq_decode_ragged_kernel, dim3((unsigned)((max_tlen + 1) / 2), (unsigned)batch), dim3(256), 0, s,
+                       codes, Ts, K, nsem, ncodes, cb_rows, out, flag, tlen, toff);
+    return hipGetLastError();
+}
+
+// x [sum tlen][C] -> y [2 sum tlen][C]; x[t - 1] = 0 at each item's first frame (t is the position in the item)
+__global__ __launch_bounds__(256) void upsample_dw_ragged_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                 float* __restrict__ y, int C4,
+                                                                 const int* __restrict__ tlen,
+                                                                 const int* __restrict__ toff) {
+    const int b = blockIdx.y;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int t = (int)(i / C4);
+    if (t >= tlen[b]) return;
+    const int c4 = (int)(i - (long long)t * C4);
+    const long long row = (long long)toff[b] + t;
+    const int C = C4 * 4;
+    const f32x4 x1 = *reinterpret_cast<const f32x4*>(x + row * C + 4 * c4);
+    f32x4 x0 = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (t > 0) x0 = *reinterpret_cast<const f32x4*>(x + (row - 1) * C + 4 * c4);
+    f32x4 o0, o1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const f32x4 wc = *reinterpret_cast<const f32x4*>(w + (long long)(4 * c4 + e) * 4);
+        o0[e] = wc[0] * x1[e] + wc[2] * x0[e];
+        o1[e] = wc[1] * x1[e] + wc[3] * x0[e];
+    }
+    float* yo = y + (2 * row) * C + 4 * c4;
+    *reinterpret_cast<f32x4*>(yo) = o0;
+    *reinterpret_cast<f32x4*>(yo + C) = o1;
+}
+
+hipError_t launch_upsample_dw_ragged(const float* x, const float* w, float* y, int batch, int max_tlen, int C,
+                                     const int* tlen, const int* toff, hipStream_t s) {
+    if (batch <= 0 || batch > 65535 || max_tlen <= 0 || C <= 0 || C % 4 || !x || !w || !y || !tlen || !toff)
+        return hipErrorInvalidValue;
+    const long long blocks = ((long long)max_tlen * (C / 4) + 255) / 256;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(upsample_dw_ragged_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(256), 0, s, x, w, y,
+                       C / 4, tlen, toff);
+    return hipGetLastError();
+}
+
+// x [sum llen][64] packed -> y [B][Ls] padded (row stride Ls); samples >= llen[b] of row b are left untouched
+__global__ __launch_bounds__(FC_TILE) void final_conv_ragged_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                    const float* __restrict__ bias, float* __restrict__ y,
+                                                                    long long Ls, const int* __restrict__ llen,
+                                                                    const int* __restrict__ loff) {
+    __shared__ __attribute__((aligned(16))) float xs[(FC_TILE + 2) * FC_LD];
+    __shared__ __attribute__((aligned(16))) float ws[3 * FC_C];
+    const int tid = threadIdx.x;
+    const long long l0 = (long long)blockIdx.x * FC_TILE;
+    const long long L = llen[blockIdx.y];
+    if (l0 >= L) return;
+    const float* __restrict__ xb = x + (long long)loff[blockIdx.y] * FC_C;
+    for (int i = tid; i < 3 * FC_C; i += FC_TILE) ws[i] = w[i];
+    for (int idx = tid; idx < (FC_TILE + 2) * (FC_C / 4); idx += FC_TILE) {
+        const int r = idx >> 4, c4 = idx & 15;
+        const long long g = l0 - 2 + r;
+        f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (g >= 0 && g < L) v = *reinterpret_cast<const f32x4*>(xb + g * FC_C + 4 * c4);
+        *reinterpret_cast<f32x4*>(xs + r * FC_LD + 4 * c4) = v;
+    }
+    __syncthreads();
+    const long long l = l0 + tid;
+    if (l >= L) return;
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int c4 = 0; c4 < FC_C / 4; ++c4) {
+            const f32x4 xv = *reinterpret_cast<const f32x4*>(xs + (tid + k) * FC_LD + 4 * c4);
+            const f32x4 wv = *reinterpret_cast<const f32x4*>(ws + k * FC_C + 4 * c4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = __builtin_fmaf(xv[e], wv[e], acc[e]);
+        }
+    y[(long long)blockIdx.y * Ls + l] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + bias[0];
+}
+
+hipError_t launch_final_conv_ragged(const float* x, const float* w, const float* bias, float* y, int batch, long long Ls,
+                                    long long max_llen, int C, int ksize, const int* llen, const int* loff,
+                                    hipStream_t s) {
+    if (C != FC_C || ksize != 3 || batch <= 0 || batch > 65535 || max_llen <= 0 || max_llen > Ls || !x || !w || !bias ||
+        !y || !llen || !loff)
+        return hipErrorInvalidValue;
+    const long long tiles = (max_llen + FC_TILE - 1) / FC_TILE;
+    if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(final_conv_ragged_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(FC_TILE), 0, s, x, w, bias,
+                       y, Ls, llen, loff);
+    return hipGetLastError();
+}
+
 }  // namespace mimi

@@ -411,6 +411,8 @@ struct mimi_engine {
     size_t dws_bytes = 0;
     unsigned* dec_flag = nullptr;       // device word: a code outside [0, codebook_size) was seen
     unsigned* dec_flag_host = nullptr;  // pinned
+    int* dec_rg_host = nullptr;         // pinned: the host image of a ragged decode's length tables (DecRagged)
+    size_t dec_rg_cap = 0;              // ints
 };
 
 static int dev_alloc(mimi_engine* e, void** p, size_t bytes) {
@@ -2705,7 +2707,8 @@ extern "C" int mimi_rvq_encode(mimi_engine* e, const float* emb, int64_t frames,
 // so the channels-last GEMM output [T][r Cout] IS the up-sampled tensor [T r][Cout]: no pixel-shuffle pass.
 // ARITHMETIC: decode always runs the fp32-MFMA GEMMs and the fp32 attention / residual-block kernels (PREC_F32),
 // whatever mimi_set_precision says: no activation scales, so no calibration, no overflow read-back, no fallback.
-// Not built here: f16x3 decode, hipGraph capture of decode, ragged decode, KV-cache / streaming decode.
+// A mixed-length batch runs in one pass over packed rows: "ragged decode" below (mimi_decode_ragged).
+// Not built here: f16x3 decode, hipGraph capture of decode, KV-cache / streaming decode.
 
 static int64_t decode_upsampling(const mimi_config& c) {
     int64_t f = 2;  // upsample: 12.5 -> 25 Hz
@@ -3003,13 +3006,32 @@ extern "C" int mimi_rvq_decode(mimi_engine* e, const int32_t* dev_codes, int64_t
     return read_decode_flag(e, s);
 }
 
+// Ragged decode (mimi_decode_ragged): every stage's rows are PACKED, item b's rows of a stage at rate factor f starting
+// at row f * toff[b] of one [f * sumT][C] tensor (toff = the prefix sum of the frame lengths; f = 1 for the 12.5 Hz
+// frames, 2 for the 25 Hz ones, then 2 r0, 2 r0 r1, ... behind each up conv) -- the transformer-section layout of
+// encode's RaggedTable carried through the whole pass.  The factors are integers, so one (tlen, toff) pair describes
+// every stage; the device image holds it once per stage already multiplied, [stage][tlen | toff][B] ints, so that the
+// kernels index an int table as the encode-side ragged kernels do.  Uploaded once per call from pinned memory.
+struct DecRagged {
+    int B = 0, nst = 0;
+    int64_t sumT = 0, maxT = 0, minT = 0;
+    std::vector<int64_t> f;  // rate factor per stage
+    const int* dev = nullptr;
+    const int* tlen(int st) const { return dev + (size_t)(2 * st) * B; }
+    const int* toff(int st) const { return dev + (size_t)(2 * st + 1) * B; }
+    static size_t ints(int B, int nst) { return (size_t)2 * nst * B; }
+};
+
 // The decoder transformer: the encoder's fp32 launches (LayerNorm, q/k/v + RoPE, attention, o_proj, fc1, fc2) on the
-// weight set xf over B items of T rows, residual stream in t0 (in place)
+// weight set xf over B items of T rows, residual stream in t0 (in place).  rg (ragged decode): the items' rows are
+// packed (stage 1 of rg: 2 tlen[b] rows at 2 toff[b]), T = the longest item's rows; the flat-row stages run unchanged
+// on the packed rows, q/k/v and attention per item
 static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, int B, int64_t T, float* t0, float* t1,
-                               float* qkv, float* att, float* ff, hipStream_t s, Recorder& rec, const char* stage_prefix) {
+                               float* qkv, float* att, float* ff, hipStream_t s, Recorder& rec, const char* stage_prefix,
+                               const DecRagged* rg = nullptr) {
     const mimi_config& c = e->cfg;
     const int Hd = c.hidden_size, H = c.num_attention_heads, Dh = c.head_dim;
-    const int64_t rows = (int64_t)B * T;
+    const int64_t rows = rg ? 2 * rg->sumT : (int64_t)B * T;
     const std::string sp = stage_prefix;
     const char* kname = "?";
     double att_flops = 0;
@@ -3032,13 +3054,37 @@ static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, i
         aq.rope_cos = e->rope_cos;
         aq.rope_sin = e->rope_sin;
         aq.rope_cols = 2 * H * Dh;
+        if (rg) {  // per item: rows, zero padding and RoPE position relative to the item's first row
+            aq.a_rows = aq.m_rows = rg->tlen(1);
+            aq.a_boff = aq.c_boff = rg->toff(1);
+        }
         LAUNCH_TRY(launch_gemm(ROLE_QKV, aq, s, &kname, PREC_F32), "qkv");
         rec.mark(sp + "qkv", fl(aq), by(aq, false), kname);
         const char* akn = T <= 256 ? "mimi::attention_t256_kernel" : "mimi::attention_kernel";
-        LAUNCH_TRY(launch_attention(qkv, att, B, (int)T, H, Dh, c.sliding_window, 1.0f / std::sqrt((float)Dh), s, att,
-                                    rows * Hd, 0, 0.0f, nullptr, false, nullptr, 0, 0, nullptr, &akn, e->attn_band_split),
-                   "attention");
-        rec.mark(sp + "attention", att_flops, (double)rows * 4 * Hd * 4, akn);
+        if (rg) {
+            // each item the kernel it would run alone: one launch per regime present (and one record each), each
+            // kernel exiting on the other's items
+            const int lo = (int)(2 * rg->minT), hi = (int)(2 * rg->maxT);
+            const float sc = 1.0f / std::sqrt((float)Dh);
+            if (lo <= 256) {
+                LAUNCH_TRY(launch_attention(qkv, att, B, 0, H, Dh, c.sliding_window, sc, s, nullptr, 0, 0, 0.0f, nullptr,
+                                            false, rg->tlen(1), std::min(hi, 256), lo, rg->toff(1), &akn),
+                           "attention");
+                rec.mark(sp + "attention", att_flops, (double)rows * 4 * Hd * 4, akn);
+            }
+            if (hi > 256) {
+                LAUNCH_TRY(launch_attention(qkv, att, B, 0, H, Dh, c.sliding_window, sc, s, nullptr, 0, 0, 0.0f, nullptr,
+                                            false, rg->tlen(1), hi, std::max(lo, 257), rg->toff(1), &akn),
+                           "attention");
+                rec.mark(sp + "attention", att_flops, (double)rows * 4 * Hd * 4, akn);
+            }
+        } else {
+            LAUNCH_TRY(launch_attention(qkv, att, B, (int)T, H, Dh, c.sliding_window, 1.0f / std::sqrt((float)Dh), s, att,
+                                        rows * Hd, 0, 0.0f, nullptr, false, nullptr, 0, 0, nullptr, &akn,
+                                        e->attn_band_split),
+                       "attention");
+            rec.mark(sp + "attention", att_flops, (double)rows * 4 * Hd * 4, akn);
+        }
         GemmArgs ao = linear_args(att, rows, H * Dh, x.wo, Hd, t0);
         ao.R = t0;
         ao.scale = x.ls1;
@@ -3157,6 +3203,217 @@ extern "C" int mimi_decode(mimi_engine* e, const int32_t* dev_codes, int32_t bat
     return read_decode_flag(e, s);
 }
 
+// ---- ragged decode: B items of frame_lengths[b] frames in one pass over packed rows (DecRagged) ----
+// Every stage either runs unchanged on the packed rows (the flat-row GEMMs and LayerNorm) or in its ragged form, which
+// takes an item's base and length from the table and otherwise repeats the uniform kernel's arithmetic: item b's
+// samples are bitwise those of mimi_decode on that item alone.  The workspace is decode's (dws), laid out as a B = 1
+// decode of sumT frames with the int tables behind it.
+static size_t pad256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+static int plan_decode_ragged(const mimi_engine* e, const int64_t* lengths, int32_t batch, DecRagged* rg) {
+    const mimi_config& c = e->cfg;
+    rg->B = batch;
+    rg->nst = 2 + c.num_ratios;
+    rg->f.assign(1, 1);
+    rg->f.push_back(2);
+    for (int i = 0; i < c.num_ratios; ++i) rg->f.push_back(rg->f.back() * c.upsampling_ratios[i]);
+    rg->sumT = 0;
+    rg->maxT = 0;
+    rg->minT = INT64_MAX;
+    for (int b = 0; b < batch; ++b) {
+        if (lengths[b] < 1) return 1;
+        rg->sumT += lengths[b];
+        rg->maxT = std::max(rg->maxT, lengths[b]);
+        rg->minT = std::min(rg->minT, lengths[b]);
+        if (rg->sumT > 0x7fffffffLL) return 2;
+    }
+    return 0;
+}
+
+extern "C" int64_t mimi_decode_ragged_workspace_bytes(const mimi_engine* e, const int64_t* frame_lengths, int32_t batch) {
+    if (!e || !frame_lengths || batch <= 0) return -1;
+    DecRagged rg;
+    if (plan_decode_ragged(e, frame_lengths, batch, &rg)) return -1;
+    return (int64_t)(decode_ws_layout(e, 1, rg.sumT, e->taps).bytes + pad256(DecRagged::ints(batch, rg.nst) * sizeof(int)));
+}
+
+// the "audio" tap of a ragged decode: the items' samples packed, as every other tap of the pass
+static int save_tap_audio_ragged(mimi_engine* e, const float* audio, const int64_t* lengths, const DecRagged& rg,
+                                 int64_t row_stride, hipStream_t s) {
+    if (!e->taps) return MIMI_OK;
+    auto& tp = e->tapmap["audio"];
+    const int64_t up = rg.f.back();
+    const size_t n = (size_t)(up * rg.sumT);
+    if (tp.cap < n) {
+        if (tp.d) HIP_TRY(hipFree(tp.d));
+        HIP_TRY(hipMalloc(&tp.d, n * 4));
+        tp.cap = n;
+    }
+    int64_t off = 0;
+    for (int b = 0; b < rg.B; ++b) {
+        HIP_TRY(hipMemcpyAsync(tp.d + up * off, audio + (size_t)b * row_stride, (size_t)(up * lengths[b]) * 4,
+                               hipMemcpyDeviceToDevice, s));
+        off += lengths[b];
+    }
+    tp.dims[0] = 1;
+    tp.dims[1] = (int64_t)n;
+    tp.dims[2] = 1;
+    return MIMI_OK;
+}
+
+static int decode_ragged_locked(mimi_engine* e, const int32_t* dev_codes, const int64_t* lengths, int B, int64_t Tmax,
+                                int K, float* dev_audio, hipStream_t s, DecRagged& rg) {
+    const mimi_config& c = e->cfg;
+    const int Hd = c.hidden_size, Dq = c.vq_hidden_dim;
+    const int64_t S = rg.sumT, S2 = 2 * S, M2 = 2 * rg.maxT;
+    int rc;
+    const size_t act_bytes = decode_ws_layout(e, 1, S, e->taps).bytes;
+    const size_t nints = DecRagged::ints(B, rg.nst);
+    if ((rc = ensure_dws(e, act_bytes + pad256(nints * sizeof(int))))) return rc;
+    const DecodeWs w = decode_ws_layout(e, 1, S, e->taps);
+    if ((rc = ensure_rope(e, M2))) return rc;
+    if (e->dec_rg_cap < nints) {
+        if (e->dec_rg_host) HIP_TRY(hipHostFree(e->dec_rg_host));
+        e->dec_rg_host = nullptr;
+        e->dec_rg_cap = 0;
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->dec_rg_host), nints * sizeof(int), hipHostMallocDefault));
+        e->dec_rg_cap = nints;
+    }
+    {
+        int* h = e->dec_rg_host;
+        for (int st = 0; st < rg.nst; ++st) {
+            int64_t off = 0;
+            for (int b = 0; b < B; ++b) {
+                h[(size_t)(2 * st) * B + b] = (int)(rg.f[st] * lengths[b]);
+                h[(size_t)(2 * st + 1) * B + b] = (int)(rg.f[st] * off);
+                off += lengths[b];
+            }
+        }
+    }
+    int* dtab = reinterpret_cast<int*>(reinterpret_cast<char*>(e->dws) + act_bytes);
+    HIP_TRY(hipMemcpyAsync(dtab, e->dec_rg_host, nints * sizeof(int), hipMemcpyHostToDevice, s));
+    rg.dev = dtab;
+    HIP_TRY(hipMemsetAsync(e->dec_flag, 0, sizeof(unsigned), s));
+    Recorder rec{e, s};
+    rec.begin();
+    const char* kname = "?";
+    auto fl = [&](const GemmArgs& a, int st) { return 2.0 * (double)(rg.f[st] * S) * a.N * a.K; };
+    auto by = [&](const GemmArgs& a, int st) { return ((double)(rg.f[st] * S) * (a.a_rs + a.N) + (double)a.N * a.K) * 4; };
+    auto per_item = [&](GemmArgs& a, int st) {
+        a.a_rows = a.m_rows = rg.tlen(st);
+        a.a_boff = a.c_boff = rg.toff(st);
+    };
+
+    // ---- quantizer.decode + upsample ----
+    float* sums = w.p;
+    float* emb = w.p + (size_t)S * 2 * Dq;
+    LAUNCH_TRY(launch_rvq_decode_ragged(dev_codes, B, (int)Tmax, (int)rg.maxT, K, c.num_semantic_quantizers,
+                                        c.codebook_size, c.codebook_dim, e->cb_rows, sums, e->dec_flag, rg.tlen(0),
+                                        rg.toff(0), s),
+               "rvq_decode (ragged)");
+    rec.mark("dec_rvq", (double)S * K * Dq, (double)S * (K * Dq + 2 * Dq) * 4, "mimi::rvq_decode_ragged_kernel");
+    {
+        GemmArgs ap = linear_args(sums, S, 2 * Dq, e->outproj, Hd, emb);
+        LAUNCH_TRY(launch_gemm(ROLE_INPROJ, ap, s, &kname, PREC_F32), "output_proj");
+        rec.mark("dec_output_proj", 2.0 * S * 2 * Dq * Hd, (double)S * (2 * Dq + Hd) * 4, kname);
+    }
+    if ((rc = save_tap(e, "quantized", emb, 1, S, Hd, s))) return rc;
+    float* t0 = w.q;
+    float* t1 = t0 + (size_t)S2 * Hd;
+    float* qkv = t1 + (size_t)S2 * Hd;
+    float* att = qkv + (size_t)S2 * 3 * c.num_attention_heads * c.head_dim;
+    float* ff = att + (size_t)S2 * Hd;
+    LAUNCH_TRY(launch_upsample_dw_ragged(emb, e->upsample_w, t0, B, (int)rg.maxT, Hd, rg.tlen(0), rg.toff(0), s),
+               "upsample (ragged)");
+    rec.mark("dec_upsample", 4.0 * S2 * Hd, 3.0 * S * Hd * 4, "mimi::upsample_dw_ragged_kernel");
+    if ((rc = save_tap(e, "upsample", t0, 1, S2, Hd, s))) return rc;
+
+    // ---- decoder transformer ----
+    if ((rc = run_transformer_f32(e, e->dxf, B, M2, t0, t1, qkv, att, ff, s, rec, "dec_", &rg))) return rc;
+    char nm[64];
+    snprintf(nm, sizeof nm, "xfmr%d", c.num_hidden_layers - 1);
+    if ((rc = save_tap(e, nm, t0, 1, S2, Hd, s))) return rc;
+
+    // ---- SEANet decoder ----
+    int C = c.num_filters << c.num_ratios;
+    if (e->taps) {
+        GemmArgs at = conv_args(e->dec_first, t0, M2, w.tap, M2, B);
+        per_item(at, 1);
+        LAUNCH_TRY(launch_gemm(ROLE_DOWN, at, s, &kname, PREC_F32), "decoder conv 0 (tap)");
+        rec.mark("dec_conv0_tap", fl(at, 1), by(at, 1), kname);
+        if ((rc = save_tap(e, "dconv0", w.tap, 1, S2, C, s))) return rc;
+    }
+    float* xe = w.p;
+    GemmArgs a0 = conv_args(e->dec_first, t0, M2, xe, M2, B);
+    per_item(a0, 1);
+    LAUNCH_TRY(launch_gemm(ROLE_DOWN_ELU, a0, s, &kname, PREC_F32), "decoder conv 0");
+    rec.mark("dec_conv0", fl(a0, 1), by(a0, 1), kname);
+    if ((rc = save_tap(e, "dconv0_elu", xe, 1, S2, C, s))) return rc;
+    for (int si = 0; si < c.num_ratios; ++si) {
+        const int st = 1 + si;  // the up conv's input (and GEMM rows); its output is stage st + 1
+        const DevConv& uc = e->dec_up[si];
+        const int64_t mlen = rg.f[st] * rg.maxT;
+        GemmArgs au = conv_args(uc, xe, mlen, w.q, mlen, B);
+        per_item(au, st);
+        LAUNCH_TRY(launch_gemm(ROLE_UPCONV, au, s, &kname, PREC_F32), "up conv");
+        snprintf(nm, sizeof nm, "dec_up_s%d", si);
+        rec.mark(nm, fl(au, st), by(au, st), kname);
+        C /= 2;
+        const int64_t rows = rg.f[st + 1] * S;
+        snprintf(nm, sizeof nm, "up%d", si);
+        if ((rc = save_tap(e, nm, w.q, 1, rows, C, s))) return rc;
+        ResArgs ra{};
+        ra.x = w.q;
+        ra.T = rg.f[st + 1] * rg.maxT;
+        ra.batch = B;
+        ra.w3 = e->dec_res3[si].w;
+        ra.b3 = e->dec_res3[si].b;
+        ra.w1 = e->dec_res1[si].w;
+        ra.b1 = e->dec_res1[si].b;
+        ra.y = xe;
+        ra.ilen = rg.tlen(st + 1);
+        ra.ioff = rg.toff(st + 1);
+        LAUNCH_TRY(launch_resblock(C, ra, s, &kname), "decoder resblock");
+        snprintf(nm, sizeof nm, "dec_res_s%d", si);
+        const double Hh = C / c.compress;
+        rec.mark(nm, 2.0 * rows * (3.0 * C * Hh + Hh * C), (double)rows * 2 * C * 4, kname);
+        snprintf(nm, sizeof nm, "dres%d_elu", si);
+        if ((rc = save_tap(e, nm, xe, 1, rows, C, s))) return rc;
+    }
+    const int last = rg.nst - 1;
+    const int64_t up = rg.f[last];
+    LAUNCH_TRY(launch_final_conv_ragged(xe, e->dec_last.w, e->dec_last.b, dev_audio, B, up * Tmax, up * rg.maxT, C,
+                                        c.last_kernel_size, rg.tlen(last), rg.toff(last), s),
+               "final conv (ragged)");
+    rec.mark("dec_final", 2.0 * up * S * C * c.last_kernel_size, (double)up * S * (C + 1) * 4,
+             "mimi::final_conv_ragged_kernel");
+    if ((rc = save_tap_audio_ragged(e, dev_audio, lengths, rg, up * Tmax, s))) return rc;
+    return read_decode_flag(e, s);
+}
+
+extern "C" int mimi_decode_ragged(mimi_engine* e, const int32_t* dev_codes, const int64_t* frame_lengths, int32_t batch,
+                                  int64_t max_frames, int32_t K, float* dev_audio, void* stream) {
+    if (!e) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null engine");
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = check_decode_state(e, K);
+    if (rc) return rc;
+    if (batch <= 0 || batch > 65535 || max_frames <= 0 || !dev_codes || !dev_audio)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "batch=%d max_frames=%lld", batch, (long long)max_frames);
+    if ((rc = check_ragged(e, frame_lengths, batch, max_frames))) return rc;
+    DecRagged rg;
+    // the kernels index packed rows with 32-bit ints at every rate, the caller's padded waveform rows too
+    if (plan_decode_ragged(e, frame_lengths, batch, &rg) || rg.sumT * decode_upsampling(e->cfg) > 0x7fffffffLL ||
+        max_frames * decode_upsampling(e->cfg) > 0x7fffffffLL)
+        return set_err(MIMI_ERR_UNSUPPORTED, "ragged decode of %lld frames in all exceeds the 32-bit row range",
+                       (long long)rg.sumT);
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    rc = decode_ragged_locked(e, dev_codes, frame_lengths, batch, max_frames, K, dev_audio, s, rg);
+    // the tables' pinned host image and the workspace are reused by the next call: nothing of this one stays in flight
+    if (rc) (void)hipStreamSynchronize(s);
+    return rc;
+}
+
 extern "C" void mimi_destroy(mimi_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
@@ -3176,6 +3433,7 @@ extern "C" void mimi_destroy(mimi_engine* e) {
     if (e->item_codes) (void)hipFree(e->item_codes);
     if (e->dws) (void)hipFree(e->dws);
     if (e->dec_flag_host) (void)hipHostFree(e->dec_flag_host);
+    if (e->dec_rg_host) (void)hipHostFree(e->dec_rg_host);
     for (auto& q : e->pend) {
         if (q.done) (void)hipEventDestroy(q.done);
         if (q.amax) (void)hipHostFree(q.amax);

@@ -490,6 +490,19 @@ static hipError_t dispatch_planes(int role, const GemmArgs& a, hipStream_t s) {
 
 static hipError_t dispatch(int role, const GemmArgs& a, hipStream_t s) {
     if (a.Ap) return dispatch_planes(role, a, s);
+    if (a.m_rows || a.a_rows || a.a_boff || a.c_boff) {
+        // packed ragged items on the fp32 kernel (the ragged decode pass): the role's instantiation with TAG + 100
+        // (gemm_kernel.h RG).  a.M = the longest item's rows picks the tile; <64, 128> and <128, 128> run the same
+        // 32-deep MFMA sequence per output element, so each item keeps the bits of its own launch
+        if (!a.m_rows || !a.a_rows || !a.a_boff || !a.c_boff || g_prec != PREC_F32 || a.R) return hipErrorInvalidValue;
+        switch (role) {
+            case ROLE_DOWN: return run_auto<false, PAD_ZERO, EPI_BIAS, 102>(a, s);
+            case ROLE_DOWN_ELU: return run_auto<false, PAD_ZERO, EPI_BIAS_ELU, 103>(a, s);
+            case ROLE_QKV: return run<64, 128, 1, 2, 32, 1, false, false, PAD_ZERO, EPI_ROPE, 105>(a, s);
+            case ROLE_UPCONV: return run_auto<false, PAD_ZERO, EPI_BIAS, 114>(a, s);
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (role) {
         case ROLE_DOWN: return run_prec<false, PAD_ZERO, EPI_BIAS, 2>(a, s, g_prec);
         case ROLE_DOWN_ELU: return run_prec<false, PAD_ZERO, EPI_BIAS_ELU, 3>(a, s, g_prec);

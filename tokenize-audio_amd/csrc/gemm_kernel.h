@@ -67,6 +67,12 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs p) {
     const int wave = tid >> 6;
     const int wm = wave / WN;
     const int wn = wave % WN;
+    // RG (TAG >= 100: the decode pass's packed ragged batches): item b has m_rows[b] output rows and a_rows[b] input
+    // rows starting at row a_boff[b] / c_boff[b] of one packed tensor; its rows, the [0, a_len) padding check and the
+    // RoPE position are relative to that base, as alone.  A tile past the item's rows exits before any load.
+    // (Grid order: an item's M tiles consecutive, as the uniform kernel.  The item fastest instead -- the same (M tile,
+    // N tile) of consecutive items sharing a weight slice -- measured slower: CHANGELOG.)
+    constexpr bool RG = TAG >= 100;
     const int b = blockIdx.z;
     // NFAST: consecutive workgroups walk the N tiles of one M tile, so an activation tile is re-read by the
     // other N tiles while it is still in L2 / the Infinity Cache instead of one full pass over M later.
@@ -83,9 +89,11 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs p) {
     }
     const int m0 = mt * BM;
     const int n0 = nt * BN;
-    const int M = p.M, N = p.N, K = p.K;
+    const int M = RG ? p.m_rows[b] : p.M, N = p.N, K = p.K;
+    if (RG && m0 >= M) return;
+    const long long a_len = RG ? (long long)p.a_rows[b] * p.a_cin : p.a_len;
 
-    const float* __restrict__ Ab = p.A + (long long)b * p.a_bstride;
+    const float* __restrict__ Ab = RG ? p.A + (long long)p.a_boff[b] * p.a_cin : p.A + (long long)b * p.a_bstride;
     const float* __restrict__ W = p.W;
 
     f32x4 ra[A_F4];
@@ -102,12 +110,12 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs p) {
             if (m < M) {
                 long long e = p.a_off + (long long)m * p.a_rs + k0 + c;
                 if (PAD == PAD_ZERO) {
-                    if (e >= 0 && e < p.a_len) v = *reinterpret_cast<const f32x4*>(Ab + e);
+                    if (e >= 0 && e < a_len) v = *reinterpret_cast<const f32x4*>(Ab + e);
                 } else {
                     const long long cin = p.a_cin;
                     long long t = e >= 0 ? e / cin : -((-e + cin - 1) / cin);
                     const long long ch = e - t * cin;
-                    const long long tmax = p.a_len / cin - 1;
+                    const long long tmax = a_len / cin - 1;
                     t = t < 0 ? 0 : (t > tmax ? tmax : t);
                     v = *reinterpret_cast<const f32x4*>(Ab + t * cin + ch);
                 }
@@ -194,8 +202,9 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs p) {
     }
 
     // ---- epilogue: lane holds col (lane&31), rows (r&3) + 8*(r>>2) + 4*(lane>>5) of each 32x32 tile
-    float* __restrict__ Cb = p.C + (long long)b * p.c_bstride;
-    const float* __restrict__ Rb = p.R ? p.R + (long long)b * p.c_bstride : nullptr;
+    const long long cbo = RG ? (long long)p.c_boff[b] * p.ldc : (long long)b * p.c_bstride;
+    float* __restrict__ Cb = p.C + cbo;
+    const float* __restrict__ Rb = p.R ? p.R + cbo : nullptr;
     const int rbase = m0 + wm * TM * 32 + 4 * (lane >> 5);
     const int cbase = n0 + wn * TN * 32 + (lane & 31);
 #pragma unroll

@@ -331,6 +331,9 @@ struct ResArgs {
     // stage 1 fp16 block (resblock128_h16_kernel): 0 = one 8-wave workgroup per CU, 1 = two 4-wave workgroups per CU
     // (engine option res1_form; which wave computes a tile only, the same bits)
     int form;
+    // ragged decode (fp32 resblock_ragged_kernel, C = 64 .. 512, no conv0 fusion): item b's ilen[b] rows start at row
+    // ioff[b] of the packed x / y; T = the longest item's rows (the grid).  null = the forms above
+    const int* ioff;
 };
 hipError_t launch_resblock(int C, const ResArgs& a, hipStream_t s, const char** kname);
 // stage 0 + down conv 0 in one kernel (PREC_F16X3)
@@ -356,6 +359,8 @@ hipError_t launch_layernorm(const float* x, const float* g, const float* b, floa
 // output [B][T][H*D].  h16: the fp16-plane kernels (PREC_F16X3; T <= 256 needs fp16-plane output), else fp32.
 // tlen (ragged batches, h16 only): item b has tlen[b] frames (T is the row stride); each item runs the kernel it
 // would run alone (tlen[b] <= 256: attention_t256_h16_kernel, else the banded one)
+// tlen with !h16 (the ragged decode pass): fp32 in and out on packed rows (toff required, T unused):
+// attention_t256_ragged_kernel where min_tlen <= 256, attention_ragged_kernel where max_tlen > 256
 hipError_t launch_attention(const float* qkv, float* out, int batch, int T, int H, int D, int window,
                             float scale, hipStream_t s, void* outp, long long out_pstride, int outns, float oscale,
                             unsigned* oamax, bool h16, const int* tlen = nullptr, int max_tlen = 0, int min_tlen = 0,
@@ -466,6 +471,17 @@ hipError_t launch_upsample_dw(const float* x, const float* w, float* y, int batc
 // the decoder's last conv (k = 3, causal, 64 -> 1): x [B][L][64] already ELU'd, w [3][64] tap-major, y [B][L]
 hipError_t launch_final_conv(const float* x, const float* w, const float* bias, float* y, int batch, long long L, int C,
                              int ksize, hipStream_t s);
+// Ragged forms (mimi_decode_ragged): packed rows, item b's tlen[b] rows of the stage start at row toff[b] (device int
+// tables of the stage's rate); max_tlen sizes the grid.  Codes keep the caller's padded [B][K][Ts] layout (columns past
+// tlen[b] are never read) and the waveform the padded [B][Ls] one (samples past llen[b] are left untouched).
+hipError_t launch_rvq_decode_ragged(const int32_t* codes, int batch, int Ts, int max_tlen, int K, int nsem, int ncodes,
+                                    int D, const float* cb_rows, float* out, unsigned* flag, const int* tlen,
+                                    const int* toff, hipStream_t s);
+hipError_t launch_upsample_dw_ragged(const float* x, const float* w, float* y, int batch, int max_tlen, int C,
+                                     const int* tlen, const int* toff, hipStream_t s);
+hipError_t launch_final_conv_ragged(const float* x, const float* w, const float* bias, float* y, int batch, long long Ls,
+                                    long long max_llen, int C, int ksize, const int* llen, const int* loff,
+                                    hipStream_t s);
 
 // polyphase resampler (resample.hip): clips packed at in_off / out_off (device int64 arrays), one launch
 hipError_t launch_resample_poly(const float* x, const long long* in_off, const long long* in_len, int nclips,

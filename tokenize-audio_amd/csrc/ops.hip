@@ -249,10 +249,13 @@ __device__ __forceinline__ void attn_chunk(f32x16 (&o)[2], float& m, float& l, c
     }
 }
 
-__global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                        int T, int H, int window, float scale,
-                                                        void* __restrict__ outp, long long pstride, int outns,
-                                                        float oscale, unsigned* __restrict__ oamax) {
+// RG (the ragged decode pass): item b has tlen[b] rows starting at packed row toff[b]; items of <= 256 rows belong to
+// the T <= 256 kernel and a tile past the item's rows has nothing to do: both exit before any load
+template <bool RG>
+__device__ __forceinline__ void attention_body(const float* __restrict__ qkv, float* __restrict__ out, int Ts, int H,
+                                               int window, float scale, void* __restrict__ outp, long long pstride,
+                                               int outns, float oscale, unsigned* __restrict__ oamax,
+                                               const int* __restrict__ tlen, const int* __restrict__ toff) {
     constexpr int D = 64;
     constexpr int KC = 32;
     constexpr int LDKS = D + 4;
@@ -264,10 +267,13 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hf = lane >> 5, col = lane & 31;
     const int q0 = blockIdx.x * 128;
+    const int T = RG ? tlen[b] : Ts;
+    if (RG && (T <= 256 || q0 >= T)) return;
+    const long long row0 = RG ? (long long)toff[b] : (long long)b * T;  // the item's first row
     const int qw = q0 + wave * 32;
     const int qi = qw + col;  // this lane's query (B operand column / S^T column)
     const long long ld = 3LL * H * D;
-    const float* base = qkv + (long long)b * T * ld;
+    const float* base = qkv + row0 * ld;
 
     // Q fragment (B operand): lane (q, hf) holds q[8kq + 4hf + s], kq = 0..7, pre-scaled
     f32x4 qf[8];
@@ -335,29 +341,47 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
     for (int qq = 0; qq < 32; ++qq) {
         const int q = qw + qq;
         if (q < T)
-            store_act(out, outp, pstride, outns, ((long long)b * T + q) * (H * D) + h * D + lane, ow[qq * LDO + lane],
+            store_act(out, outp, pstride, outns, (row0 + q) * (H * D) + h * D + lane, ow[qq * LDO + lane],
                       oscale, &mx);
     }
     amax_commit(oamax, mx);
 }
 
+__global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+                                                        int T, int H, int window, float scale,
+                                                        void* __restrict__ outp, long long pstride, int outns,
+                                                        float oscale, unsigned* __restrict__ oamax) {
+    attention_body<false>(qkv, out, T, H, window, scale, outp, pstride, outns, oscale, oamax, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void attention_ragged_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+                                                               int H, int window, float scale,
+                                                               const int* __restrict__ tlen,
+                                                               const int* __restrict__ toff) {
+    attention_body<true>(qkv, out, 0, H, window, scale, nullptr, 0, 0, 0.0f, nullptr, tlen, toff);
+}
+
 // T <= 256 (every 10 s clip: T = 250): one workgroup per (head, batch item) with the item's whole K and V
 // resident in LDS (loaded once, 128 KiB), 8 waves x 32 queries and no per-chunk barriers.  Wave w takes query
 // tile w (w < 4) or 11 - w, so the two waves sharing a SIMD (w, w + 4) own 9 causal chunks between them.
-__global__ __launch_bounds__(512) void attention_t256_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                             int T, int H, int window, float scale,
-                                                             void* __restrict__ outp, long long pstride, int outns,
-                                                             float oscale, unsigned* __restrict__ oamax) {
+// RG: as attention_body; items of more than 256 rows belong to the banded kernel and exit before any load
+template <bool RG>
+__device__ __forceinline__ void attention_t256_body(const float* __restrict__ qkv, float* __restrict__ out, int Ts, int H,
+                                                    int window, float scale, void* __restrict__ outp, long long pstride,
+                                                    int outns, float oscale, unsigned* __restrict__ oamax,
+                                                    const int* __restrict__ tlen, const int* __restrict__ toff) {
     constexpr int D = 64, LDKS = D + 4, LDO = D + 1, TM = 256;
     __shared__ __attribute__((aligned(16))) float lds[TM * LDKS + TM * D];
     float* Ks = lds;
     float* Vs = lds + TM * LDKS;
     const int h = blockIdx.x, b = blockIdx.y;
+    const int T = RG ? tlen[b] : Ts;
+    if (RG && T > 256) return;
+    const long long row0 = RG ? (long long)toff[b] : (long long)b * T;  // the item's first row
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hf = lane >> 5, col = lane & 31;
     const long long ld = 3LL * H * D;
-    const float* base = qkv + (long long)b * T * ld;
+    const float* base = qkv + row0 * ld;
     // K / V rows 0 .. 255 (zeros past T): 2 x 16 float4 per thread, all in flight before the first store
     {
         constexpr int PER = TM * (D / 4) / 512;  // 8
@@ -419,10 +443,23 @@ __global__ __launch_bounds__(512) void attention_t256_kernel(const float* __rest
     for (int qq = 0; qq < 32; ++qq) {
         const int q = qw + qq;
         if (q < T)
-            store_act(out, outp, pstride, outns, ((long long)b * T + q) * (H * D) + h * D + lane, ow[qq * LDO + lane],
+            store_act(out, outp, pstride, outns, (row0 + q) * (H * D) + h * D + lane, ow[qq * LDO + lane],
                       oscale, &mx);
     }
     amax_commit(oamax, mx);
+}
+
+__global__ __launch_bounds__(512) void attention_t256_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+                                                             int T, int H, int window, float scale,
+                                                             void* __restrict__ outp, long long pstride, int outns,
+                                                             float oscale, unsigned* __restrict__ oamax) {
+    attention_t256_body<false>(qkv, out, T, H, window, scale, outp, pstride, outns, oscale, oamax, nullptr, nullptr);
+}
+__global__ __launch_bounds__(512) void attention_t256_ragged_kernel(const float* __restrict__ qkv,
+                                                                    float* __restrict__ out, int H, int window,
+                                                                    float scale, const int* __restrict__ tlen,
+                                                                    const int* __restrict__ toff) {
+    attention_t256_body<true>(qkv, out, 0, H, window, scale, nullptr, 0, 0, 0.0f, nullptr, tlen, toff);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1095,6 +1132,22 @@ hipError_t launch_attention(const float* qkv, float* out, int batch, int T, int 
                             unsigned* oamax, bool h16, const int* tlen, int max_tlen, int min_tlen,
                             const int* toff, const char** kname, int band_split_mode) {
     if (D != 64 || (outns != 0 && !outp) || (outns == 0 && !out) || (oscale > 0.0f && outns != 2)) return hipErrorInvalidValue;
+    if (tlen && !h16) {  // fp32 ragged batch (the decode pass): packed rows, fp32 output; *kname = the last kernel run
+        if (!toff || outns != 0 || max_tlen < min_tlen || min_tlen < 1 || batch > 65535) return hipErrorInvalidValue;
+        if (min_tlen <= 256) {
+            hipLaunchKernelGGL(attention_t256_ragged_kernel, dim3(H, batch), dim3(512), 0, s, qkv, out, H, window, scale,
+                               tlen, toff);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            if (kname) *kname = "mimi::attention_t256_ragged_kernel";
+        }
+        if (max_tlen > 256) {
+            hipLaunchKernelGGL(attention_ragged_kernel, dim3((max_tlen + 127) / 128, H, batch), dim3(256), 0, s, qkv, out,
+                               H, window, scale, tlen, toff);
+            if (kname) *kname = "mimi::attention_ragged_kernel";
+        }
+        return hipGetLastError();
+    }
     if (tlen) {  // ragged batch: each item the kernel it would run alone (each exits on the other's items)
         if (!h16 || !(oscale > 0.0f && outns == 2) || max_tlen > T || min_tlen < 1) return hipErrorInvalidValue;
         if (min_tlen <= 256) {

@@ -82,8 +82,11 @@ __device__ __forceinline__ void store_y_block(const ResArgs& p, float* stg, cons
     }
 }
 
-template <int C, int BM, bool WINDOW, bool FIRST, int W1M, int W1N, int W2M, int W2N, int NP>
-__global__ __launch_bounds__(256) void resblock_kernel(ResArgs p) {
+// RG (the ragged decode pass, never with the conv0 fusion): item b has p.ilen[b] rows starting at row p.ioff[b] of the
+// packed x / y; the BM tiling starts at the item's first row, as alone, and a tile past its rows exits before any load
+template <int C, int BM, bool WINDOW, bool FIRST, int W1M, int W1N, int W2M, int W2N, int NP, bool RG>
+__device__ __forceinline__ void resblock_body(const ResArgs& p) {
+    static_assert(!(RG && FIRST), "ragged blocks read x");
     constexpr int H = C / 2;
     constexpr int K1 = 3 * C;
     constexpr int LDK = 36;
@@ -112,10 +115,12 @@ __global__ __launch_bounds__(256) void resblock_kernel(ResArgs p) {
     float* Aud = Bs + BST;  // FIRST: audio[m0-8 .. m0+BM), then w0[64][7] (stride 8), b0[64]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long T = p.T;
     const long long m0 = (long long)blockIdx.x * BM;
     const int b = blockIdx.y;
-    const float* __restrict__ xb = p.x + (long long)b * T * C;
+    const long long T = RG ? (long long)p.ilen[b] : p.T;
+    if (RG && m0 >= T) return;
+    const long long xoff = RG ? (long long)p.ioff[b] * C : (long long)b * T * C;  // the item's first element of x / y
+    const float* __restrict__ xb = p.x + xoff;
 
     // ---------------- GEMM1: h = ELU(x) (*) W3 ----------------
     if (FIRST) {
@@ -282,7 +287,7 @@ __global__ __launch_bounds__(256) void resblock_kernel(ResArgs p) {
     }
 
     // ---------------- GEMM2: y = ELU(x + b1 + h . W1^T), NP columns per pass ----------------
-    const long long ybase = (long long)b * T * C;
+    const long long ybase = xoff;
     float ymx = 0.0f;  // max|y| (fp16 planes: the engine's range check)
     for (int n0 = 0; n0 < C; n0 += NP) {
         auto load2 = [&](int k0) {
@@ -355,6 +360,15 @@ __global__ __launch_bounds__(256) void resblock_kernel(ResArgs p) {
         if (n0 + NP < C) prefetch_res(n0 + NP);
     }
     amax_commit(p.yamax, ymx);
+}
+
+template <int C, int BM, bool WINDOW, bool FIRST, int W1M, int W1N, int W2M, int W2N, int NP>
+__global__ __launch_bounds__(256) void resblock_kernel(ResArgs p) {
+    resblock_body<C, BM, WINDOW, FIRST, W1M, W1N, W2M, W2N, NP, false>(p);
+}
+template <int C, int BM, bool WINDOW, int W1M, int W1N, int W2M, int W2N, int NP>
+__global__ __launch_bounds__(256) void resblock_ragged_kernel(ResArgs p) {
+    resblock_body<C, BM, WINDOW, false, W1M, W1N, W2M, W2N, NP, true>(p);
 }
 
 
@@ -1017,8 +1031,31 @@ static hipError_t run_res(const ResArgs& a, hipStream_t s, const char** kname) {
     return hipGetLastError();
 }
 
+// packed ragged items (a.ioff, a.ilen; a.T = the longest item's rows sizes the grid): the fp32 block of the same tile
+template <int C, int BM, bool WINDOW, int W1M, int W1N, int W2M, int W2N, int NP>
+static hipError_t run_res_ragged(const ResArgs& a, hipStream_t s, const char** kname) {
+    static thread_local char name[160];
+    if (!name[0])
+        snprintf(name, sizeof(name), "mimi::resblock_ragged_kernel<%d, %d, %s, %d, %d, %d, %d, %d>", C, BM,
+                 WINDOW ? "true" : "false", W1M, W1N, W2M, W2N, NP);
+    if (kname) *kname = name;
+    dim3 grid((unsigned)((a.T + BM - 1) / BM), a.batch);
+    hipLaunchKernelGGL((resblock_ragged_kernel<C, BM, WINDOW, W1M, W1N, W2M, W2N, NP>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_resblock(int C, const ResArgs& a, hipStream_t s, const char** kname) {
     if (a.T <= 0 || a.batch <= 0) return hipErrorInvalidValue;
+    if (a.ioff) {
+        if (!a.ilen || a.audio || a.wh16 || a.yns != 0 || !a.x || !a.y || a.batch > 65535) return hipErrorInvalidValue;
+        switch (C) {
+            case 64: return run_res_ragged<64, 128, true, 4, 1, 4, 1, 64>(a, s, kname);
+            case 128: return run_res_ragged<128, 64, true, 2, 2, 2, 2, 128>(a, s, kname);
+            case 256: return run_res_ragged<256, 64, false, 2, 2, 2, 2, 128>(a, s, kname);
+            case 512: return run_res_ragged<512, 32, false, 1, 4, 1, 4, 256>(a, s, kname);
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (C) {
         case 64:
             if (a.audio && a.wh16) {

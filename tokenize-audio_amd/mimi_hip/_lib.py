@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "mimi_split_check", "mimi_gelu_check",
     "mimi_enable_decode", "mimi_create_from_dir_flags", "mimi_decoded_length", "mimi_decoded_length_cfg", "mimi_decode",
     "mimi_rvq_decode", "mimi_decode_workspace_bytes", "mimi_upconv_relayout",
+    "mimi_decode_ragged", "mimi_decode_ragged_workspace_bytes",
 )
 CREATE_DECODE = 1  # MIMI_CREATE_DECODE
 RESAMPLE_MAX_TAPS = 65536  # MIMI_RESAMPLE_MAX_TAPS
@@ -136,6 +137,8 @@ def _declare(lib):
         "mimi_rvq_decode": (c.c_int, [vp, vp, c.c_int64, c.c_int32, vp, vp]),
         "mimi_decode_workspace_bytes": (c.c_int64, [vp, c.c_int32, c.c_int64]),
         "mimi_upconv_relayout": (c.c_int, [vp, c.c_int32, c.c_int32, c.c_int32, vp]),
+        "mimi_decode_ragged": (c.c_int, [vp, vp, vp, c.c_int32, c.c_int64, c.c_int32, vp, vp]),
+        "mimi_decode_ragged_workspace_bytes": (c.c_int64, [vp, vp, c.c_int32]),
         "mimi_resample_poly": (c.c_int, [vp, vp, vp, c.c_int32, vp, vp, vp, c.c_int64, vp, c.c_int32, c.c_int32,
                                          c.c_int32, c.c_int64, vp]),
     }

@@ -408,6 +408,47 @@ class MimiHipModel:
             return (audio, None)
         return MimiDecoderOutput(audio)
 
+    def decode_ragged_workspace_bytes(self, lengths) -> int:
+        """Bytes of a ragged decode's workspace at the current taps setting (``mimi_decode_ragged_workspace_bytes``)."""
+        lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+        return int(self._lib.mimi_decode_ragged_workspace_bytes(self._h, ctypes.c_void_p(lens.ctypes.data), lens.size))
+
+    def decode_ragged(self, audio_codes: torch.Tensor, lengths, out: Optional[torch.Tensor] = None):
+        """Mixed-length batch in one pass (``mimi_decode_ragged``): item b = ``audio_codes[b, :, :lengths[b]]`` of an
+        int64 / int32 ``[B, K, Tmax]`` tensor on any device (the codes past an item's length are never read).
+        Returns a list of B float32 device tensors ``[1, 1920 lengths[b]]``, views of one ``[B, 1920 Tmax]`` buffer
+        (``out`` if given: the samples past an item's length are left as they were).  Item b is bit for bit
+        ``decode(audio_codes[b:b + 1, :, :lengths[b]]).audio_values[0]``."""
+        self._require_decode()
+        if not torch.is_tensor(audio_codes):
+            audio_codes = torch.as_tensor(np.asarray(audio_codes))
+        if audio_codes.dim() != 3:
+            raise ValueError(f"audio_codes must be [batch, num_quantizers, frames], got {tuple(audio_codes.shape)}")
+        B, K, T = audio_codes.shape
+        if K > self.config.num_quantizers or K < 1:
+            raise ValueError(f"The number of quantizers (i.e codebooks) must be in [1, {self.config.num_quantizers}], "
+                             f"but is currently {K}.")
+        lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+        if lens.shape != (B,) or (B and (int(lens.min()) < 1 or int(lens.max()) > T)):
+            raise ValueError(f"lengths must be {B} values in [1, {T}]")
+        L = self.get_decoded_length(T)
+        if out is None:
+            out = torch.empty((B, L), dtype=torch.float32, device=self.device)
+        elif (tuple(out.shape) != (B, L) or out.dtype != torch.float32 or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 [{B}, {L}] tensor on {self.device}")
+        if B:
+            codes = audio_codes.to(device=self.device, dtype=torch.int32).contiguous()
+            try:
+                _lib.check(self._lib.mimi_decode_ragged(self._h, ctypes.c_void_p(codes.data_ptr()),
+                                                        ctypes.c_void_p(lens.ctypes.data), B, T, K,
+                                                        ctypes.c_void_p(out.data_ptr()), self._stream()))
+            except _lib.MimiHipError as err:
+                if err.status == 1:  # MIMI_ERR_INVALID_ARGUMENT: a code outside [0, codebook_size) inside an item
+                    raise ValueError(str(err)) from None
+                raise
+        return [out[b:b + 1, : self.get_decoded_length(int(lens[b]))] for b in range(B)]
+
     def dequantize(self, codes: torch.Tensor) -> torch.Tensor:
         """Quantizer decode alone (``mimi_rvq_decode``): codes [B, K, T] -> float32 embedding [B, 512, T], the mirror
         of ``quantize``."""

@@ -12,6 +12,9 @@ Reports, as audio-seconds per second (one frame = 0.08 s of audio):
   since decode is its mirror;
 * the per-stage table of one profiled decode (``mimi_profile_read``).
 
+``--ragged`` measures the mixed-length path instead (``ragged_bench``): one fixed mix of 32 lengths decoded as one
+ragged batch, as a padded uniform batch and item by item.
+
 Seeded synthetic weights (``synthetic:0``) and codes from the engine's own encode of speech-like clips.
 """
 import argparse
@@ -44,8 +47,83 @@ def event_timed(fn, steps, warmup):
     return a.elapsed_time(b) / steps  # ms per call
 
 
+def ragged_bench(m, a):
+    """--ragged: one fixed mixed-length batch (B = 32, K = 8, T_b from default_rng(0).integers(25, 251): 2-20 s) decoded
+    three ways in the same run, HIP-event timed after warm-up: (a) one ragged decode; (b) the uniform decode of the
+    codes padded to Tmax, then trimmed; (c) the per-item B = 1 loop.  (b) and (c) are the yardsticks."""
+    B, K = 32, 8
+    lens = [int(t) for t in np.random.default_rng(0).integers(25, 251, B)]
+    S, Tmax = sum(lens), max(lens)
+    rng = np.random.default_rng(1)
+    codes = torch.zeros((B, K, Tmax), dtype=torch.int32)
+    for b, T in enumerate(lens):
+        codes[b, :, :T] = torch.from_numpy(rng.integers(0, 2048, (K, T)).astype(np.int32))
+    codes = codes.cuda()
+    items = [codes[b:b + 1, :, :T].contiguous() for b, T in enumerate(lens)]
+    out = {"mode": "ragged", "batch": B, "k": K, "lengths": lens, "sum_frames": S, "max_frames": Tmax,
+           "fill_ratio": S / (B * Tmax), "audio_s": S * FRAME_S, "steps": a.steps, "warmup": a.warmup,
+           "device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d"),
+           "note": "single run on a shared box"}
+    buf = torch.empty((B, m.get_decoded_length(Tmax)), dtype=torch.float32, device="cuda:0")
+
+    def padded():
+        y = m.decode(codes).audio_values
+        return [y[b, :, : 1920 * T] for b, T in enumerate(lens)]
+
+    def loop():
+        return [m.decode(c).audio_values[0] for c in items]
+
+    ya = [y.clone() for y in m.decode_ragged(codes, lens, out=buf)]
+    yc = loop()
+    out["ragged_bitwise_equals_b1_loop"] = all(torch.equal(p, q) for p, q in zip(ya, yc))
+    yb = padded()
+    out["padded_max_rel_diff_vs_b1_loop"] = max(float((p - q).abs().max() / q.abs().max()) for p, q in zip(yb, yc))
+    del ya, yb, yc
+    for key, fn in (("ragged", lambda: m.decode_ragged(codes, lens, out=buf)), ("padded_uniform", padded),
+                    ("b1_loop", loop)):
+        ms = event_timed(fn, a.steps, a.warmup)
+        out[key] = {"ms_per_step": ms, "audio_s_per_s": S * FRAME_S / (ms * 1e-3)}
+    out["ragged_over_padded_time"] = out["ragged"]["ms_per_step"] / out["padded_uniform"]["ms_per_step"]
+    out["workspace_bytes"] = {"ragged": m.decode_ragged_workspace_bytes(lens), "padded_uniform": m.decode_workspace_bytes(B, Tmax)}
+    stages = {}
+    for key, fn in (("ragged", lambda: m.decode_ragged(codes, lens, out=buf)), ("padded_uniform", lambda: m.decode(codes))):
+        m.set_profiling(1)
+        m.profile_reset()
+        fn()
+        prof = m.profile_read()
+        m.set_profiling(0)
+        stages[key] = {k: {"ms": v["ms"], "launches": v["launches"], "kernel": v["kernel"]} for k, v in prof.items()
+                       if k.startswith("dec_")}
+    out["stages"] = stages
+    print(f"ragged decode mix: B = {B}, K = {K}, sum T = {S}, Tmax = {Tmax}, fill sum T / (B Tmax) = {out['fill_ratio']:.3f}, "
+          f"{out['audio_s']:.1f} s of audio   [{out['date']}, {out['device']}; single run on a shared box]")
+    for key, label in (("ragged", "(a) ragged decode"), ("padded_uniform", "(b) padded uniform + trim"),
+                       ("b1_loop", "(c) B = 1 loop")):
+        print(f"  {label:28s} {out[key]['ms_per_step']:9.3f} ms/step  {out[key]['audio_s_per_s']:10.0f} audio-s/s")
+    print(f"  (a) / (b) time {out['ragged_over_padded_time']:.3f} (fill ratio {out['fill_ratio']:.3f});  ragged == B = 1 loop "
+          f"bitwise: {out['ragged_bitwise_equals_b1_loop']};  workspace {out['workspace_bytes']['ragged'] / 2 ** 30:.2f} vs "
+          f"{out['workspace_bytes']['padded_uniform'] / 2 ** 30:.2f} GiB")
+    for key in ("ragged", "padded_uniform"):
+        print(f"  per-stage, {key}:")
+        agg = {}
+        for k, v in stages[key].items():
+            s = k.split("#")[0]
+            agg[s] = agg.get(s, 0.0) + v["ms"]
+        for s, msv in sorted(agg.items(), key=lambda kv: -kv[1]):
+            print(f"    {s:18s} {msv:8.3f} ms")
+    line = json.dumps(out)
+    print(line)
+    if a.json_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json_out)), exist_ok=True)
+        with open(a.json_out, "w") as f:
+            f.write(line + "\n")
+    if not out["ragged"]["ms_per_step"] < out["b1_loop"]["ms_per_step"]:
+        print("WARNING: the ragged decode is not faster than the B = 1 loop")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ragged", action="store_true", help="the mixed-length mix: ragged vs padded uniform vs B = 1 loop")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--frames", type=int, default=125)
     ap.add_argument("--k", type=int, default=8)
@@ -64,6 +142,10 @@ def main():
     sd = synthetic.make_state_dict(seed=0)
     sd.update(synthetic.make_decoder_state_dict(seed=0))
     m = MimiHipModel(sd, device="cuda:0", decode=True)
+    if a.ragged:
+        ragged_bench(m, a)
+        m.close()
+        return
     L = 1920 * T
     audio = torch.from_numpy(synthetic.clip_batch(B, L, seed=3)).cuda()
     codes = m.encode_int32(audio, K)            # device int32 [B, K, T]
