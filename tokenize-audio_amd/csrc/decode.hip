@@ -8,6 +8,13 @@
 // All three are memory-bound streams: 16-byte loads and stores, consecutive lanes on consecutive addresses.  The
 // transposed convs of the SEANet decoder run as GEMMs (gemm.hip ROLE_UPCONV), its residual blocks as the fused
 // blocks of resblock.hip, the transformer as the encoder's launches on the decoder_transformer weights (engine.cpp).
+//
+// Each stage is one `template <bool RG>` body under two thin kernels.  RG = false: a uniform batch, [B][rows][C]
+// tensors.  RG = true (mimi_decode_ragged): item b = blockIdx.y has tlen[b] rows of this stage starting at row toff[b]
+// of the packed tensor (the stage's own table: lengths and offsets already times its rate factor).  The grid covers
+// the longest item; a workgroup (or wave) whose rows start at or past its item's length exits before any load, so
+// nothing past an item's length is read, computed or stored.  Only where a row and its item come from differs: per
+// row the arithmetic is one text, so an item's values are the bits of its own uniform launch.
 #include "kernels.h"
 
 namespace mimi {
@@ -21,18 +28,30 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // One wave per (frame, half): lane l holds columns 4l .. 4l+3 (D = 256).  K <= nsem leaves the acoustic half zero.
 // BOUNDS BEFORE LOAD: a code outside [0, ncodes) never forms an address -- the wave raises *flag and gathers row 0
 // (the host then fails the call: the output is unspecified but every access was in bounds).
+// RG: T = the codes' padded row stride (columns >= tlen[b] are never read), out [sum tlen][2*D]; frames unused.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rvq_decode_kernel(const int32_t* __restrict__ codes, long long frames, int T,
-                                                         int K, int nsem, int ncodes, const float* __restrict__ cb_rows,
-                                                         float* __restrict__ out, unsigned* __restrict__ flag) {
+template <bool RG>
+__device__ __forceinline__ void rvq_decode_body(const int32_t* __restrict__ codes, long long frames, int T, int K,
+                                                int nsem, int ncodes, const float* __restrict__ cb_rows,
+                                                float* __restrict__ out, unsigned* __restrict__ flag,
+                                                const int* __restrict__ tlen, const int* __restrict__ toff) {
     constexpr int D = 256;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const long long frame = (long long)blockIdx.x * 2 + (wave >> 1);
-    if (frame >= frames) return;
+    long long b, frame;
+    int t;
+    if constexpr (RG) {
+        b = blockIdx.y;
+        t = (int)blockIdx.x * 2 + (wave >> 1);
+        if (t >= tlen[b]) return;
+        frame = (long long)toff[b] + t;
+    } else {
+        frame = (long long)blockIdx.x * 2 + (wave >> 1);
+        if (frame >= frames) return;
+        b = frame / T;
+        t = (int)(frame - b * T);
+    }
     const int half = wave & 1;
-    const long long b = frame / T;
-    const int t = (int)(frame - b * T);
     const int lv0 = half ? nsem : 0;
     const int lv1 = half ? K : (K < nsem ? K : nsem);
     f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -51,15 +70,37 @@ __global__ __launch_bounds__(256) void rvq_decode_kernel(const int32_t* __restri
     *reinterpret_cast<f32x4*>(out + frame * (2 * D) + half * D + 4 * lane) = acc;
 }
 
-hipError_t launch_rvq_decode(const int32_t* codes, long long frames, int frames_per_item, int K, int nsem, int ncodes,
-                             int D, const float* cb_rows, float* out, unsigned* flag, hipStream_t s) {
-    if (D != 256 || frames <= 0 || frames_per_item <= 0 || K < 1 || nsem < 1 || ncodes < 1 || !codes || !cb_rows ||
-        !out || !flag || frames % frames_per_item != 0)
+__global__ __launch_bounds__(256) void rvq_decode_kernel(const int32_t* __restrict__ codes, long long frames, int T,
+                                                         int K, int nsem, int ncodes, const float* __restrict__ cb_rows,
+                                                         float* __restrict__ out, unsigned* __restrict__ flag) {
+    rvq_decode_body<false>(codes, frames, T, K, nsem, ncodes, cb_rows, out, flag, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void rvq_decode_ragged_kernel(const int32_t* __restrict__ codes, int Ts, int K, int nsem,
+                                                                int ncodes, const float* __restrict__ cb_rows,
+                                                                float* __restrict__ out, unsigned* __restrict__ flag,
+                                                                const int* __restrict__ tlen,
+                                                                const int* __restrict__ toff) {
+    rvq_decode_body<true>(codes, 0, Ts, K, nsem, ncodes, cb_rows, out, flag, tlen, toff);
+}
+
+hipError_t launch_rvq_decode(const int32_t* codes, long long frames, int T, int K, int nsem, int ncodes, int D,
+                             const float* cb_rows, float* out, unsigned* flag, hipStream_t s, const int* tlen,
+                             const int* toff, int max_tlen) {
+    if (D != 256 || frames <= 0 || T <= 0 || K < 1 || nsem < 1 || ncodes < 1 || !codes || !cb_rows || !out || !flag ||
+        frames % T != 0 || !tlen != !toff)
         return hipErrorInvalidValue;
-    const long long blocks = (frames + 1) / 2;
-    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rvq_decode_kernel, dim3((unsigned)blocks), dim3(256), 0, s, codes, frames, frames_per_item, K,
-                       nsem, ncodes, cb_rows, out, flag);
+    if (tlen) {
+        const long long batch = frames / T;
+        if (batch > 65535 || max_tlen <= 0 || max_tlen > T) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(rvq_decode_ragged_kernel, dim3((unsigned)((max_tlen + 1) / 2), (unsigned)batch), dim3(256), 0,
+                           s, codes, T, K, nsem, ncodes, cb_rows, out, flag, tlen, toff);
+    } else {
+        const long long blocks = (frames + 1) / 2;
+        if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(rvq_decode_kernel, dim3((unsigned)blocks), dim3(256), 0, s, codes, frames, T, K, nsem, ncodes,
+                           cb_rows, out, flag);
+    }
     return hipGetLastError();
 }
 
@@ -67,14 +108,28 @@ hipError_t launch_rvq_decode(const int32_t* codes, long long frames, int frames_
 // x [B][T][C] -> y [B][2T][C], depthwise (groups = C), k = 4, stride 2, no bias, causal (the 2 trailing outputs of
 // conv_transpose1d trimmed): y[2t + p][c] = w[c][p] x[t][c] + w[c][p + 2] x[t - 1][c], x[-1] = 0.
 // One thread per (b, t, 4 channels): two 16-B loads of x, four of w (w[c][0..3] is one float4), two 16-B stores.
+// RG: x [sum tlen][C] -> y [2 sum tlen][C]; x[t - 1] = 0 at each item's first frame (t is the position in the item);
+// rows and T unused.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void upsample_dw_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                          float* __restrict__ y, long long rows, int T, int C4) {
+template <bool RG>
+__device__ __forceinline__ void upsample_dw_body(const float* __restrict__ x, const float* __restrict__ w,
+                                                 float* __restrict__ y, long long rows, int T, int C4,
+                                                 const int* __restrict__ tlen, const int* __restrict__ toff) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * C4) return;
-    const long long row = i / C4;  // b * T + t
-    const int c4 = (int)(i - row * C4);
-    const int t = (int)(row % T);
+    long long row;
+    int c4, t;
+    if constexpr (RG) {
+        const int b = blockIdx.y;
+        t = (int)(i / C4);
+        if (t >= tlen[b]) return;
+        c4 = (int)(i - (long long)t * C4);
+        row = (long long)toff[b] + t;
+    } else {
+        if (i >= rows * C4) return;
+        row = i / C4;  // b * T + t
+        c4 = (int)(i - row * C4);
+        t = (int)(row % T);
+    }
     const int C = C4 * 4;
     const f32x4 x1 = *reinterpret_cast<const f32x4*>(x + row * C + 4 * c4);
     f32x4 x0 = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -86,18 +141,37 @@ __global__ __launch_bounds__(256) void upsample_dw_kernel(const float* __restric
         o0[e] = wc[0] * x1[e] + wc[2] * x0[e];
         o1[e] = wc[1] * x1[e] + wc[3] * x0[e];
     }
-    float* yo = y + (2 * row) * C + 4 * c4;  // item b's rows start at 2 b T: 2 (b T + t) = 2 b T + 2 t
+    float* yo = y + (2 * row) * C + 4 * c4;  // item b's rows start at twice its input's: 2 (b T + t) = 2 b T + 2 t
     *reinterpret_cast<f32x4*>(yo) = o0;
     *reinterpret_cast<f32x4*>(yo + C) = o1;
 }
 
-hipError_t launch_upsample_dw(const float* x, const float* w, float* y, int batch, long long T, int C, hipStream_t s) {
-    if (batch <= 0 || T <= 0 || T > 0x7fffffffLL || C <= 0 || C % 4 || !x || !w || !y) return hipErrorInvalidValue;
-    const long long n = (long long)batch * T * (C / 4);
+__global__ __launch_bounds__(256) void upsample_dw_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                          float* __restrict__ y, long long rows, int T, int C4) {
+    upsample_dw_body<false>(x, w, y, rows, T, C4, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void upsample_dw_ragged_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                 float* __restrict__ y, int C4,
+                                                                 const int* __restrict__ tlen,
+                                                                 const int* __restrict__ toff) {
+    upsample_dw_body<true>(x, w, y, 0, 0, C4, tlen, toff);
+}
+
+hipError_t launch_upsample_dw(const float* x, const float* w, float* y, int batch, long long T, int C, hipStream_t s,
+                              const int* tlen, const int* toff) {
+    if (batch <= 0 || T <= 0 || T > 0x7fffffffLL || C <= 0 || C % 4 || !x || !w || !y || !tlen != !toff ||
+        (tlen && batch > 65535))
+        return hipErrorInvalidValue;
+    const long long n = (tlen ? 1 : (long long)batch) * T * (C / 4);  // threads along x: ragged items go along y
     const long long blocks = (n + 255) / 256;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(upsample_dw_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, w, y, (long long)batch * T,
-                       (int)T, C / 4);
+    if (tlen)
+        hipLaunchKernelGGL(upsample_dw_ragged_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(256), 0, s, x, w, y,
+                           C / 4, tlen, toff);
+    else
+        hipLaunchKernelGGL(upsample_dw_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, w, y, (long long)batch * T,
+                           (int)T, C / 4);
     return hipGetLastError();
 }
 
@@ -108,151 +182,28 @@ hipError_t launch_upsample_dw(const float* x, const float* w, float* y, int batc
 // contiguous tile of FC_TILE samples: its FC_TILE + 2 rows go to LDS with 16-B loads, consecutive lanes on
 // consecutive 16 B (a wave reads 1 KiB = 4 whole rows per load); then thread i reads its three rows from LDS (row
 // stride 68 floats: conflict-free ds_read_b128) against the weights (LDS broadcasts) in four running sums.
+// RG: x [sum llen][64] packed -> y [B][Ls] padded (Ls = y's row stride); samples >= llen[b] of row b are left untouched.
 // ------------------------------------------------------------------------------------------------
 constexpr int FC_TILE = 128, FC_C = 64, FC_LD = 68;
 
-__global__ __launch_bounds__(FC_TILE) void final_conv_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                             const float* __restrict__ bias, float* __restrict__ y,
-                                                             long long L) {
+template <bool RG>
+__device__ __forceinline__ void final_conv_body(const float* __restrict__ x, const float* __restrict__ w,
+                                                const float* __restrict__ bias, float* __restrict__ y, long long Ls,
+                                                const int* __restrict__ llen, const int* __restrict__ loff) {
     __shared__ __attribute__((aligned(16))) float xs[(FC_TILE + 2) * FC_LD];
     __shared__ __attribute__((aligned(16))) float ws[3 * FC_C];
     const int tid = threadIdx.x;
     const long long l0 = (long long)blockIdx.x * FC_TILE;
-    const float* __restrict__ xb = x + (long long)blockIdx.y * L * FC_C;
-    for (int i = tid; i < 3 * FC_C; i += FC_TILE) ws[i] = w[i];
-    for (int idx = tid; idx < (FC_TILE + 2) * (FC_C / 4); idx += FC_TILE) {
-        const int r = idx >> 4, c4 = idx & 15;
-        const long long g = l0 - 2 + r;
-        f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (g >= 0 && g < L) v = *reinterpret_cast<const f32x4*>(xb + g * FC_C + 4 * c4);
-        *reinterpret_cast<f32x4*>(xs + r * FC_LD + 4 * c4) = v;
+    long long L;
+    const float* __restrict__ xb;
+    if constexpr (RG) {
+        L = llen[blockIdx.y];
+        if (l0 >= L) return;
+        xb = x + (long long)loff[blockIdx.y] * FC_C;
+    } else {
+        L = Ls;  // every item fills its row
+        xb = x + (long long)blockIdx.y * L * FC_C;
     }
-    __syncthreads();
-    const long long l = l0 + tid;
-    if (l >= L) return;
-    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int c4 = 0; c4 < FC_C / 4; ++c4) {
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(xs + (tid + k) * FC_LD + 4 * c4);
-            const f32x4 wv = *reinterpret_cast<const f32x4*>(ws + k * FC_C + 4 * c4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[e] = __builtin_fmaf(xv[e], wv[e], acc[e]);
-        }
-    y[(long long)blockIdx.y * L + l] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + bias[0];
-}
-
-hipError_t launch_final_conv(const float* x, const float* w, const float* bias, float* y, int batch, long long L, int C,
-                             int ksize, hipStream_t s) {
-    if (C != FC_C || ksize != 3 || batch <= 0 || batch > 65535 || L <= 0 || !x || !w || !bias || !y)
-        return hipErrorInvalidValue;
-    const long long tiles = (L + FC_TILE - 1) / FC_TILE;
-    if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(final_conv_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(FC_TILE), 0, s, x, w, bias, y, L);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------
-// Ragged forms (mimi_decode_ragged): item b = blockIdx.y has tlen[b] rows of this stage starting at row toff[b] of the
-// packed tensor (the stage's own table: lengths and offsets already times its rate factor).  The grid covers the
-// longest item; a workgroup (or wave) whose rows start at or past its item's length exits before any load, so nothing
-// past an item's length is read, computed or stored.  Per row the arithmetic is the uniform kernel's, statement for
-// statement: an item's values are the bits of its own launch.
-// ------------------------------------------------------------------------------------------------
-// codes [B][K][Ts] (Ts = the padded row stride; columns >= tlen[b] are never read) -> out [sum tlen][2*D]
-__global__ __launch_bounds__(256) void rvq_decode_ragged_kernel(const int32_t* __restrict__ codes, int Ts, int K, int nsem,
-                                                                int ncodes, const float* __restrict__ cb_rows,
-                                                                float* __restrict__ out, unsigned* __restrict__ flag,
-                                                                const int* __restrict__ tlen,
-                                                                const int* __restrict__ toff) {
-    constexpr int D = 256;
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const long long b = blockIdx.y;
-    const int t = (int)blockIdx.x * 2 + (wave >> 1);
-    if (t >= tlen[b]) return;
-    const long long frame = (long long)toff[b] + t;
-    const int half = wave & 1;
-    const int lv0 = half ? nsem : 0;
-    const int lv1 = half ? K : (K < nsem ? K : nsem);
-    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    bool bad = false;
-    for (int lv = lv0; lv < lv1; ++lv) {
-        const int32_t code = codes[(b * K + lv) * (long long)Ts + t];
-        unsigned c = (unsigned)code;
-        if (c >= (unsigned)ncodes) {  // (negative codes wrap above ncodes)
-            bad = true;
-            c = 0u;
-        }
-        const f32x4 v = *reinterpret_cast<const f32x4*>(cb_rows + ((long long)lv * ncodes + c) * D + 4 * lane);
-        acc = acc + v;
-    }
-    if (bad && lane == 0) atomicOr(flag, 1u);
-    *reinterpret_cast<f32x4*>(out + frame * (2 * D) + half * D + 4 * lane) = acc;
-}
-
-hipError_t launch_rvq_decode_ragged(const int32_t* codes, int batch, int Ts, int max_tlen, int K, int nsem, int ncodes,
-                                    int D, const float* cb_rows, float* out, unsigned* flag, const int* tlen,
-                                    const int* toff, hipStream_t s) {
-    if (D != 256 || batch <= 0 || batch > 65535 || max_tlen <= 0 || max_tlen > Ts || K < 1 || nsem < 1 || ncodes < 1 ||
-        !codes || !cb_rows || !out || !flag || !tlen || !toff)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rvq_decode_ragged_kernel, dim3((unsigned)((max_tlen + 1) / 2), (unsigned)batch), dim3(256), 0, s,
-                       codes, Ts, K, nsem, ncodes, cb_rows, out, flag, tlen, toff);
-    return hipGetLastError();
-}
-
-// x [sum tlen][C] -> y [2 sum tlen][C]; x[t - 1] = 0 at each item's first frame (t is the position in the item)
-__global__ __launch_bounds__(256) void upsample_dw_ragged_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                 float* __restrict__ y, int C4,
-                                                                 const int* __restrict__ tlen,
-                                                                 const int* __restrict__ toff) {
-    const int b = blockIdx.y;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int t = (int)(i / C4);
-    if (t >= tlen[b]) return;
-    const int c4 = (int)(i - (long long)t * C4);
-    const long long row = (long long)toff[b] + t;
-    const int C = C4 * 4;
-    const f32x4 x1 = *reinterpret_cast<const f32x4*>(x + row * C + 4 * c4);
-    f32x4 x0 = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (t > 0) x0 = *reinterpret_cast<const f32x4*>(x + (row - 1) * C + 4 * c4);
-    f32x4 o0, o1;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const f32x4 wc = *reinterpret_cast<const f32x4*>(w + (long long)(4 * c4 + e) * 4);
-        o0[e] = wc[0] * x1[e] + wc[2] * x0[e];
-        o1[e] = wc[1] * x1[e] + wc[3] * x0[e];
-    }
-    float* yo = y + (2 * row) * C + 4 * c4;
-    *reinterpret_cast<f32x4*>(yo) = o0;
-    *reinterpret_cast<f32x4*>(yo + C) = o1;
-}
-
-hipError_t launch_upsample_dw_ragged(const float* x, const float* w, float* y, int batch, int max_tlen, int C,
-                                     const int* tlen, const int* toff, hipStream_t s) {
-    if (batch <= 0 || batch > 65535 || max_tlen <= 0 || C <= 0 || C % 4 || !x || !w || !y || !tlen || !toff)
-        return hipErrorInvalidValue;
-    const long long blocks = ((long long)max_tlen * (C / 4) + 255) / 256;
-    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(upsample_dw_ragged_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(256), 0, s, x, w, y,
-                       C / 4, tlen, toff);
-    return hipGetLastError();
-}
-
-// x [sum llen][64] packed -> y [B][Ls] padded (row stride Ls); samples >= llen[b] of row b are left untouched
-__global__ __launch_bounds__(FC_TILE) void final_conv_ragged_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                    const float* __restrict__ bias, float* __restrict__ y,
-                                                                    long long Ls, const int* __restrict__ llen,
-                                                                    const int* __restrict__ loff) {
-    __shared__ __attribute__((aligned(16))) float xs[(FC_TILE + 2) * FC_LD];
-    __shared__ __attribute__((aligned(16))) float ws[3 * FC_C];
-    const int tid = threadIdx.x;
-    const long long l0 = (long long)blockIdx.x * FC_TILE;
-    const long long L = llen[blockIdx.y];
-    if (l0 >= L) return;
-    const float* __restrict__ xb = x + (long long)loff[blockIdx.y] * FC_C;
     for (int i = tid; i < 3 * FC_C; i += FC_TILE) ws[i] = w[i];
     for (int idx = tid; idx < (FC_TILE + 2) * (FC_C / 4); idx += FC_TILE) {
         const int r = idx >> 4, c4 = idx & 15;
@@ -277,16 +228,31 @@ __global__ __launch_bounds__(FC_TILE) void final_conv_ragged_kernel(const float*
     y[(long long)blockIdx.y * Ls + l] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + bias[0];
 }
 
-hipError_t launch_final_conv_ragged(const float* x, const float* w, const float* bias, float* y, int batch, long long Ls,
-                                    long long max_llen, int C, int ksize, const int* llen, const int* loff,
-                                    hipStream_t s) {
-    if (C != FC_C || ksize != 3 || batch <= 0 || batch > 65535 || max_llen <= 0 || max_llen > Ls || !x || !w || !bias ||
-        !y || !llen || !loff)
+__global__ __launch_bounds__(FC_TILE) void final_conv_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, float* __restrict__ y,
+                                                             long long L) {
+    final_conv_body<false>(x, w, bias, y, L, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(FC_TILE) void final_conv_ragged_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                    const float* __restrict__ bias, float* __restrict__ y,
+                                                                    long long Ls, const int* __restrict__ llen,
+                                                                    const int* __restrict__ loff) {
+    final_conv_body<true>(x, w, bias, y, Ls, llen, loff);
+}
+
+hipError_t launch_final_conv(const float* x, const float* w, const float* bias, float* y, int batch, long long L, int C,
+                             int ksize, hipStream_t s, const int* llen, const int* loff, long long max_llen) {
+    if (C != FC_C || ksize != 3 || batch <= 0 || batch > 65535 || L <= 0 || !x || !w || !bias || !y || !llen != !loff ||
+        (llen && (max_llen <= 0 || max_llen > L)))
         return hipErrorInvalidValue;
-    const long long tiles = (max_llen + FC_TILE - 1) / FC_TILE;
+    const long long tiles = ((llen ? max_llen : L) + FC_TILE - 1) / FC_TILE;
     if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(final_conv_ragged_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(FC_TILE), 0, s, x, w, bias,
-                       y, Ls, llen, loff);
+    const dim3 grid((unsigned)tiles, (unsigned)batch);
+    if (llen)
+        hipLaunchKernelGGL(final_conv_ragged_kernel, grid, dim3(FC_TILE), 0, s, x, w, bias, y, L, llen, loff);
+    else
+        hipLaunchKernelGGL(final_conv_kernel, grid, dim3(FC_TILE), 0, s, x, w, bias, y, L);
     return hipGetLastError();
 }
 

@@ -411,7 +411,7 @@ struct mimi_engine {
     size_t dws_bytes = 0;
     unsigned* dec_flag = nullptr;       // device word: a code outside [0, codebook_size) was seen
     unsigned* dec_flag_host = nullptr;  // pinned
-    int* dec_rg_host = nullptr;         // pinned: the host image of a ragged decode's length tables (DecRagged)
+    int* dec_rg_host = nullptr;         // pinned: the host image of a ragged decode's length tables (DecLayout)
     size_t dec_rg_cap = 0;              // ints
 };
 
@@ -2707,7 +2707,7 @@ extern "C" int mimi_rvq_encode(mimi_engine* e, const float* emb, int64_t frames,
 // so the channels-last GEMM output [T][r Cout] IS the up-sampled tensor [T r][Cout]: no pixel-shuffle pass.
 // ARITHMETIC: decode always runs the fp32-MFMA GEMMs and the fp32 attention / residual-block kernels (PREC_F32),
 // whatever mimi_set_precision says: no activation scales, so no calibration, no overflow read-back, no fallback.
-// A mixed-length batch runs in one pass over packed rows: "ragged decode" below (mimi_decode_ragged).
+// A mixed-length batch (mimi_decode_ragged) runs the same pass (decode_pass) over packed rows: DecLayout below.
 // Not built here: f16x3 decode, hipGraph capture of decode, KV-cache / streaming decode.
 
 static int64_t decode_upsampling(const mimi_config& c) {
@@ -2897,17 +2897,67 @@ static int finalize_decode(mimi_engine* e) {
     return MIMI_OK;
 }
 
+// The layout of one decode pass.  Every stage's tensor is [rows][C]: stage 0 the 12.5 Hz frames, 1 the 25 Hz ones, 2 ..
+// behind each up conv; a stage's rows are f[st] per frame (1, 2, 2 r0, 2 r0 r1, ...: integers).
+//   uniform (mimi_decode): item b's rows of a stage are rows b f T .. of [B][f T][C]; no tables.
+//   ragged (mimi_decode_ragged): the rows are PACKED, item b's at row f toff[b] of one [f sumT][C] tensor (toff = the
+//     prefix sum of the frame lengths) -- the transformer-section layout of encode's RaggedTable carried through the
+//     whole pass.  One (tlen, toff) pair describes every stage; the device image holds it once per stage already
+//     multiplied, [stage][tlen | toff][B] ints, so that the kernels index an int table as the encode-side ragged
+//     kernels do.  Uploaded once per call from pinned memory.
+// A uniform batch is the ragged one whose items all have T frames: both have f sumT rows per stage.
+struct DecLayout {
+    int B = 0, nst = 0;
+    bool ragged = false;
+    int64_t sumT = 0, maxT = 0, minT = 0;  // frames: of all items, of the longest and of the shortest
+    int64_t stride = 0;                    // frames per item of the caller's padded codes and waveform
+    std::vector<int64_t> f;                // rate factor per stage
+    const int* dev = nullptr;              // ragged: the tables' device image
+    int64_t rows(int st) const { return f[st] * sumT; }  // of the whole tensor
+    int64_t len(int st) const { return f[st] * maxT; }   // of the longest item: what a launch covers
+    const int* tlen(int st) const { return ragged ? dev + (size_t)(2 * st) * B : nullptr; }
+    const int* toff(int st) const { return ragged ? dev + (size_t)(2 * st + 1) * B : nullptr; }
+    size_t ints() const { return ragged ? (size_t)2 * nst * B : 0; }
+};
+
+// lengths: the items' frames (ragged: codes rows of `stride` frames), or null for a uniform batch of `stride` frames each
+static int plan_decode(const mimi_engine* e, const int64_t* lengths, int32_t batch, int64_t stride, DecLayout* L) {
+    const mimi_config& c = e->cfg;
+    L->B = batch;
+    L->nst = 2 + c.num_ratios;
+    L->ragged = lengths != nullptr;
+    L->stride = stride;
+    L->f.assign(1, 1);
+    L->f.push_back(2);
+    for (int i = 0; i < c.num_ratios; ++i) L->f.push_back(L->f.back() * c.upsampling_ratios[i]);
+    L->sumT = lengths ? 0 : batch * stride;
+    L->maxT = lengths ? 0 : stride;
+    L->minT = lengths ? INT64_MAX : stride;
+    for (int b = 0; lengths && b < batch; ++b) {
+        if (lengths[b] < 1) return 1;
+        L->sumT += lengths[b];
+        L->maxT = std::max(L->maxT, lengths[b]);
+        L->minT = std::min(L->minT, lengths[b]);
+        if (L->sumT > 0x7fffffffLL) return 2;
+    }
+    return 0;
+}
+
+static size_t pad256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
 // decode's workspace: two ping-pong regions (P: RVQ sums + embedding, then the SEANet's ELU'd tensors; Q: the
-// transformer's buffers, then the raw up-conv outputs) and, with taps on, the raw decoder.layers.0 output
+// transformer's buffers, then the raw up-conv outputs), with taps on the raw decoder.layers.0 output, and a ragged
+// pass's tables.  Every size is per frame, so a ragged pass has the activations of the B = 1 decode of sumT frames.
 struct DecodeWs {
     float *p, *q, *tap;
+    int* tab;
     size_t bytes;
 };
-static DecodeWs decode_ws_layout(const mimi_engine* e, int B, int64_t T, bool taps) {
+static DecodeWs decode_ws_layout(const mimi_engine* e, const DecLayout& L, bool taps) {
     const mimi_config& c = e->cfg;
-    const size_t h = c.hidden_size, T2 = 2 * (size_t)T;
+    const size_t h = c.hidden_size, T = (size_t)L.sumT, T2 = 2 * T;
     size_t C = (size_t)c.num_filters << c.num_ratios, len = T2;
-    size_t pmax = std::max((size_t)T * (h + 2 * c.vq_hidden_dim), T2 * C);
+    size_t pmax = std::max(T * (h + 2 * c.vq_hidden_dim), T2 * C);
     size_t qmax = T2 * (3 * h + 3 * (size_t)c.num_attention_heads * c.head_dim + c.intermediate_size);
     for (int s = 0; s < c.num_ratios; ++s) {
         len *= c.upsampling_ratios[s];
@@ -2915,16 +2965,17 @@ static DecodeWs decode_ws_layout(const mimi_engine* e, int B, int64_t T, bool ta
         pmax = std::max(pmax, len * C);
         qmax = std::max(qmax, len * C);
     }
-    auto pad = [](size_t floats) { return (floats * sizeof(float) + 255) / 256 * 256; };
     DecodeWs w{};
     char* base = reinterpret_cast<char*>(e->dws);
     size_t off = 0;
     w.p = reinterpret_cast<float*>(base + off);
-    off += pad(pmax * B);
+    off += pad256(pmax * sizeof(float));
     w.q = reinterpret_cast<float*>(base + off);
-    off += pad(qmax * B);
+    off += pad256(qmax * sizeof(float));
     w.tap = reinterpret_cast<float*>(base + off);
-    if (taps) off += pad(T2 * ((size_t)c.num_filters << c.num_ratios) * B);
+    if (taps) off += pad256(T2 * ((size_t)c.num_filters << c.num_ratios) * sizeof(float));
+    w.tab = reinterpret_cast<int*>(base + off);
+    off += pad256(L.ints() * sizeof(int));
     w.bytes = off;
     return w;
 }
@@ -2950,18 +3001,22 @@ static int ensure_dws(mimi_engine* e, size_t bytes) {
 
 extern "C" int64_t mimi_decode_workspace_bytes(const mimi_engine* e, int32_t batch, int64_t frames) {
     if (!e || batch <= 0 || frames <= 0) return -1;
-    return (int64_t)decode_ws_layout(e, batch, frames, e->taps).bytes;
+    DecLayout L;
+    plan_decode(e, nullptr, batch, frames, &L);
+    return (int64_t)decode_ws_layout(e, L, e->taps).bytes;
 }
 
-// codes -> (semantic | acoustic) sums in `sums` -> embedding [frames][hidden] in `emb`
-static int run_dequantize(mimi_engine* e, const int32_t* codes, int64_t frames, int frames_per_item, int K, float* sums,
-                          float* emb, hipStream_t s, Recorder& rec) {
+// codes -> (semantic | acoustic) sums in `sums` -> embedding [frames][hidden] in `emb` (the rows of L's stage 0)
+static int run_dequantize(mimi_engine* e, const int32_t* codes, const DecLayout& L, int K, float* sums, float* emb,
+                          hipStream_t s, Recorder& rec) {
     const mimi_config& c = e->cfg;
     const int Dq = c.vq_hidden_dim;
-    LAUNCH_TRY(launch_rvq_decode(codes, frames, frames_per_item, K, c.num_semantic_quantizers, c.codebook_size,
-                                 c.codebook_dim, e->cb_rows, sums, e->dec_flag, s),
+    const int64_t frames = L.rows(0);
+    LAUNCH_TRY(launch_rvq_decode(codes, L.B * L.stride, (int)L.stride, K, c.num_semantic_quantizers, c.codebook_size,
+                                 c.codebook_dim, e->cb_rows, sums, e->dec_flag, s, L.tlen(0), L.toff(0), (int)L.maxT),
                "rvq_decode");
-    rec.mark("dec_rvq", (double)frames * K * Dq, (double)frames * (K * Dq + 2 * Dq) * 4, "mimi::rvq_decode_kernel");
+    rec.mark("dec_rvq", (double)frames * K * Dq, (double)frames * (K * Dq + 2 * Dq) * 4,
+             L.ragged ? "mimi::rvq_decode_ragged_kernel" : "mimi::rvq_decode_kernel");
     GemmArgs ap = linear_args(sums, frames, 2 * Dq, e->outproj, c.hidden_size, emb);
     const char* kname = "?";
     LAUNCH_TRY(launch_gemm(ROLE_INPROJ, ap, s, &kname, PREC_F32), "output_proj");
@@ -2997,41 +3052,26 @@ extern "C" int mimi_rvq_decode(mimi_engine* e, const int32_t* dev_codes, int64_t
         return set_err(MIMI_ERR_INVALID_ARGUMENT, "frames=%lld", (long long)frames);
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if ((rc = ensure_dws(e, ((size_t)frames * 2 * e->cfg.vq_hidden_dim * sizeof(float) + 255) / 256 * 256))) return rc;
+    if ((rc = ensure_dws(e, pad256((size_t)frames * 2 * e->cfg.vq_hidden_dim * sizeof(float))))) return rc;
     HIP_TRY(hipMemsetAsync(e->dec_flag, 0, sizeof(unsigned), s));
     Recorder rec{e, s};
     rec.begin();
-    if ((rc = run_dequantize(e, dev_codes, frames, (int)frames, K, reinterpret_cast<float*>(e->dws), dev_embedding, s, rec)))
-        return rc;
+    DecLayout L;
+    plan_decode(e, nullptr, 1, frames, &L);
+    if ((rc = run_dequantize(e, dev_codes, L, K, reinterpret_cast<float*>(e->dws), dev_embedding, s, rec))) return rc;
     return read_decode_flag(e, s);
 }
 
-// Ragged decode (mimi_decode_ragged): every stage's rows are PACKED, item b's rows of a stage at rate factor f starting
-// at row f * toff[b] of one [f * sumT][C] tensor (toff = the prefix sum of the frame lengths; f = 1 for the 12.5 Hz
-// frames, 2 for the 25 Hz ones, then 2 r0, 2 r0 r1, ... behind each up conv) -- the transformer-section layout of
-// encode's RaggedTable carried through the whole pass.  The factors are integers, so one (tlen, toff) pair describes
-// every stage; the device image holds it once per stage already multiplied, [stage][tlen | toff][B] ints, so that the
-// kernels index an int table as the encode-side ragged kernels do.  Uploaded once per call from pinned memory.
-struct DecRagged {
-    int B = 0, nst = 0;
-    int64_t sumT = 0, maxT = 0, minT = 0;
-    std::vector<int64_t> f;  // rate factor per stage
-    const int* dev = nullptr;
-    const int* tlen(int st) const { return dev + (size_t)(2 * st) * B; }
-    const int* toff(int st) const { return dev + (size_t)(2 * st + 1) * B; }
-    static size_t ints(int B, int nst) { return (size_t)2 * nst * B; }
-};
-
 // The decoder transformer: the encoder's fp32 launches (LayerNorm, q/k/v + RoPE, attention, o_proj, fc1, fc2) on the
-// weight set xf over B items of T rows, residual stream in t0 (in place).  rg (ragged decode): the items' rows are
-// packed (stage 1 of rg: 2 tlen[b] rows at 2 toff[b]), T = the longest item's rows; the flat-row stages run unchanged
-// on the packed rows, q/k/v and attention per item
-static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, int B, int64_t T, float* t0, float* t1,
-                               float* qkv, float* att, float* ff, hipStream_t s, Recorder& rec, const char* stage_prefix,
-                               const DecRagged* rg = nullptr) {
+// weight set xf over the rows of L's stage 1 (B items, T = the longest item's rows), residual stream in t0 (in
+// place).  The flat-row stages run on all rows whatever the layout; q/k/v and attention run per item, a ragged
+// batch's from the tables (2 tlen[b] rows at 2 toff[b])
+static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, const DecLayout& L, float* t0, float* t1,
+                               float* qkv, float* att, float* ff, hipStream_t s, Recorder& rec, const char* stage_prefix) {
     const mimi_config& c = e->cfg;
     const int Hd = c.hidden_size, H = c.num_attention_heads, Dh = c.head_dim;
-    const int64_t rows = rg ? 2 * rg->sumT : (int64_t)B * T;
+    const int B = L.B;
+    const int64_t T = L.len(1), rows = L.rows(1);
     const std::string sp = stage_prefix;
     const char* kname = "?";
     double att_flops = 0;
@@ -3054,27 +3094,26 @@ static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, i
         aq.rope_cos = e->rope_cos;
         aq.rope_sin = e->rope_sin;
         aq.rope_cols = 2 * H * Dh;
-        if (rg) {  // per item: rows, zero padding and RoPE position relative to the item's first row
-            aq.a_rows = aq.m_rows = rg->tlen(1);
-            aq.a_boff = aq.c_boff = rg->toff(1);
-        }
+        // ragged, per item: rows, zero padding and RoPE position relative to the item's first row
+        aq.a_rows = aq.m_rows = L.tlen(1);
+        aq.a_boff = aq.c_boff = L.toff(1);
         LAUNCH_TRY(launch_gemm(ROLE_QKV, aq, s, &kname, PREC_F32), "qkv");
         rec.mark(sp + "qkv", fl(aq), by(aq, false), kname);
         const char* akn = T <= 256 ? "mimi::attention_t256_kernel" : "mimi::attention_kernel";
-        if (rg) {
+        if (L.ragged) {
             // each item the kernel it would run alone: one launch per regime present (and one record each), each
             // kernel exiting on the other's items
-            const int lo = (int)(2 * rg->minT), hi = (int)(2 * rg->maxT);
+            const int lo = (int)(2 * L.minT), hi = (int)(2 * L.maxT);
             const float sc = 1.0f / std::sqrt((float)Dh);
             if (lo <= 256) {
                 LAUNCH_TRY(launch_attention(qkv, att, B, 0, H, Dh, c.sliding_window, sc, s, nullptr, 0, 0, 0.0f, nullptr,
-                                            false, rg->tlen(1), std::min(hi, 256), lo, rg->toff(1), &akn),
+                                            false, L.tlen(1), std::min(hi, 256), lo, L.toff(1), &akn),
                            "attention");
                 rec.mark(sp + "attention", att_flops, (double)rows * 4 * Hd * 4, akn);
             }
             if (hi > 256) {
                 LAUNCH_TRY(launch_attention(qkv, att, B, 0, H, Dh, c.sliding_window, sc, s, nullptr, 0, 0, 0.0f, nullptr,
-                                            false, rg->tlen(1), hi, std::max(lo, 257), rg->toff(1), &akn),
+                                            false, L.tlen(1), hi, std::max(lo, 257), L.toff(1), &akn),
                            "attention");
                 rec.mark(sp + "attention", att_flops, (double)rows * 4 * Hd * 4, akn);
             }
@@ -3106,14 +3145,112 @@ static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, i
     return MIMI_OK;
 }
 
+// The decode pass on the layout L (its tables, if any, already on the device; the workspace w sized for it): every
+// launch from the codes to the last conv, with its profile record and tap.  A stage either runs on all rows at once
+// (the flat-row GEMMs and LayerNorm) or per item, where a ragged batch takes an item's base and length from the
+// tables and otherwise runs the uniform batch's arithmetic: item b's samples are bitwise those of its own B = 1 pass.
+// The caller takes the "audio" tap and reads the bounds flag.
+static int decode_pass(mimi_engine* e, const int32_t* dev_codes, const DecLayout& L, const DecodeWs& w, int K,
+                       float* dev_audio, hipStream_t s) {
+    const mimi_config& c = e->cfg;
+    const int B = L.B, Hd = c.hidden_size, Dq = c.vq_hidden_dim;
+    int rc;
+    if ((rc = ensure_rope(e, L.len(1)))) return rc;
+    HIP_TRY(hipMemsetAsync(e->dec_flag, 0, sizeof(unsigned), s));
+    Recorder rec{e, s};
+    rec.begin();
+    const char* kname = "?";
+    // a conv over stage st's rows as a GEMM per item
+    auto conv = [&](const DevConv& cv, const float* in, float* out, int st) {
+        GemmArgs a = conv_args(cv, in, L.len(st), out, L.len(st), B);
+        a.a_rows = a.m_rows = L.tlen(st);
+        a.a_boff = a.c_boff = L.toff(st);
+        return a;
+    };
+    auto fl = [&](const GemmArgs& a, int st) { return 2.0 * (double)L.rows(st) * a.N * a.K; };
+    auto by = [&](const GemmArgs& a, int st) { return ((double)L.rows(st) * (a.a_rs + a.N) + (double)a.N * a.K) * 4; };
+    auto tap = [&](const char* name, const float* src, int st, int C) {  // a ragged pass's taps are packed
+        return L.ragged ? save_tap(e, name, src, 1, L.rows(st), C, s) : save_tap(e, name, src, B, L.len(st), C, s);
+    };
+
+    // ---- quantizer.decode + upsample ----
+    float* sums = w.p;
+    float* emb = w.p + (size_t)L.rows(0) * 2 * Dq;
+    if ((rc = run_dequantize(e, dev_codes, L, K, sums, emb, s, rec))) return rc;
+    if ((rc = tap("quantized", emb, 0, Hd))) return rc;
+    float* t0 = w.q;
+    float* t1 = t0 + (size_t)L.rows(1) * Hd;
+    float* qkv = t1 + (size_t)L.rows(1) * Hd;
+    float* att = qkv + (size_t)L.rows(1) * 3 * c.num_attention_heads * c.head_dim;
+    float* ff = att + (size_t)L.rows(1) * Hd;
+    LAUNCH_TRY(launch_upsample_dw(emb, e->upsample_w, t0, B, L.len(0), Hd, s, L.tlen(0), L.toff(0)), "upsample");
+    rec.mark("dec_upsample", 4.0 * L.rows(1) * Hd, 3.0 * L.rows(0) * Hd * 4,
+             L.ragged ? "mimi::upsample_dw_ragged_kernel" : "mimi::upsample_dw_kernel");
+    if ((rc = tap("upsample", t0, 1, Hd))) return rc;
+
+    // ---- decoder transformer ----
+    if ((rc = run_transformer_f32(e, e->dxf, L, t0, t1, qkv, att, ff, s, rec, "dec_"))) return rc;
+    char nm[64];
+    snprintf(nm, sizeof nm, "xfmr%d", c.num_hidden_layers - 1);
+    if ((rc = tap(nm, t0, 1, Hd))) return rc;
+
+    // ---- SEANet decoder ----
+    int C = c.num_filters << c.num_ratios;
+    if (e->taps) {  // the raw layer-0 output (the pass itself only needs its ELU)
+        GemmArgs at = conv(e->dec_first, t0, w.tap, 1);
+        LAUNCH_TRY(launch_gemm(ROLE_DOWN, at, s, &kname, PREC_F32), "decoder conv 0 (tap)");
+        rec.mark("dec_conv0_tap", fl(at, 1), by(at, 1), kname);
+        if ((rc = tap("dconv0", w.tap, 1, C))) return rc;
+    }
+    float* xe = w.p;  // ELU'd input of the next up conv
+    GemmArgs a0 = conv(e->dec_first, t0, xe, 1);
+    LAUNCH_TRY(launch_gemm(ROLE_DOWN_ELU, a0, s, &kname, PREC_F32), "decoder conv 0");
+    rec.mark("dec_conv0", fl(a0, 1), by(a0, 1), kname);
+    if ((rc = tap("dconv0_elu", xe, 1, C))) return rc;  // what the pass itself computes and up conv 0 reads
+    for (int si = 0; si < c.num_ratios; ++si) {
+        const int st = 1 + si;  // the up conv's input (and GEMM rows); its output is stage st + 1
+        // [len][C] -> [len][r * C/2] = [len * r][C/2]
+        GemmArgs au = conv(e->dec_up[si], xe, w.q, st);
+        LAUNCH_TRY(launch_gemm(ROLE_UPCONV, au, s, &kname, PREC_F32), "up conv");
+        snprintf(nm, sizeof nm, "dec_up_s%d", si);
+        rec.mark(nm, fl(au, st), by(au, st), kname);
+        C /= 2;
+        snprintf(nm, sizeof nm, "up%d", si);
+        if ((rc = tap(nm, w.q, st + 1, C))) return rc;
+        ResArgs ra{};
+        ra.x = w.q;
+        ra.T = L.len(st + 1);
+        ra.batch = B;
+        ra.w3 = e->dec_res3[si].w;
+        ra.b3 = e->dec_res3[si].b;
+        ra.w1 = e->dec_res1[si].w;
+        ra.b1 = e->dec_res1[si].b;
+        ra.y = xe;
+        ra.ilen = L.tlen(st + 1);
+        ra.ioff = L.toff(st + 1);
+        LAUNCH_TRY(launch_resblock(C, ra, s, &kname), "decoder resblock");
+        snprintf(nm, sizeof nm, "dec_res_s%d", si);
+        const double Hh = C / c.compress, rows = (double)L.rows(st + 1);
+        rec.mark(nm, 2.0 * rows * (3.0 * C * Hh + Hh * C), rows * 2 * C * 4, kname);
+        snprintf(nm, sizeof nm, "dres%d_elu", si);
+        if ((rc = tap(nm, xe, st + 1, C))) return rc;
+    }
+    const int last = L.nst - 1;
+    LAUNCH_TRY(launch_final_conv(xe, e->dec_last.w, e->dec_last.b, dev_audio, B, L.f[last] * L.stride, C,
+                                 c.last_kernel_size, s, L.tlen(last), L.toff(last), L.len(last)),
+               "final conv");
+    rec.mark("dec_final", 2.0 * L.rows(last) * C * c.last_kernel_size, (double)L.rows(last) * (C + 1) * 4,
+             L.ragged ? "mimi::final_conv_ragged_kernel" : "mimi::final_conv_kernel");
+    return MIMI_OK;
+}
+
 extern "C" int mimi_decode(mimi_engine* e, const int32_t* dev_codes, int32_t batch, int64_t frames, int32_t K,
                            float* dev_audio, void* stream) {
     if (!e) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null engine");
     std::lock_guard<std::mutex> lk(e->mu);
     int rc = check_decode_state(e, K);
     if (rc) return rc;
-    const mimi_config& c = e->cfg;
-    const int64_t up = decode_upsampling(c);
+    const int64_t up = decode_upsampling(e->cfg);
     if (batch <= 0 || batch > 65535 || frames <= 0 || !dev_codes || !dev_audio)
         return set_err(MIMI_ERR_INVALID_ARGUMENT, "batch=%d frames=%lld", batch, (long long)frames);
     // the GEMMs index an item's rows with 32-bit M and the rvq kernel B * T frames with 32-bit blocks
@@ -3121,137 +3258,39 @@ extern "C" int mimi_decode(mimi_engine* e, const int32_t* dev_codes, int32_t bat
         return set_err(MIMI_ERR_UNSUPPORTED, "decode of %lld frames per item exceeds the 32-bit row range", (long long)frames);
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int B = batch;
-    const int64_t T = frames, T2 = 2 * frames;
-    if ((rc = ensure_dws(e, decode_ws_layout(e, B, T, e->taps).bytes))) return rc;
-    const DecodeWs w = decode_ws_layout(e, B, T, e->taps);
-    if ((rc = ensure_rope(e, T2))) return rc;
-    const int Hd = c.hidden_size, Dq = c.vq_hidden_dim;
-    HIP_TRY(hipMemsetAsync(e->dec_flag, 0, sizeof(unsigned), s));
-    Recorder rec{e, s};
-    rec.begin();
-    const char* kname = "?";
-    auto fl = [](const GemmArgs& a) { return 2.0 * a.batch * (double)a.M * a.N * a.K; };
-    auto by = [](const GemmArgs& a) { return ((double)a.batch * a.M * (a.a_rs + a.N) + (double)a.N * a.K) * 4; };
-
-    // ---- quantizer.decode + upsample ----
-    float* sums = w.p;
-    float* emb = w.p + (size_t)B * T * 2 * Dq;
-    if ((rc = run_dequantize(e, dev_codes, (int64_t)B * T, (int)T, K, sums, emb, s, rec))) return rc;
-    if ((rc = save_tap(e, "quantized", emb, B, T, Hd, s))) return rc;
-    float* t0 = w.q;
-    float* t1 = t0 + (size_t)B * T2 * Hd;
-    float* qkv = t1 + (size_t)B * T2 * Hd;
-    float* att = qkv + (size_t)B * T2 * 3 * c.num_attention_heads * c.head_dim;
-    float* ff = att + (size_t)B * T2 * Hd;
-    LAUNCH_TRY(launch_upsample_dw(emb, e->upsample_w, t0, B, T, Hd, s), "upsample");
-    rec.mark("dec_upsample", 4.0 * B * T2 * Hd, 3.0 * B * T * Hd * 4, "mimi::upsample_dw_kernel");
-    if ((rc = save_tap(e, "upsample", t0, B, T2, Hd, s))) return rc;
-
-    // ---- decoder transformer ----
-    if ((rc = run_transformer_f32(e, e->dxf, B, T2, t0, t1, qkv, att, ff, s, rec, "dec_"))) return rc;
-    char nm[64];
-    snprintf(nm, sizeof nm, "xfmr%d", c.num_hidden_layers - 1);
-    if ((rc = save_tap(e, nm, t0, B, T2, Hd, s))) return rc;
-
-    // ---- SEANet decoder ----
-    int C = c.num_filters << c.num_ratios;
-    if (e->taps) {  // the raw layer-0 output (the pass itself only needs its ELU)
-        GemmArgs at = conv_args(e->dec_first, t0, T2, w.tap, T2, B);
-        LAUNCH_TRY(launch_gemm(ROLE_DOWN, at, s, &kname, PREC_F32), "decoder conv 0 (tap)");
-        rec.mark("dec_conv0_tap", fl(at), by(at), kname);
-        if ((rc = save_tap(e, "dconv0", w.tap, B, T2, C, s))) return rc;
-    }
-    float* xe = w.p;  // ELU'd input of the next up conv
-    GemmArgs a0 = conv_args(e->dec_first, t0, T2, xe, T2, B);
-    LAUNCH_TRY(launch_gemm(ROLE_DOWN_ELU, a0, s, &kname, PREC_F32), "decoder conv 0");
-    rec.mark("dec_conv0", fl(a0), by(a0), kname);
-    if ((rc = save_tap(e, "dconv0_elu", xe, B, T2, C, s))) return rc;  // what the pass itself computes and up conv 0 reads
-    int64_t len = T2;
-    for (int si = 0; si < c.num_ratios; ++si) {
-        const int r = c.upsampling_ratios[si];
-        const DevConv& uc = e->dec_up[si];
-        // [len][C] -> [len][r * C/2] = [len * r][C/2]
-        GemmArgs au = conv_args(uc, xe, len, w.q, len, B);
-        LAUNCH_TRY(launch_gemm(ROLE_UPCONV, au, s, &kname, PREC_F32), "up conv");
-        snprintf(nm, sizeof nm, "dec_up_s%d", si);
-        rec.mark(nm, fl(au), by(au), kname);
-        len *= r;
-        C /= 2;
-        snprintf(nm, sizeof nm, "up%d", si);
-        if ((rc = save_tap(e, nm, w.q, B, len, C, s))) return rc;
-        ResArgs ra{};
-        ra.x = w.q;
-        ra.T = len;
-        ra.batch = B;
-        ra.w3 = e->dec_res3[si].w;
-        ra.b3 = e->dec_res3[si].b;
-        ra.w1 = e->dec_res1[si].w;
-        ra.b1 = e->dec_res1[si].b;
-        ra.y = xe;
-        LAUNCH_TRY(launch_resblock(C, ra, s, &kname), "decoder resblock");
-        snprintf(nm, sizeof nm, "dec_res_s%d", si);
-        const double Hh = C / c.compress;
-        rec.mark(nm, 2.0 * B * len * (3.0 * C * Hh + Hh * C), (double)B * len * 2 * C * 4, kname);
-        snprintf(nm, sizeof nm, "dres%d_elu", si);
-        if ((rc = save_tap(e, nm, xe, B, len, C, s))) return rc;
-    }
-    LAUNCH_TRY(launch_final_conv(xe, e->dec_last.w, e->dec_last.b, dev_audio, B, len, C, c.last_kernel_size, s),
-               "final conv");
-    rec.mark("dec_final", 2.0 * B * len * C * c.last_kernel_size, (double)B * len * (C + 1) * 4, "mimi::final_conv_kernel");
-    if ((rc = save_tap(e, "audio", dev_audio, B, len, 1, s))) return rc;
+    DecLayout L;
+    plan_decode(e, nullptr, batch, frames, &L);
+    if ((rc = ensure_dws(e, decode_ws_layout(e, L, e->taps).bytes))) return rc;
+    if ((rc = decode_pass(e, dev_codes, L, decode_ws_layout(e, L, e->taps), K, dev_audio, s))) return rc;
+    if ((rc = save_tap(e, "audio", dev_audio, batch, up * frames, 1, s))) return rc;
     return read_decode_flag(e, s);
 }
 
-// ---- ragged decode: B items of frame_lengths[b] frames in one pass over packed rows (DecRagged) ----
-// Every stage either runs unchanged on the packed rows (the flat-row GEMMs and LayerNorm) or in its ragged form, which
-// takes an item's base and length from the table and otherwise repeats the uniform kernel's arithmetic: item b's
-// samples are bitwise those of mimi_decode on that item alone.  The workspace is decode's (dws), laid out as a B = 1
-// decode of sumT frames with the int tables behind it.
-static size_t pad256(size_t bytes) { return (bytes + 255) / 256 * 256; }
-
-static int plan_decode_ragged(const mimi_engine* e, const int64_t* lengths, int32_t batch, DecRagged* rg) {
-    const mimi_config& c = e->cfg;
-    rg->B = batch;
-    rg->nst = 2 + c.num_ratios;
-    rg->f.assign(1, 1);
-    rg->f.push_back(2);
-    for (int i = 0; i < c.num_ratios; ++i) rg->f.push_back(rg->f.back() * c.upsampling_ratios[i]);
-    rg->sumT = 0;
-    rg->maxT = 0;
-    rg->minT = INT64_MAX;
-    for (int b = 0; b < batch; ++b) {
-        if (lengths[b] < 1) return 1;
-        rg->sumT += lengths[b];
-        rg->maxT = std::max(rg->maxT, lengths[b]);
-        rg->minT = std::min(rg->minT, lengths[b]);
-        if (rg->sumT > 0x7fffffffLL) return 2;
-    }
-    return 0;
-}
-
+// ---- ragged decode: B items of frame_lengths[b] frames in one pass over packed rows (DecLayout) ----
+// The caller's codes are padded [B][K][max_frames] and its waveform padded [B][up max_frames]: the columns past an
+// item's length are never read, the samples past it never written.
 extern "C" int64_t mimi_decode_ragged_workspace_bytes(const mimi_engine* e, const int64_t* frame_lengths, int32_t batch) {
     if (!e || !frame_lengths || batch <= 0) return -1;
-    DecRagged rg;
-    if (plan_decode_ragged(e, frame_lengths, batch, &rg)) return -1;
-    return (int64_t)(decode_ws_layout(e, 1, rg.sumT, e->taps).bytes + pad256(DecRagged::ints(batch, rg.nst) * sizeof(int)));
+    DecLayout L;
+    if (plan_decode(e, frame_lengths, batch, 0, &L)) return -1;
+    return (int64_t)decode_ws_layout(e, L, e->taps).bytes;
 }
 
 // the "audio" tap of a ragged decode: the items' samples packed, as every other tap of the pass
-static int save_tap_audio_ragged(mimi_engine* e, const float* audio, const int64_t* lengths, const DecRagged& rg,
-                                 int64_t row_stride, hipStream_t s) {
+static int save_tap_audio_ragged(mimi_engine* e, const float* audio, const int64_t* lengths, const DecLayout& L,
+                                 hipStream_t s) {
     if (!e->taps) return MIMI_OK;
     auto& tp = e->tapmap["audio"];
-    const int64_t up = rg.f.back();
-    const size_t n = (size_t)(up * rg.sumT);
+    const int64_t up = L.f.back();
+    const size_t n = (size_t)(up * L.sumT);
     if (tp.cap < n) {
         if (tp.d) HIP_TRY(hipFree(tp.d));
         HIP_TRY(hipMalloc(&tp.d, n * 4));
         tp.cap = n;
     }
     int64_t off = 0;
-    for (int b = 0; b < rg.B; ++b) {
-        HIP_TRY(hipMemcpyAsync(tp.d + up * off, audio + (size_t)b * row_stride, (size_t)(up * lengths[b]) * 4,
+    for (int b = 0; b < L.B; ++b) {
+        HIP_TRY(hipMemcpyAsync(tp.d + up * off, audio + (size_t)b * (up * L.stride), (size_t)(up * lengths[b]) * 4,
                                hipMemcpyDeviceToDevice, s));
         off += lengths[b];
     }
@@ -3261,17 +3300,12 @@ static int save_tap_audio_ragged(mimi_engine* e, const float* audio, const int64
     return MIMI_OK;
 }
 
-static int decode_ragged_locked(mimi_engine* e, const int32_t* dev_codes, const int64_t* lengths, int B, int64_t Tmax,
-                                int K, float* dev_audio, hipStream_t s, DecRagged& rg) {
-    const mimi_config& c = e->cfg;
-    const int Hd = c.hidden_size, Dq = c.vq_hidden_dim;
-    const int64_t S = rg.sumT, S2 = 2 * S, M2 = 2 * rg.maxT;
+static int decode_ragged_locked(mimi_engine* e, const int32_t* dev_codes, const int64_t* lengths, int K,
+                                float* dev_audio, hipStream_t s, DecLayout& L) {
     int rc;
-    const size_t act_bytes = decode_ws_layout(e, 1, S, e->taps).bytes;
-    const size_t nints = DecRagged::ints(B, rg.nst);
-    if ((rc = ensure_dws(e, act_bytes + pad256(nints * sizeof(int))))) return rc;
-    const DecodeWs w = decode_ws_layout(e, 1, S, e->taps);
-    if ((rc = ensure_rope(e, M2))) return rc;
+    if ((rc = ensure_dws(e, decode_ws_layout(e, L, e->taps).bytes))) return rc;
+    const DecodeWs w = decode_ws_layout(e, L, e->taps);
+    const size_t nints = L.ints();
     if (e->dec_rg_cap < nints) {
         if (e->dec_rg_host) HIP_TRY(hipHostFree(e->dec_rg_host));
         e->dec_rg_host = nullptr;
@@ -3279,115 +3313,19 @@ static int decode_ragged_locked(mimi_engine* e, const int32_t* dev_codes, const 
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->dec_rg_host), nints * sizeof(int), hipHostMallocDefault));
         e->dec_rg_cap = nints;
     }
-    {
-        int* h = e->dec_rg_host;
-        for (int st = 0; st < rg.nst; ++st) {
-            int64_t off = 0;
-            for (int b = 0; b < B; ++b) {
-                h[(size_t)(2 * st) * B + b] = (int)(rg.f[st] * lengths[b]);
-                h[(size_t)(2 * st + 1) * B + b] = (int)(rg.f[st] * off);
-                off += lengths[b];
-            }
+    int* h = e->dec_rg_host;
+    for (int st = 0; st < L.nst; ++st) {
+        int64_t off = 0;
+        for (int b = 0; b < L.B; ++b) {
+            h[(size_t)(2 * st) * L.B + b] = (int)(L.f[st] * lengths[b]);
+            h[(size_t)(2 * st + 1) * L.B + b] = (int)(L.f[st] * off);
+            off += lengths[b];
         }
     }
-    int* dtab = reinterpret_cast<int*>(reinterpret_cast<char*>(e->dws) + act_bytes);
-    HIP_TRY(hipMemcpyAsync(dtab, e->dec_rg_host, nints * sizeof(int), hipMemcpyHostToDevice, s));
-    rg.dev = dtab;
-    HIP_TRY(hipMemsetAsync(e->dec_flag, 0, sizeof(unsigned), s));
-    Recorder rec{e, s};
-    rec.begin();
-    const char* kname = "?";
-    auto fl = [&](const GemmArgs& a, int st) { return 2.0 * (double)(rg.f[st] * S) * a.N * a.K; };
-    auto by = [&](const GemmArgs& a, int st) { return ((double)(rg.f[st] * S) * (a.a_rs + a.N) + (double)a.N * a.K) * 4; };
-    auto per_item = [&](GemmArgs& a, int st) {
-        a.a_rows = a.m_rows = rg.tlen(st);
-        a.a_boff = a.c_boff = rg.toff(st);
-    };
-
-    // ---- quantizer.decode + upsample ----
-    float* sums = w.p;
-    float* emb = w.p + (size_t)S * 2 * Dq;
-    LAUNCH_TRY(launch_rvq_decode_ragged(dev_codes, B, (int)Tmax, (int)rg.maxT, K, c.num_semantic_quantizers,
-                                        c.codebook_size, c.codebook_dim, e->cb_rows, sums, e->dec_flag, rg.tlen(0),
-                                        rg.toff(0), s),
-               "rvq_decode (ragged)");
-    rec.mark("dec_rvq", (double)S * K * Dq, (double)S * (K * Dq + 2 * Dq) * 4, "mimi::rvq_decode_ragged_kernel");
-    {
-        GemmArgs ap = linear_args(sums, S, 2 * Dq, e->outproj, Hd, emb);
-        LAUNCH_TRY(launch_gemm(ROLE_INPROJ, ap, s, &kname, PREC_F32), "output_proj");
-        rec.mark("dec_output_proj", 2.0 * S * 2 * Dq * Hd, (double)S * (2 * Dq + Hd) * 4, kname);
-    }
-    if ((rc = save_tap(e, "quantized", emb, 1, S, Hd, s))) return rc;
-    float* t0 = w.q;
-    float* t1 = t0 + (size_t)S2 * Hd;
-    float* qkv = t1 + (size_t)S2 * Hd;
-    float* att = qkv + (size_t)S2 * 3 * c.num_attention_heads * c.head_dim;
-    float* ff = att + (size_t)S2 * Hd;
-    LAUNCH_TRY(launch_upsample_dw_ragged(emb, e->upsample_w, t0, B, (int)rg.maxT, Hd, rg.tlen(0), rg.toff(0), s),
-               "upsample (ragged)");
-    rec.mark("dec_upsample", 4.0 * S2 * Hd, 3.0 * S * Hd * 4, "mimi::upsample_dw_ragged_kernel");
-    if ((rc = save_tap(e, "upsample", t0, 1, S2, Hd, s))) return rc;
-
-    // ---- decoder transformer ----
-    if ((rc = run_transformer_f32(e, e->dxf, B, M2, t0, t1, qkv, att, ff, s, rec, "dec_", &rg))) return rc;
-    char nm[64];
-    snprintf(nm, sizeof nm, "xfmr%d", c.num_hidden_layers - 1);
-    if ((rc = save_tap(e, nm, t0, 1, S2, Hd, s))) return rc;
-
-    // ---- SEANet decoder ----
-    int C = c.num_filters << c.num_ratios;
-    if (e->taps) {
-        GemmArgs at = conv_args(e->dec_first, t0, M2, w.tap, M2, B);
-        per_item(at, 1);
-        LAUNCH_TRY(launch_gemm(ROLE_DOWN, at, s, &kname, PREC_F32), "decoder conv 0 (tap)");
-        rec.mark("dec_conv0_tap", fl(at, 1), by(at, 1), kname);
-        if ((rc = save_tap(e, "dconv0", w.tap, 1, S2, C, s))) return rc;
-    }
-    float* xe = w.p;
-    GemmArgs a0 = conv_args(e->dec_first, t0, M2, xe, M2, B);
-    per_item(a0, 1);
-    LAUNCH_TRY(launch_gemm(ROLE_DOWN_ELU, a0, s, &kname, PREC_F32), "decoder conv 0");
-    rec.mark("dec_conv0", fl(a0, 1), by(a0, 1), kname);
-    if ((rc = save_tap(e, "dconv0_elu", xe, 1, S2, C, s))) return rc;
-    for (int si = 0; si < c.num_ratios; ++si) {
-        const int st = 1 + si;  // the up conv's input (and GEMM rows); its output is stage st + 1
-        const DevConv& uc = e->dec_up[si];
-        const int64_t mlen = rg.f[st] * rg.maxT;
-        GemmArgs au = conv_args(uc, xe, mlen, w.q, mlen, B);
-        per_item(au, st);
-        LAUNCH_TRY(launch_gemm(ROLE_UPCONV, au, s, &kname, PREC_F32), "up conv");
-        snprintf(nm, sizeof nm, "dec_up_s%d", si);
-        rec.mark(nm, fl(au, st), by(au, st), kname);
-        C /= 2;
-        const int64_t rows = rg.f[st + 1] * S;
-        snprintf(nm, sizeof nm, "up%d", si);
-        if ((rc = save_tap(e, nm, w.q, 1, rows, C, s))) return rc;
-        ResArgs ra{};
-        ra.x = w.q;
-        ra.T = rg.f[st + 1] * rg.maxT;
-        ra.batch = B;
-        ra.w3 = e->dec_res3[si].w;
-        ra.b3 = e->dec_res3[si].b;
-        ra.w1 = e->dec_res1[si].w;
-        ra.b1 = e->dec_res1[si].b;
-        ra.y = xe;
-        ra.ilen = rg.tlen(st + 1);
-        ra.ioff = rg.toff(st + 1);
-        LAUNCH_TRY(launch_resblock(C, ra, s, &kname), "decoder resblock");
-        snprintf(nm, sizeof nm, "dec_res_s%d", si);
-        const double Hh = C / c.compress;
-        rec.mark(nm, 2.0 * rows * (3.0 * C * Hh + Hh * C), (double)rows * 2 * C * 4, kname);
-        snprintf(nm, sizeof nm, "dres%d_elu", si);
-        if ((rc = save_tap(e, nm, xe, 1, rows, C, s))) return rc;
-    }
-    const int last = rg.nst - 1;
-    const int64_t up = rg.f[last];
-    LAUNCH_TRY(launch_final_conv_ragged(xe, e->dec_last.w, e->dec_last.b, dev_audio, B, up * Tmax, up * rg.maxT, C,
-                                        c.last_kernel_size, rg.tlen(last), rg.toff(last), s),
-               "final conv (ragged)");
-    rec.mark("dec_final", 2.0 * up * S * C * c.last_kernel_size, (double)up * S * (C + 1) * 4,
-             "mimi::final_conv_ragged_kernel");
-    if ((rc = save_tap_audio_ragged(e, dev_audio, lengths, rg, up * Tmax, s))) return rc;
+    HIP_TRY(hipMemcpyAsync(w.tab, h, nints * sizeof(int), hipMemcpyHostToDevice, s));
+    L.dev = w.tab;
+    if ((rc = decode_pass(e, dev_codes, L, w, K, dev_audio, s))) return rc;
+    if ((rc = save_tap_audio_ragged(e, dev_audio, lengths, L, s))) return rc;
     return read_decode_flag(e, s);
 }
 
@@ -3400,15 +3338,15 @@ extern "C" int mimi_decode_ragged(mimi_engine* e, const int32_t* dev_codes, cons
     if (batch <= 0 || batch > 65535 || max_frames <= 0 || !dev_codes || !dev_audio)
         return set_err(MIMI_ERR_INVALID_ARGUMENT, "batch=%d max_frames=%lld", batch, (long long)max_frames);
     if ((rc = check_ragged(e, frame_lengths, batch, max_frames))) return rc;
-    DecRagged rg;
+    DecLayout L;
     // the kernels index packed rows with 32-bit ints at every rate, the caller's padded waveform rows too
-    if (plan_decode_ragged(e, frame_lengths, batch, &rg) || rg.sumT * decode_upsampling(e->cfg) > 0x7fffffffLL ||
+    if (plan_decode(e, frame_lengths, batch, max_frames, &L) || L.sumT * decode_upsampling(e->cfg) > 0x7fffffffLL ||
         max_frames * decode_upsampling(e->cfg) > 0x7fffffffLL)
         return set_err(MIMI_ERR_UNSUPPORTED, "ragged decode of %lld frames in all exceeds the 32-bit row range",
-                       (long long)rg.sumT);
+                       (long long)L.sumT);
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    rc = decode_ragged_locked(e, dev_codes, frame_lengths, batch, max_frames, K, dev_audio, s, rg);
+    rc = decode_ragged_locked(e, dev_codes, frame_lengths, K, dev_audio, s, L);
     // the tables' pinned host image and the workspace are reused by the next call: nothing of this one stays in flight
     if (rc) (void)hipStreamSynchronize(s);
     return rc;

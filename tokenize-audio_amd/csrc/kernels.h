@@ -461,27 +461,25 @@ size_t rvq_work_bytes(long long frames);
 hipError_t launch_rvq(const RvqArgs& a, hipStream_t s, const char** kname = nullptr, unsigned** chain_flag = nullptr,
                       size_t* clear_bytes = nullptr);
 
-// Decode path (decode.hip).  launch_rvq_decode: codes [B][K][T] (frames = B * T, frames_per_item = T) -> out
-// [frames][2 * D] = (semantic sum | acoustic sum) of cb_rows ([level][ncodes][D]) in level order; a code outside
-// [0, ncodes) is never used as an index: it raises *flag (device word, zeroed by the caller) and row 0 is read.
-hipError_t launch_rvq_decode(const int32_t* codes, long long frames, int frames_per_item, int K, int nsem, int ncodes,
-                             int D, const float* cb_rows, float* out, unsigned* flag, hipStream_t s);
-// depthwise causal transposed conv (k = 4, stride 2, no bias): x [B][T][C] -> y [B][2T][C]; w [C][4]
-hipError_t launch_upsample_dw(const float* x, const float* w, float* y, int batch, long long T, int C, hipStream_t s);
-// the decoder's last conv (k = 3, causal, 64 -> 1): x [B][L][64] already ELU'd, w [3][64] tap-major, y [B][L]
+// Decode path (decode.hip).  tlen / toff (ragged batches, mimi_decode_ragged; else both null): the activations' rows
+// are packed, item b's tlen[b] rows of the stage starting at row toff[b] (device int tables of the stage's rate), and
+// the longest item's length sizes the grid.  Codes keep the caller's padded [B][K][T] layout (columns past tlen[b] are
+// never read) and the waveform the padded [B][L] one (samples past llen[b] are left untouched).
+// launch_rvq_decode: codes [B][K][T] (frames = B * T) -> out [frames][2 * D] (ragged: [sum tlen][2 * D]) = (semantic
+// sum | acoustic sum) of cb_rows ([level][ncodes][D]) in level order; a code outside [0, ncodes) is never used as an
+// index: it raises *flag (device word, zeroed by the caller) and row 0 is read.
+hipError_t launch_rvq_decode(const int32_t* codes, long long frames, int T, int K, int nsem, int ncodes, int D,
+                             const float* cb_rows, float* out, unsigned* flag, hipStream_t s, const int* tlen = nullptr,
+                             const int* toff = nullptr, int max_tlen = 0);
+// depthwise causal transposed conv (k = 4, stride 2, no bias): x [B][T][C] -> y [B][2T][C]; w [C][4] (ragged: T = the
+// longest item's frames)
+hipError_t launch_upsample_dw(const float* x, const float* w, float* y, int batch, long long T, int C, hipStream_t s,
+                              const int* tlen = nullptr, const int* toff = nullptr);
+// the decoder's last conv (k = 3, causal, 64 -> 1): x [B][L][64] already ELU'd, w [3][64] tap-major, y [B][L] (ragged:
+// L = y's row stride, max_llen = the longest item's samples)
 hipError_t launch_final_conv(const float* x, const float* w, const float* bias, float* y, int batch, long long L, int C,
-                             int ksize, hipStream_t s);
-// Ragged forms (mimi_decode_ragged): packed rows, item b's tlen[b] rows of the stage start at row toff[b] (device int
-// tables of the stage's rate); max_tlen sizes the grid.  Codes keep the caller's padded [B][K][Ts] layout (columns past
-// tlen[b] are never read) and the waveform the padded [B][Ls] one (samples past llen[b] are left untouched).
-hipError_t launch_rvq_decode_ragged(const int32_t* codes, int batch, int Ts, int max_tlen, int K, int nsem, int ncodes,
-                                    int D, const float* cb_rows, float* out, unsigned* flag, const int* tlen,
-                                    const int* toff, hipStream_t s);
-hipError_t launch_upsample_dw_ragged(const float* x, const float* w, float* y, int batch, int max_tlen, int C,
-                                     const int* tlen, const int* toff, hipStream_t s);
-hipError_t launch_final_conv_ragged(const float* x, const float* w, const float* bias, float* y, int batch, long long Ls,
-                                    long long max_llen, int C, int ksize, const int* llen, const int* loff,
-                                    hipStream_t s);
+                             int ksize, hipStream_t s, const int* llen = nullptr, const int* loff = nullptr,
+                             long long max_llen = 0);
 
 // polyphase resampler (resample.hip): clips packed at in_off / out_off (device int64 arrays), one launch
 hipError_t launch_resample_poly(const float* x, const long long* in_off, const long long* in_len, int nclips,

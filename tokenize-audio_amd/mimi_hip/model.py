@@ -376,6 +376,29 @@ class MimiHipModel:
             raise RuntimeError("this MimiHipModel holds the encode path only: construct it with decode=True "
                                "(MimiHipModel(..., decode=True) / from_pretrained(..., decode=True)) to decode")
 
+    def _decode_codes(self, audio_codes) -> torch.Tensor:
+        """The ``[B, K, T]`` codes of a decode call as a tensor, K within the model's levels."""
+        self._require_decode()
+        if not torch.is_tensor(audio_codes):
+            audio_codes = torch.as_tensor(np.asarray(audio_codes))
+        if audio_codes.dim() != 3:
+            raise ValueError(f"audio_codes must be [batch, num_quantizers, frames], got {tuple(audio_codes.shape)}")
+        K = audio_codes.shape[1]
+        if K > self.config.num_quantizers or K < 1:
+            raise ValueError(f"The number of quantizers (i.e codebooks) must be in [1, {self.config.num_quantizers}], "
+                             f"but is currently {K}.")
+        return audio_codes
+
+    def _decode_call(self, fn, *args):
+        """One decode entry point of the library on this model's stream; its MIMI_ERR_INVALID_ARGUMENT (a code outside
+        ``[0, codebook_size)``, K over the levels) is a ``ValueError``."""
+        try:
+            _lib.check(fn(self._h, *args, self._stream()))
+        except _lib.MimiHipError as err:
+            if err.status == 1:
+                raise ValueError(str(err)) from None
+            raise
+
     def decode(self, audio_codes: torch.Tensor, padding_mask: Optional[torch.Tensor] = None,
                decoder_past_key_values=None, return_dict: Optional[bool] = None):
         """``MimiModel.decode`` (``TF/modeling_mimi.py:1408-1458``): int64 / int32 codes ``[B, K, T]`` on any device
@@ -384,24 +407,13 @@ class MimiHipModel:
         self._require_decode()
         if decoder_past_key_values is not None:
             raise NotImplementedError("streaming decode (KV cache) is not on the batch path")
-        if not torch.is_tensor(audio_codes):
-            audio_codes = torch.as_tensor(np.asarray(audio_codes))
-        if audio_codes.dim() != 3:
-            raise ValueError(f"audio_codes must be [batch, num_quantizers, frames], got {tuple(audio_codes.shape)}")
+        audio_codes = self._decode_codes(audio_codes)
         B, K, T = audio_codes.shape
-        if K > self.config.num_quantizers or K < 1:
-            raise ValueError(f"The number of quantizers (i.e codebooks) must be in [1, {self.config.num_quantizers}], "
-                             f"but is currently {K}.")
         audio = torch.empty((B, 1, self.get_decoded_length(T)), dtype=torch.float32, device=self.device)
         if B and T:
             codes = audio_codes.to(device=self.device, dtype=torch.int32).contiguous()
-            try:
-                _lib.check(self._lib.mimi_decode(self._h, ctypes.c_void_p(codes.data_ptr()), B, T, K,
-                                                 ctypes.c_void_p(audio.data_ptr()), self._stream()))
-            except _lib.MimiHipError as err:
-                if err.status == 1:  # MIMI_ERR_INVALID_ARGUMENT: a code outside [0, codebook_size), K over the levels
-                    raise ValueError(str(err)) from None
-                raise
+            self._decode_call(self._lib.mimi_decode, ctypes.c_void_p(codes.data_ptr()), B, T, K,
+                              ctypes.c_void_p(audio.data_ptr()))
         if padding_mask is not None and padding_mask.shape[-1] < audio.shape[-1]:
             audio = audio[..., : padding_mask.shape[-1]]
         if return_dict is False:
@@ -419,15 +431,8 @@ class MimiHipModel:
         Returns a list of B float32 device tensors ``[1, 1920 lengths[b]]``, views of one ``[B, 1920 Tmax]`` buffer
         (``out`` if given: the samples past an item's length are left as they were).  Item b is bit for bit
         ``decode(audio_codes[b:b + 1, :, :lengths[b]]).audio_values[0]``."""
-        self._require_decode()
-        if not torch.is_tensor(audio_codes):
-            audio_codes = torch.as_tensor(np.asarray(audio_codes))
-        if audio_codes.dim() != 3:
-            raise ValueError(f"audio_codes must be [batch, num_quantizers, frames], got {tuple(audio_codes.shape)}")
+        audio_codes = self._decode_codes(audio_codes)
         B, K, T = audio_codes.shape
-        if K > self.config.num_quantizers or K < 1:
-            raise ValueError(f"The number of quantizers (i.e codebooks) must be in [1, {self.config.num_quantizers}], "
-                             f"but is currently {K}.")
         lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
         if lens.shape != (B,) or (B and (int(lens.min()) < 1 or int(lens.max()) > T)):
             raise ValueError(f"lengths must be {B} values in [1, {T}]")
@@ -439,33 +444,19 @@ class MimiHipModel:
             raise ValueError(f"out must be a contiguous float32 [{B}, {L}] tensor on {self.device}")
         if B:
             codes = audio_codes.to(device=self.device, dtype=torch.int32).contiguous()
-            try:
-                _lib.check(self._lib.mimi_decode_ragged(self._h, ctypes.c_void_p(codes.data_ptr()),
-                                                        ctypes.c_void_p(lens.ctypes.data), B, T, K,
-                                                        ctypes.c_void_p(out.data_ptr()), self._stream()))
-            except _lib.MimiHipError as err:
-                if err.status == 1:  # MIMI_ERR_INVALID_ARGUMENT: a code outside [0, codebook_size) inside an item
-                    raise ValueError(str(err)) from None
-                raise
+            self._decode_call(self._lib.mimi_decode_ragged, ctypes.c_void_p(codes.data_ptr()),
+                              ctypes.c_void_p(lens.ctypes.data), B, T, K, ctypes.c_void_p(out.data_ptr()))
         return [out[b:b + 1, : self.get_decoded_length(int(lens[b]))] for b in range(B)]
 
     def dequantize(self, codes: torch.Tensor) -> torch.Tensor:
         """Quantizer decode alone (``mimi_rvq_decode``): codes [B, K, T] -> float32 embedding [B, 512, T], the mirror
         of ``quantize``."""
-        self._require_decode()
+        codes = self._decode_codes(codes)
         B, K, T = codes.shape
-        if K > self.config.num_quantizers or K < 1:
-            raise ValueError(f"The number of quantizers (i.e codebooks) must be in [1, {self.config.num_quantizers}], "
-                             f"but is currently {K}.")
         c = codes.to(device=self.device, dtype=torch.int32).permute(1, 0, 2).contiguous()  # [K][B * T]
         emb = torch.empty((B * T, self.config.hidden_size), dtype=torch.float32, device=self.device)
-        try:
-            _lib.check(self._lib.mimi_rvq_decode(self._h, ctypes.c_void_p(c.data_ptr()), B * T, K,
-                                                 ctypes.c_void_p(emb.data_ptr()), self._stream()))
-        except _lib.MimiHipError as err:
-            if err.status == 1:
-                raise ValueError(str(err)) from None
-            raise
+        self._decode_call(self._lib.mimi_rvq_decode, ctypes.c_void_p(c.data_ptr()), B * T, K,
+                          ctypes.c_void_p(emb.data_ptr()))
         return emb.view(B, T, -1).permute(0, 2, 1)
 
     # ---- instrumentation ------------------------------------------------------------------------

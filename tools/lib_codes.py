@@ -1,7 +1,12 @@
 """Codes of fixed synthetic batches from the engine library named by MIMI_HIP_LIB (A/B builds): writes
 gpurun_out/<tag>_codes.npz with B = 32 x 10 s (K = 32), a ragged 17-item batch and a batch-1 clip, and every stage tap
 (sha-256 of the fp32 values, planes reconstructed) of a B = 32 x 1 s batch (the fused q/k/v + attention path) and a B = 2 x 3 s batch
-(the two-kernel path), so builds that must give the same bits can be compared file to file (tools/cmp_codes.py)."""
+(the two-kernel path), so builds that must give the same bits can be compared file to file (tools/cmp_codes.py).
+
+`lib_codes.py <tag> decode` writes the decode path's entries instead: the uniform decode of B = 3 x T = 13 x K = 8 and of
+B = 2 x T = 129 x K = 1, the ragged decode of T = [13, 1, 129, 2, 64, 65, 5, 3] at K = 8 (an odd T, 1- to 3-frame items,
+both sides of 256 rows and of the 1024-row tile change), the sha-256 of every tap and the profiled launch sequence and
+records of one uniform and one ragged pass, and the workspace sizes with taps off and on."""
 import hashlib
 import os
 import sys
@@ -15,31 +20,90 @@ from mimi_hip import synthetic  # noqa: E402
 from mimi_hip.model import MimiHipModel  # noqa: E402
 
 tag = sys.argv[1]
-m = MimiHipModel(synthetic.make_state_dict(seed=0), device="cuda:0")
 out = {}
-x = torch.from_numpy(synthetic.clip_batch(32, 240000, seed=501)).cuda()
-out["b32"] = m.encode_int32(x, 32).cpu().numpy()
-rng = np.random.default_rng(502)
-lengths = [int(v) for v in rng.integers(1, 300000, 17)]
-clips = [synthetic.speech_like(L, 503, i) for i, L in enumerate(lengths)]
-xr = np.zeros((len(clips), max(lengths)), np.float32)
-for i, c in enumerate(clips):
-    xr[i, :len(c)] = c
-out["ragged"] = m.encode_ragged(torch.from_numpy(xr).cuda(), lengths, 32).cpu().numpy()
-out["b1"] = m.encode_int32(torch.from_numpy(synthetic.clip_batch(1, 240000, seed=504)).cuda(), 32).cpu().numpy()
-TAPS = (["conv0", "encoder", "ds_gemm", "downsample", "proj"] + [f"res{i}_elu" for i in range(4)] +
-        [f"down{i}" for i in range(3)] + ["down3_elu"] +
-        [f"{n}{l}" for l in range(8) for n in ("qkv", "att", "oproj", "ff", "xfmr")])
-for name, (B, L, seed) in {"tb32": (32, 24000, 505), "tb2": (2, 72000, 506)}.items():
-    m.set_taps(True)
-    out[name] = m.encode_int32(torch.from_numpy(synthetic.clip_batch(B, L, seed=seed)).cuda(), 32).cpu().numpy()
-    for t in TAPS:
-        try:
-            a = np.ascontiguousarray(m.get_tap(t))
-            out[f"{name}_{t}"] = np.array([hashlib.sha256(a.tobytes()).hexdigest() + f" {a.shape}"])
-        except Exception:  # (a tap the path does not produce, e.g. q/k/v under the fused attention)
-            pass
+
+
+def tap_sha(m, t):
+    a = np.ascontiguousarray(m.get_tap(t))
+    return np.array([hashlib.sha256(a.tobytes()).hexdigest() + f" {a.shape}"])
+
+
+def encode_section():
+    m = MimiHipModel(synthetic.make_state_dict(seed=0), device="cuda:0")
+    x = torch.from_numpy(synthetic.clip_batch(32, 240000, seed=501)).cuda()
+    out["b32"] = m.encode_int32(x, 32).cpu().numpy()
+    rng = np.random.default_rng(502)
+    lengths = [int(v) for v in rng.integers(1, 300000, 17)]
+    clips = [synthetic.speech_like(L, 503, i) for i, L in enumerate(lengths)]
+    xr = np.zeros((len(clips), max(lengths)), np.float32)
+    for i, c in enumerate(clips):
+        xr[i, :len(c)] = c
+    out["ragged"] = m.encode_ragged(torch.from_numpy(xr).cuda(), lengths, 32).cpu().numpy()
+    out["b1"] = m.encode_int32(torch.from_numpy(synthetic.clip_batch(1, 240000, seed=504)).cuda(), 32).cpu().numpy()
+    TAPS = (["conv0", "encoder", "ds_gemm", "downsample", "proj"] + [f"res{i}_elu" for i in range(4)] +
+            [f"down{i}" for i in range(3)] + ["down3_elu"] +
+            [f"{n}{l}" for l in range(8) for n in ("qkv", "att", "oproj", "ff", "xfmr")])
+    for name, (B, L, seed) in {"tb32": (32, 24000, 505), "tb2": (2, 72000, 506)}.items():
+        m.set_taps(True)
+        out[name] = m.encode_int32(torch.from_numpy(synthetic.clip_batch(B, L, seed=seed)).cuda(), 32).cpu().numpy()
+        for t in TAPS:
+            try:
+                out[f"{name}_{t}"] = tap_sha(m, t)
+            except Exception:  # (a tap the path does not produce, e.g. q/k/v under the fused attention)
+                pass
+        m.set_taps(False)
+
+
+def decode_section():
+    sd = synthetic.make_state_dict(seed=0)
+    sd.update(synthetic.make_decoder_state_dict(seed=0))
+    m = MimiHipModel(sd, device="cuda:0", decode=True)
+    LENS = [13, 1, 129, 2, 64, 65, 5, 3]
+    TAPS = (["quantized", "upsample", f"xfmr{m.config.num_hidden_layers - 1}", "dconv0", "dconv0_elu"] +
+            [f"up{i}" for i in range(4)] + [f"dres{i}_elu" for i in range(4)] + ["audio"])
+    rng = np.random.default_rng(601)
+
+    def codes(B, K, T):
+        return torch.from_numpy(rng.integers(0, m.config.codebook_size, (B, K, T)).astype(np.int32)).cuda()
+
+    def text(rows):
+        return np.array([repr(r) for r in rows])
+
+    def traced(name, fn):
+        """One pass with taps and profiling on: every tap's sha-256, the launch sequence and the records."""
+        m.set_taps(True)
+        m.set_profiling(1)
+        m.profile_reset()
+        fn()
+        prof = m.profile_read()
+        out[f"{name}_sequence"] = text(m.profile_sequence())
+        out[f"{name}_records"] = text((k, v["kernel"], v["launches"], v["flops"], v["bytes"]) for k, v in prof.items())
+        m.set_profiling(0)
+        for t in TAPS:
+            out[f"{name}_{t}"] = tap_sha(m, t)
+        m.set_taps(False)
+
+    cu, c1, cr = codes(3, 8, 13), codes(2, 1, 129), codes(len(LENS), 8, max(LENS))
+    out["u_b3_t13_k8"] = m.decode(cu).audio_values.cpu().numpy()
+    out["u_b2_t129_k1"] = m.decode(c1).audio_values.cpu().numpy()
+    buf = torch.zeros((len(LENS), m.get_decoded_length(max(LENS))), dtype=torch.float32, device="cuda:0")
+    m.decode_ragged(cr, LENS, out=buf)
+    out["ragged"] = buf.cpu().numpy()  # (the samples past an item's length stay 0: never written)
+    traced("tu", lambda: m.decode(cu))
+    traced("tr", lambda: m.decode_ragged(cr, LENS))
+    for taps in (False, True):
+        m.set_taps(taps)
+        out[f"workspace_taps{int(taps)}"] = np.array(
+            [m.decode_workspace_bytes(B, T) for B, T in ((1, 13), (3, 13), (32, 125))] +
+            [m.decode_ragged_workspace_bytes(LENS)], dtype=np.int64)
     m.set_taps(False)
+    print(tag, "workspace", out["workspace_taps0"].tolist(), out["workspace_taps1"].tolist())
+
+
+if sys.argv[2:] == ["decode"]:
+    decode_section()
+else:
+    encode_section()
 os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
 np.savez(os.path.join(ROOT, "gpurun_out", f"{tag}_codes.npz"), **out)
 print(tag, {k: v.shape for k, v in out.items()})
