@@ -48,6 +48,7 @@ def ref(state_dict):
             cache[key] = m.encode_int32(x, 8).cpu()
             assert m.lane_encodes[1] == 0
         return cache[key]
+    get.quantize = lambda emb: m.quantize(emb, 8).cpu()  # (the quantizer alone, on the same engine)
     yield get
     m.close()
 
@@ -179,6 +180,23 @@ def test_sync_encodes_stay_in_lane_0(state_dict, ref):
         assert m.lane_encodes == (2, 0)
     finally:
         m.close()
+
+
+def test_quantize_between_encodes_in_flight(eng, ref):
+    """``quantize`` (mimi_rvq_encode) borrows lane 0's workspace: beside an encode in flight in each lane it gives its
+    own bits and leaves theirs alone."""
+    emb = torch.from_numpy(np.random.default_rng(11).standard_normal((1, 512, 13)).astype(np.float32)).cuda()
+    want = ref.quantize(emb)
+    x1, x2 = clip(SMALL, 800), clip(OTHER, 801)
+    chain0, f160 = eng.rvq_chain_reruns, eng.f16_reruns
+    log = []
+    t1, t2 = submit(eng, x1, log), submit(eng, x2, log)
+    assert [l for l, _, _ in log] == [0, 1]
+    got = eng.quantize(emb, 8).cpu()
+    c1, c2 = t1.wait().cpu(), t2.wait().cpu()
+    assert torch.equal(got, want)
+    assert torch.equal(c1, ref(x1)) and torch.equal(c2, ref(x2))
+    assert (eng.rvq_chain_reruns, eng.f16_reruns) == (chain0, f160)
 
 
 def test_decode_between_encodes_in_flight(state_dict, ref):

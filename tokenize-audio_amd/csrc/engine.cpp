@@ -254,9 +254,7 @@ struct mimi_engine {
     // Its producer max-reduces |x| into amax_dev[slot] for the overflow check.
     std::map<std::string, int> slot_of;
     std::vector<float> act_scale;
-    bool calibrating = false;
-    bool calibrated = false;         // calibrate_scales has run (lazily, before the first f16x3 encode)
-    bool uncalibrated_slot = false;  // the current encode named a tensor the calibration did not see (reset per encode)
+    bool calibrated = false;  // calibrate_scales has run (lazily, before the first f16x3 encode)
     unsigned* amax_host = nullptr;  // pinned (read_amax: filled and read under the lock, behind a stream sync)
     int32_t* item_codes = nullptr;  // one item's codes (per-item overflow fallback)
     // encodes enqueued by mimi_encode_async and not yet waited (see encode_async_locked)
@@ -340,13 +338,10 @@ struct mimi_engine {
     };
     static constexpr int kLanes = 2;
     Lane lanes[kLanes];
-    Lane* ln = &lanes[0];  // the lane of the submission / wait in progress (set under mu, lane 0 otherwise)
     // which encodes take a lane (mimi_set_option "lanes"): 0 none (every encode on the caller's stream in lane 0), 1 f16x3
     // uniform batches on the per-level RVQ kernels, 2 ragged and chain-eligible encodes too
     int lanes_opt = 1;
     bool graphs_enabled = true;
-    bool capturing = false;
-    size_t cap_chain_clear = 0;  // (capture) the captured chain's flag + granule bytes
     hipStream_t cap_stream = nullptr;
     int rope_gen = 0;
     uint64_t graph_clock = 0;
@@ -362,11 +357,9 @@ struct mimi_engine {
     int ln_rpw = 1;  // LayerNorm rows per wave (mimi_set_option "ln_rpw": 1 (A/B r4h: 0.186 vs 0.200 ms per B = 32 step for 2), 2, 4, 8; the same bits)
     int rvq_xcd = 1;  // large grids: a frame tile's RVQ slices on one XCD (mimi_set_option "rvq_xcd"; same bits)
     int rvq_chain = 1;  // small grids: the persistent all-levels RVQ (mimi_set_option "rvq_chain"; RvqArgs::chain)
-    // The chain is taken only where its give-up flag is read back (chain_ok: the main encode path, whose ticket carries
-    // the flag to mimi_encode_wait, and mimi_rvq_encode, which checks it itself); every fallback and internal pass runs
-    // the per-level kernels.  chain_flag: the flag word of the chain launched by the last run_rvq (null: none)
-    bool chain_ok = false;
-    unsigned* chain_flag = nullptr;
+    // The chain is taken only where its give-up flag is read back (PassCtx::chain_ok: the main encode path, whose ticket
+    // carries the flag to mimi_encode_wait, and mimi_rvq_encode, which checks it itself); every fallback and internal
+    // pass runs the per-level kernels
     int rvq_chain_fault = 0;    // tests only (mimi_set_option "rvq_chain_fault"; RvqArgs::chain_fault)
     int64_t chain_reruns = 0;   // encodes re-run without the chain after a sweep gave up (diagnostic)
     // q/k/v + attention as one kernel (qkv_attn.hip) for items of <= 256 frames: 0 off, 1 when the batch has at least
@@ -606,10 +599,11 @@ extern "C" int mimi_create(const mimi_config* cfg, int device, mimi_engine** out
     if (device < 0 || device >= ndev) return set_err(MIMI_ERR_INVALID_ARGUMENT, "device %d of %d", device, ndev);
     e->device = device;
     HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipEventCreateWithFlags(&e->ln->ws_free, hipEventDisableTiming));
-    HIP_TRY(hipMalloc(&e->ln->amax_dev, ((size_t)kMaxActSlots * AMAX_SLOT_WORDS + kMaxActSlots) * sizeof(unsigned)));
-    e->ln->amax_red = e->ln->amax_dev + (size_t)kMaxActSlots * AMAX_SLOT_WORDS;
-    HIP_TRY(hipMemset(e->ln->amax_dev, 0, ((size_t)kMaxActSlots * AMAX_SLOT_WORDS + kMaxActSlots) * sizeof(unsigned)));
+    mimi_engine::Lane& l0 = e->lanes[0];  // (lane 1's event and buffers: lane_prepare, on its first use)
+    HIP_TRY(hipEventCreateWithFlags(&l0.ws_free, hipEventDisableTiming));
+    HIP_TRY(hipMalloc(&l0.amax_dev, ((size_t)kMaxActSlots * AMAX_SLOT_WORDS + kMaxActSlots) * sizeof(unsigned)));
+    l0.amax_red = l0.amax_dev + (size_t)kMaxActSlots * AMAX_SLOT_WORDS;
+    HIP_TRY(hipMemset(l0.amax_dev, 0, ((size_t)kMaxActSlots * AMAX_SLOT_WORDS + kMaxActSlots) * sizeof(unsigned)));
     HIP_TRY(hipHostMalloc(&e->amax_host, kMaxActSlots * sizeof(unsigned), hipHostMallocDefault));
     build_expected(e.get());
     *out = e.release();
@@ -1104,7 +1098,8 @@ static int act_planes(const mimi_engine* e, const StagePlan& p, int prec) {
     return ns;
 }
 
-static size_t ws_layout(const mimi_engine* e, int B, const StagePlan& p, Workspace* w, int prec, bool ragged = false) {
+static size_t ws_layout(const mimi_engine* e, int B, const StagePlan& p, int prec, bool ragged = false,
+                        Workspace* w = nullptr, void* ws_base = nullptr) {
     const mimi_config& c = e->cfg;
     const int ns = act_planes(e, p, prec);
     // a plane-format buffer of n values takes ns * n bf16 = ns * n / 2 floats
@@ -1137,7 +1132,7 @@ static size_t ws_layout(const mimi_engine* e, int B, const StagePlan& p, Workspa
     float* rgp = nullptr;
     float** ptrs[] = {&w->x, &w->y, &w->t0, &w->t1, &w->qkv, &w->att, &w->ff, &w->dsout, &w->proj, &w->rvq,
                       &w->xe, &w->h, &rgp};
-    char* base = reinterpret_cast<char*>(e->ln->ws);
+    char* base = reinterpret_cast<char*>(ws_base);
     for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) {
         if (w) *ptrs[i] = reinterpret_cast<float*>(base + off);
         off += ((sizes[i] * sizeof(float) + 255) / 256) * 256;
@@ -1148,7 +1143,7 @@ static size_t ws_layout(const mimi_engine* e, int B, const StagePlan& p, Workspa
 
 extern "C" int64_t mimi_workspace_bytes(const mimi_engine* e, int32_t batch, int64_t length) {
     if (!e || batch <= 0 || length <= 0) return -1;
-    return (int64_t)ws_layout(e, batch, plan_lengths(e->cfg, length), nullptr, e->precision);
+    return (int64_t)ws_layout(e, batch, plan_lengths(e->cfg, length), e->precision);
 }
 
 // every lane's work done (each encode ends with its lane's ws_free, on whichever stream it ran)
@@ -1157,25 +1152,25 @@ static void drain_lanes(mimi_engine* e) {
         if (l.ws_free) (void)hipEventSynchronize(l.ws_free);
 }
 
-// the active lane's workspace (the other lane's encodes, workspace and graphs are untouched by a regrow)
-static int ensure_ws(mimi_engine* e, size_t bytes, hipStream_t s) {
-    if (bytes <= e->ln->ws_bytes) return MIMI_OK;
+// the lane's workspace (the other lane's encodes, workspace and graphs are untouched by a regrow)
+static int ensure_ws(mimi_engine::Lane& lane, size_t bytes, hipStream_t s) {
+    if (bytes <= lane.ws_bytes) return MIMI_OK;
     HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipEventSynchronize(e->ln->ws_free));  // (the lane's last encode may have run on another stream)
-    if (e->ln->ws) {
-        HIP_TRY(hipFree(e->ln->ws));
-        e->ln->ws = nullptr;
-        e->ln->ws_bytes = 0;
+    HIP_TRY(hipEventSynchronize(lane.ws_free));  // (the lane's last encode may have run on another stream)
+    if (lane.ws) {
+        HIP_TRY(hipFree(lane.ws));
+        lane.ws = nullptr;
+        lane.ws_bytes = 0;
     }
-    hipError_t err = hipMalloc(&e->ln->ws, bytes);
+    hipError_t err = hipMalloc(&lane.ws, bytes);
     if (err != hipSuccess) {
         (void)hipGetLastError();  // clear it: the launch checks (hipGetLastError) must not see this failure
-        e->ln->ws = nullptr;
+        lane.ws = nullptr;
         return set_err(err == hipErrorOutOfMemory ? MIMI_ERR_OUT_OF_MEMORY : MIMI_ERR_HIP,
                        "workspace hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(err));
     }
-    e->ln->ws_bytes = bytes;
-    ++e->ln->ws_gen;  // captured graphs address the old workspace
+    lane.ws_bytes = bytes;
+    ++lane.ws_gen;  // captured graphs address the old workspace
     return MIMI_OK;
 }
 
@@ -1336,8 +1331,29 @@ static const char* ln_kname(int rpw) {
     }
 }
 
-static int run_rvq(mimi_engine* e, const float* proj, int64_t frames, int K, int32_t* codes, int frames_per_item,
-                   void* work, hipStream_t s, Recorder& rec, const int* flen = nullptr, double valid_share = 1.0) {
+// What an encode pass runs in and how: filled by the caller of the pass, read by everything the pass calls.  Nothing a
+// pass needs about its lane, stream or mode lives on the engine, so passes in different lanes share no such state.
+struct PassCtx {
+    mimi_engine::Lane& lane;  // its workspace, ws_free, maxima buffers and io_dev
+    hipStream_t s;
+    int prec;
+    const RaggedTable* rg = nullptr;  // a ragged batch: its length table ...
+    const int* rg_pinned = nullptr;   // ... and the table's pinned host image, alive until the encode is waited
+    bool capturing = false;    // inside capture_graph's stream capture: audio / codes through io_dev, no event calls
+    bool chain_ok = false;     // the persistent RVQ chain may run: the caller reads its give-up flag back
+    bool calibrating = false;  // calibrate_scales' pass: new tensor names are expected, every range check stays on
+};
+
+// What a pass hands back to its caller.
+struct PassOut {
+    unsigned* chain_flag = nullptr;  // the give-up flag word of the RVQ chain it launched (null: no chain ran)
+    size_t chain_clear = 0;          // (capture) bytes from chain_flag that each replay zeroes first
+    bool uncalibrated = false;       // it named a plane tensor the calibration did not see
+};
+
+static int run_rvq(mimi_engine* e, const PassCtx& ctx, const float* proj, int64_t frames, int K, int32_t* codes,
+                   int frames_per_item, void* work, Recorder& rec, PassOut* out, const int* flen = nullptr,
+                   double valid_share = 1.0) {
     RvqArgs r{};
     r.flen = flen;
     r.work = work;
@@ -1354,33 +1370,41 @@ static int run_rvq(mimi_engine* e, const float* proj, int64_t frames, int K, int
     r.cb_unscale = e->cb_unscale;
     r.cb_emax = e->cb_emax;
     r.codes = codes;
-    r.codes_ref = e->capturing ? reinterpret_cast<int32_t* const*>(e->ln->io_dev + 1) : nullptr;
+    r.codes_ref = ctx.capturing ? reinterpret_cast<int32_t* const*>(ctx.lane.io_dev + 1) : nullptr;
     r.frames_per_item = frames_per_item;
     r.form = e->rvq_form;
     r.chain = e->rvq_chain;
     r.chain_fault = e->rvq_chain_fault;
     r.xcd_group_ok = e->rvq_xcd;
     const char* kname = "?";
-    unsigned* cflag = nullptr;
-    e->chain_flag = nullptr;
-    size_t clear = 0;  // (capturing: the replay's set_io_kernel zeroes the chain's words instead of a memset node)
-    LAUNCH_TRY(launch_rvq(r, s, &kname, e->chain_ok ? &cflag : nullptr, e->capturing ? &clear : nullptr), "rvq");
-    e->chain_flag = cflag;
-    if (e->capturing) e->cap_chain_clear = cflag ? clear : 0;
+    out->chain_flag = nullptr;
+    out->chain_clear = 0;  // (capturing: the replay's set_io_kernel zeroes the chain's words instead of a memset node)
+    LAUNCH_TRY(launch_rvq(r, ctx.s, &kname, ctx.chain_ok ? &out->chain_flag : nullptr,
+                          ctx.capturing ? &out->chain_clear : nullptr),
+               "rvq");
     rec.mark("rvq", 2.0 * frames * valid_share * r.D * r.ncodes * K,
              (double)frames * (2 * r.D) * 4 + (double)frames * K * 4, kname);
     return MIMI_OK;
 }
 
-// One pass of the whole encode at precision prec.
-static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int K, int32_t* codes, hipStream_t s,
-                       int prec, const RaggedTable* rg = nullptr, const int* rg_pinned = nullptr) {
+// One pass of the whole encode at precision ctx.prec, behind the lane's last encode.  On fp16 planes it zeroes the
+// lane's maxima first, and a tensor without a calibrated scale is an error of this encode only (its name is known
+// from here on).  Inside a capture only the stages are legal: the replay waits outside its graph and needs no reset
+// node (capture_graph), which reads out->uncalibrated itself.
+static int encode_pass(mimi_engine* e, const PassCtx& ctx, const float* audio, int B, int64_t L, int K, int32_t* codes,
+                       PassOut* out = nullptr) {
     const mimi_config& c = e->cfg;
     const StagePlan p = plan_lengths(c, L);
+    hipStream_t s = ctx.s;
+    const int prec = ctx.prec;
+    const RaggedTable* rg = ctx.rg;
+    PassOut unread;
+    if (!out) out = &unread;
+    *out = PassOut{};
     Workspace w{};
-    int rc = ensure_ws(e, ws_layout(e, B, p, nullptr, prec, rg != nullptr), s);
+    int rc = ensure_ws(ctx.lane, ws_layout(e, B, p, prec, rg != nullptr), s);
     if (rc) return rc;
-    ws_layout(e, B, p, &w, prec, rg != nullptr);
+    ws_layout(e, B, p, prec, rg != nullptr, &w, ctx.lane.ws);
     if ((rc = ensure_rope(e, p.frames25))) return rc;
     const int ns = act_planes(e, p, prec);  // 0: fp32 activations; 2/3: plane-format GEMM inputs
     // fp16 planes: each plane-format tensor takes the next activation-scale slot (launch order)
@@ -1399,20 +1423,20 @@ static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int
         if (it != e->slot_of.end()) {
             slot = it->second;
         } else {
-            if (!e->calibrating) e->uncalibrated_slot = true;
+            if (!ctx.calibrating) out->uncalibrated = true;
             if ((int)e->slot_of.size() >= kMaxActSlots) return a;
             slot = (int)e->slot_of.size();
             e->slot_of[name] = slot;
             e->act_scale.resize(slot + 1, 1.0f);
         }
         a.scale = e->act_scale[slot];
-        a.amax = e->ln->amax_dev + (size_t)slot * AMAX_SLOT_WORDS;
+        a.amax = ctx.lane.amax_dev + (size_t)slot * AMAX_SLOT_WORDS;
         return a;
     };
     // a LayerNorm output whose bound (DevXfmr::ln*_bound) times its scale stays under half the fp16 plane limit
     // (2^15) needs no range check (calibration still records its maximum: it sets the scale)
     auto ln_check_free = [&](const Act& a, float bound) {
-        return MIMI_LN_CHECK_SKIP && !e->calibrating && a.amax && a.scale > 0.0f && bound * a.scale < 16384.0f;
+        return MIMI_LN_CHECK_SKIP && !ctx.calibrating && a.amax && a.scale > 0.0f && bound * a.scale < 16384.0f;
     };
     // fp16 weight planes + 1 / (activation scale x weight scale) for a GEMM reading plane tensor `in`
     auto use_h = [&](GemmArgs& a, const void* wh, float wscale, const Act& in) {
@@ -1426,15 +1450,19 @@ static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int
     };
     Recorder rec{e, s};
     const char* kname = "?";
-    if (!e->capturing) HIP_TRY(hipStreamWaitEvent(s, e->ln->ws_free, 0));  // (a replay waits outside the graph)
+    if (!ctx.capturing) {
+        // (the lane's last encode may have run on another stream, and the maxima buffers are part of its workspace)
+        HIP_TRY(hipStreamWaitEvent(s, ctx.lane.ws_free, 0));
+        if (h16) HIP_TRY(hipMemsetAsync(ctx.lane.amax_dev, 0, (size_t)kMaxActSlots * AMAX_SLOT_WORDS * sizeof(unsigned), s));
+    }
     // ragged batches: the length table (pinned host image, alive until the encode is waited) -> workspace
     const int* dT[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     const int *dT25 = nullptr, *dF = nullptr;
     const unsigned *dst0 = nullptr, *dst1 = nullptr;
     const int *dToff = nullptr, *dRpos = nullptr;  // the transformer section's packed rows (RaggedTable)
     if (rg) {
-        if (!rg_pinned || rg->B != B || !w.rg) return set_err(MIMI_ERR_STATE, "ragged encode without its length table");
-        HIP_TRY(hipMemcpyAsync(w.rg, rg_pinned, RaggedTable::ints(B) * sizeof(int), hipMemcpyHostToDevice, s));
+        if (!ctx.rg_pinned || rg->B != B || !w.rg) return set_err(MIMI_ERR_STATE, "ragged encode without its length table");
+        HIP_TRY(hipMemcpyAsync(w.rg, ctx.rg_pinned, RaggedTable::ints(B) * sizeof(int), hipMemcpyHostToDevice, s));
         for (int st = 0; st < 5; ++st) dT[st] = w.rg + st * B;
         dT25 = w.rg + 5 * B;
         dF = w.rg + 6 * B;
@@ -1477,7 +1505,7 @@ static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int
             ra.x = w.x;
             if (si == 0) {
                 ra.audio = audio;
-                ra.audio_ref = e->capturing ? const_cast<const float* const*>(reinterpret_cast<float**>(e->ln->io_dev)) : nullptr;
+                ra.audio_ref = ctx.capturing ? const_cast<const float* const*>(reinterpret_cast<float**>(ctx.lane.io_dev)) : nullptr;
                 ra.w0 = e->conv0.w;
                 ra.b0 = e->conv0.b;
                 ra.w3frag = e->res3[0].wfrag;
@@ -1854,8 +1882,11 @@ static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int
     LAUNCH_TRY(launch_gemm(ROLE_INPROJ, ap, s, &kname, ds_planes ? PREC_F16X3 : PREC_F32), "input_proj");
     rec.mark("input_proj", gemm_flops(ap) * rF, gemm_bytes(ap, false), kname);
     if ((rc = save_tap(e, "proj", w.proj, B, T2, 2 * Dq, s))) return rc;
-    if ((rc = run_rvq(e, w.proj, (int64_t)B * T2, K, codes, (int)T2, w.rvq, s, rec, rg ? dF : nullptr, rF))) return rc;
-    if (!e->capturing) HIP_TRY(hipEventRecord(e->ln->ws_free, s));
+    if ((rc = run_rvq(e, ctx, w.proj, (int64_t)B * T2, K, codes, (int)T2, w.rvq, rec, out, rg ? dF : nullptr, rF)))
+        return rc;
+    if (ctx.capturing) return MIMI_OK;
+    HIP_TRY(hipEventRecord(ctx.lane.ws_free, s));
+    if (out->uncalibrated) return set_err(MIMI_ERR_STATE, "f16x3: an activation has no calibrated scale");
     return MIMI_OK;
 }
 
@@ -1872,43 +1903,42 @@ static int encode_pass(mimi_engine* e, const float* audio, int B, int64_t L, int
 // absolute error stays <= 2^-25 / s = 2^-32..2^-33 of the calibration maximum.
 constexpr float kF16Overflow = 32768.0f;  // a s >= 2^15: x s may round to an fp16 infinity
 
-// folds and reads back the per-slot maxima of the last pass (synchronises s)
-static int read_amax(mimi_engine* e, hipStream_t s, int* n) {
+// folds and reads back the per-slot maxima of the lane's last pass (synchronises s)
+static int read_amax(mimi_engine* e, mimi_engine::Lane& lane, hipStream_t s, int* n) {
     const int ns = (int)e->slot_of.size();
     *n = ns;
     if (ns == 0) return MIMI_OK;
-    LAUNCH_TRY(launch_amax_reduce(e->ln->amax_dev, ns, e->ln->amax_red, s), "amax_reduce");
-    HIP_TRY(hipMemcpyAsync(e->amax_host, e->ln->amax_red, ns * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    LAUNCH_TRY(launch_amax_reduce(lane.amax_dev, ns, lane.amax_red, s), "amax_reduce");
+    HIP_TRY(hipMemcpyAsync(e->amax_host, lane.amax_red, ns * sizeof(unsigned), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return MIMI_OK;
 }
 
-static float slot_amax(const mimi_engine* e, int i) {
+static float amax_word(const unsigned* amax, int i) {
     float a;
-    std::memcpy(&a, &e->amax_host[i], 4);
+    std::memcpy(&a, &amax[i], 4);
     return a;
 }
 
-// one f16x3 pass and its overflow check.  Non-finite maxima are not overflows of the scale: they come from a
-// non-finite input, which the reference propagates too.
-static int f16_pass(mimi_engine* e, const float* audio, int B, int64_t L, int K, int32_t* codes, hipStream_t s,
-                    bool* overflow) {
-    *overflow = false;
-    HIP_TRY(hipStreamWaitEvent(s, e->ln->ws_free, 0));  // encodes enqueued on other streams use amax_dev too
-    HIP_TRY(hipMemsetAsync(e->ln->amax_dev, 0, (size_t)kMaxActSlots * AMAX_SLOT_WORDS * sizeof(unsigned), s));
-    e->uncalibrated_slot = false;
-    int rc = encode_pass(e, audio, B, L, K, codes, s, PREC_F16X3);
-    if (rc) return rc;
-    if (e->uncalibrated_slot) {
-        e->uncalibrated_slot = false;
-        return set_err(MIMI_ERR_STATE, "f16x3: an activation has no calibrated scale");
-    }
-    int n = 0;
-    if ((rc = read_amax(e, s, &n))) return rc;
+// Whether any of n per-tensor maxima overflows its scale.  Non-finite maxima are not overflows of the scale: they
+// come from a non-finite input, which the reference propagates too.
+static bool f16_overflow(const unsigned* amax, int n, const std::vector<float>& act_scale) {
     for (int i = 0; i < n; ++i) {
-        const float a = slot_amax(e, i);
-        if (std::isfinite(a) && a * e->act_scale[i] >= kF16Overflow) *overflow = true;
+        const float a = amax_word(amax, i);
+        if (std::isfinite(a) && a * act_scale[i] >= kF16Overflow) return true;
     }
+    return false;
+}
+
+// one f16x3 pass and its overflow check
+static int f16_pass(mimi_engine* e, mimi_engine::Lane& lane, hipStream_t s, const float* audio, int B, int64_t L,
+                    int K, int32_t* codes, bool* overflow) {
+    *overflow = false;
+    int rc = encode_pass(e, PassCtx{lane, s, PREC_F16X3}, audio, B, L, K, codes);
+    if (rc) return rc;
+    int n = 0;
+    if ((rc = read_amax(e, lane, s, &n))) return rc;
+    *overflow = f16_overflow(e->amax_host, n, e->act_scale);
     return MIMI_OK;
 }
 
@@ -1953,17 +1983,14 @@ static int calibrate_scales(mimi_engine* e) {
     } else if (hipMemcpy(d_audio, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         rc = set_err(MIMI_ERR_HIP, "calibration upload");
     }
-    e->calibrating = true;
+    PassCtx ctx{e->lanes[0], s, PREC_F16X3};
+    ctx.calibrating = true;
     for (int it = 0; rc == MIMI_OK && it < 8; ++it) {
-        if (hipMemsetAsync(e->ln->amax_dev, 0, (size_t)kMaxActSlots * AMAX_SLOT_WORDS * sizeof(unsigned), s) != hipSuccess) {
-            rc = set_err(MIMI_ERR_HIP, "calibration memset");
-            break;
-        }
         int n = 0;
-        if ((rc = encode_pass(e, d_audio, B, L, K, d_codes, s, PREC_F16X3)) || (rc = read_amax(e, s, &n))) break;
+        if ((rc = encode_pass(e, ctx, d_audio, B, L, K, d_codes)) || (rc = read_amax(e, ctx.lane, s, &n))) break;
         bool changed = false;
         for (int i = 0; i < n; ++i) {
-            const float a = slot_amax(e, i);
+            const float a = amax_word(e->amax_host, i);
             if (!(a > 0.0f) || !std::isfinite(a)) continue;
             const float as = a * e->act_scale[i];
             if (as < 64.0f || as >= 512.0f) {  // hysteresis band around the [2^7, 2^8) target
@@ -1973,8 +2000,6 @@ static int calibrate_scales(mimi_engine* e) {
         }
         if (!changed) break;
     }
-    e->calibrating = false;
-    e->uncalibrated_slot = false;
     if (rc == MIMI_OK) e->calibrated = true;
     (void)hipStreamSynchronize(s);
     if (d_audio) (void)hipFree(d_audio);
@@ -1983,32 +2008,42 @@ static int calibrate_scales(mimi_engine* e) {
     return rc;
 }
 
+// e->item_codes with room for one item's `per` codes (synchronises s before it grows)
+static int ensure_item_codes(mimi_engine* e, size_t per, hipStream_t s) {
+    if (e->item_codes_cap >= per) return MIMI_OK;
+    HIP_TRY(hipStreamSynchronize(s));
+    if (e->item_codes) HIP_TRY(hipFree(e->item_codes));
+    e->item_codes = nullptr;
+    e->item_codes_cap = 0;
+    HIP_TRY(hipMalloc(&e->item_codes, per * sizeof(int32_t)));
+    e->item_codes_cap = per;
+    return MIMI_OK;
+}
+
+// One item alone at length L into e->item_codes: the f16x3 pass, then bf16x6 if the item overflows alone (*ovf).
+static int encode_item(mimi_engine* e, mimi_engine::Lane& lane, hipStream_t s, const float* audio, int64_t L, int K,
+                       bool* ovf) {
+    const int rc = f16_pass(e, lane, s, audio, 1, L, K, e->item_codes, ovf);
+    if (rc || !*ovf) return rc;
+    return encode_pass(e, PassCtx{lane, s, PREC_BF16X6}, audio, 1, L, K, e->item_codes);
+}
+
 // Per-item overflow fallback of one f16x3 encode (see "activation scales"): every item re-encoded alone at the
 // same padded length, in bf16x6 where it overflows alone.  Synchronises s.
-static int overflow_fallback(mimi_engine* e, const float* audio, int B, int64_t L, int K, int32_t* codes,
-                             hipStream_t s) {
-    ++e->f16_reruns;
-    const StagePlan p = plan_lengths(e->cfg, L);
+static int overflow_fallback(mimi_engine* e, mimi_engine::Lane& lane, hipStream_t s, const float* audio, int B,
+                             int64_t L, int K, int32_t* codes) {
+    ++e->f16_reruns;  // (once per encode, however many of its items overflow alone)
     int rc;
-    if (B == 1) {
-        if ((rc = encode_pass(e, audio, 1, L, K, codes, s, PREC_BF16X6))) return rc;
+    if (B == 1) {  // the item was alone already
+        if ((rc = encode_pass(e, PassCtx{lane, s, PREC_BF16X6}, audio, 1, L, K, codes))) return rc;
         HIP_TRY(hipStreamSynchronize(s));
         return MIMI_OK;
     }
-    const size_t per = (size_t)K * p.frames12;
-    if (e->item_codes_cap < per) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (e->item_codes) HIP_TRY(hipFree(e->item_codes));
-        e->item_codes = nullptr;
-        e->item_codes_cap = 0;
-        HIP_TRY(hipMalloc(&e->item_codes, per * sizeof(int32_t)));
-        e->item_codes_cap = per;
-    }
+    const size_t per = (size_t)K * plan_lengths(e->cfg, L).frames12;
+    if ((rc = ensure_item_codes(e, per, s))) return rc;
     bool ovf = false;
     for (int b = 0; b < B; ++b) {
-        const float* ab = audio + (int64_t)b * L;
-        if ((rc = f16_pass(e, ab, 1, L, K, e->item_codes, s, &ovf))) return rc;
-        if (ovf && (rc = encode_pass(e, ab, 1, L, K, e->item_codes, s, PREC_BF16X6))) return rc;
+        if ((rc = encode_item(e, lane, s, audio + (int64_t)b * L, L, K, &ovf))) return rc;
         HIP_TRY(hipMemcpyAsync(codes + b * per, e->item_codes, per * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
@@ -2019,30 +2054,20 @@ static int overflow_fallback(mimi_engine* e, const float* audio, int B, int64_t 
 // overflow fallback of a ragged encode, and the whole ragged encode where the batched form does not apply
 // (precision modes other than f16x3, clips too long for the plane buffers).  Item b's codes go to
 // codes[b][k][0 .. F_b) of the [B][K][Fmax] output.  Synchronises s.
-static int ragged_item_by_item(mimi_engine* e, const float* audio, int B, int64_t L, const int64_t* lens, int K,
-                               int32_t* codes, hipStream_t s, int prec) {
+static int ragged_item_by_item(mimi_engine* e, mimi_engine::Lane& lane, hipStream_t s, const float* audio, int B,
+                               int64_t L, const int64_t* lens, int K, int32_t* codes, int prec) {
     const int64_t Fmax = plan_lengths(e->cfg, L).frames12;
-    const size_t per = (size_t)K * Fmax;
-    if (e->item_codes_cap < per) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (e->item_codes) HIP_TRY(hipFree(e->item_codes));
-        e->item_codes = nullptr;
-        e->item_codes_cap = 0;
-        HIP_TRY(hipMalloc(&e->item_codes, per * sizeof(int32_t)));
-        e->item_codes_cap = per;
-    }
-    int rc;
+    int rc = ensure_item_codes(e, (size_t)K * Fmax, s);
+    if (rc) return rc;
     for (int b = 0; b < B; ++b) {
         const float* ab = audio + (int64_t)b * L;
         const int64_t Fb = plan_lengths(e->cfg, lens[b]).frames12;
         if (prec == PREC_F16X3 && act_planes(e, plan_lengths(e->cfg, lens[b]), prec) == 2) {
             bool ovf = false;
-            if ((rc = f16_pass(e, ab, 1, lens[b], K, e->item_codes, s, &ovf))) return rc;
-            if (ovf) {
-                ++e->f16_reruns;
-                if ((rc = encode_pass(e, ab, 1, lens[b], K, e->item_codes, s, PREC_BF16X6))) return rc;
-            }
-        } else if ((rc = encode_pass(e, ab, 1, lens[b], K, e->item_codes, s, prec))) {
+            rc = encode_item(e, lane, s, ab, lens[b], K, &ovf);
+            if (ovf) ++e->f16_reruns;  // (once per item that overflows alone)
+            if (rc) return rc;
+        } else if ((rc = encode_pass(e, PassCtx{lane, s, prec}, ab, 1, lens[b], K, e->item_codes))) {
             return rc;
         }
         HIP_TRY(hipMemcpy2DAsync(codes + (int64_t)b * K * Fmax, Fmax * sizeof(int32_t), e->item_codes,
@@ -2078,11 +2103,11 @@ static void drop_graphs(mimi_engine* e, bool clear_seen = false) {
 
 // Captures the f16x3 pass of (B, L, K) into a new graph.  On any failure the capture is abandoned and the
 // caller runs the eager pass (the error is cleared: a graph is an optimisation, never a requirement).
-static mimi_engine::Graph* capture_graph(mimi_engine* e, const float* audio, int B, int64_t L, int K,
-                                          int32_t* codes) {
-    if (!e->ln->io_dev && hipMalloc(&e->ln->io_dev, 4 * sizeof(void*)) != hipSuccess) {
+static mimi_engine::Graph* capture_graph(mimi_engine* e, mimi_engine::Lane& lane, const float* audio, int B,
+                                          int64_t L, int K, int32_t* codes) {
+    if (!lane.io_dev && hipMalloc(&lane.io_dev, 4 * sizeof(void*)) != hipSuccess) {
         (void)hipGetLastError();
-        e->ln->io_dev = nullptr;
+        lane.io_dev = nullptr;
         return nullptr;
     }
     if (!e->cap_stream && hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking) != hipSuccess) {
@@ -2095,66 +2120,64 @@ static mimi_engine::Graph* capture_graph(mimi_engine* e, const float* audio, int
         (void)hipGetLastError();
         return nullptr;
     }
-    e->capturing = true;
-    e->cap_chain_clear = 0;
-    e->uncalibrated_slot = false;
-    int rc = MIMI_OK;
+    PassCtx ctx{lane, cs, PREC_F16X3};
+    ctx.capturing = true;
+    ctx.chain_ok = true;  // (the submitter reads the flag back through the ticket, as after an eager pass)
+    PassOut out;
     // (no maxima reset node: amax_reduce_kernel leaves every sub-slot at 0 as it reads it, so a replay starts
     // from the zeros the previous encode's fold left behind)
-    rc = encode_pass(e, audio, B, L, K, codes, cs, PREC_F16X3);
+    int rc = encode_pass(e, ctx, audio, B, L, K, codes, &out);
     // (+ the ticket's host words from inside the graph: destinations through io_dev, set before each replay)
-    if (!rc && launch_amax_reduce(e->ln->amax_dev, (int)e->slot_of.size(), e->ln->amax_red, cs, nullptr, e->chain_flag, nullptr,
-                                  e->ln->io_dev) != hipSuccess)
+    if (!rc && launch_amax_reduce(lane.amax_dev, (int)e->slot_of.size(), lane.amax_red, cs, nullptr, out.chain_flag,
+                                  nullptr, lane.io_dev) != hipSuccess)
         rc = MIMI_ERR_HIP;
-    e->capturing = false;
     hipGraph_t g = nullptr;
     const hipError_t ec = hipStreamEndCapture(cs, &g);
     hipGraphExec_t x = nullptr;
-    if (rc || ec != hipSuccess || !g || e->uncalibrated_slot || hipGraphInstantiate(&x, g, nullptr, nullptr, 0) != hipSuccess) {
+    if (rc || ec != hipSuccess || !g || out.uncalibrated || hipGraphInstantiate(&x, g, nullptr, nullptr, 0) != hipSuccess) {
         (void)hipGetLastError();
-        e->uncalibrated_slot = false;
         if (g) (void)hipGraphDestroy(g);
         return nullptr;
     }
-    if ((int)e->ln->graphs.size() >= mimi_engine::kMaxGraphs) {  // evict the least recently used
+    if ((int)lane.graphs.size() >= mimi_engine::kMaxGraphs) {  // evict the least recently used
         size_t lru = 0;
-        for (size_t i = 1; i < e->ln->graphs.size(); ++i)
-            if (e->ln->graphs[i].used < e->ln->graphs[lru].used) lru = i;
-        destroy_graph(e->ln->graphs[lru]);
-        e->ln->graphs.erase(e->ln->graphs.begin() + (long)lru);
+        for (size_t i = 1; i < lane.graphs.size(); ++i)
+            if (lane.graphs[i].used < lane.graphs[lru].used) lru = i;
+        destroy_graph(lane.graphs[lru]);
+        lane.graphs.erase(lane.graphs.begin() + (long)lru);
     }
     mimi_engine::Graph ng;
     ng.B = B;
     ng.L = L;
     ng.K = K;
-    ng.ws_gen = e->ln->ws_gen;
+    ng.ws_gen = lane.ws_gen;
     ng.rope_gen = e->rope_gen;
     ng.g = g;
     ng.x = x;
-    ng.chain_flag = e->chain_flag;
-    ng.chain_clear = e->chain_flag ? e->cap_chain_clear : 0;
-    e->ln->graphs.push_back(ng);
+    ng.chain_flag = out.chain_flag;
+    ng.chain_clear = out.chain_clear;
+    lane.graphs.push_back(ng);
     ++e->graph_captures;
-    return &e->ln->graphs.back();
+    return &lane.graphs.back();
 }
 
-// Runs the f16x3 pass of (B, L, K) as a graph replay on s when it can (*replayed = true); otherwise leaves
+// Runs the f16x3 pass of (B, L, K) as a graph replay on s when it can (*replayed: the graph); otherwise leaves
 // everything to the eager path.
-static int graph_encode(mimi_engine* e, const float* audio, int B, int64_t L, int K, int32_t* codes, hipStream_t s,
-                        bool* replayed, unsigned** chain_flag, unsigned* host_amax, unsigned* host_flag) {
-    *replayed = false;
-    *chain_flag = nullptr;
-    if (!e->graphs_enabled || e->profiling || e->taps || e->calibrating) return MIMI_OK;
+static int graph_encode(mimi_engine* e, mimi_engine::Lane& lane, const float* audio, int B, int64_t L, int K,
+                        int32_t* codes, hipStream_t s, mimi_engine::Graph** replayed, unsigned* host_amax,
+                        unsigned* host_flag) {
+    *replayed = nullptr;
+    if (!e->graphs_enabled || e->profiling || e->taps) return MIMI_OK;
     // sizes first: nothing may be allocated inside a capture, and a reallocation retires the graphs
     const StagePlan p = plan_lengths(e->cfg, L);
-    int rc = ensure_ws(e, ws_layout(e, B, p, nullptr, PREC_F16X3), s);
+    int rc = ensure_ws(lane, ws_layout(e, B, p, PREC_F16X3), s);
     if (rc) return rc;
     if ((rc = ensure_rope(e, p.frames25))) return rc;
     mimi_engine::Graph* gr = nullptr;
-    for (auto it = e->ln->graphs.begin(); it != e->ln->graphs.end();) {
-        if (it->ws_gen != e->ln->ws_gen || it->rope_gen != e->rope_gen) {
+    for (auto it = lane.graphs.begin(); it != lane.graphs.end();) {
+        if (it->ws_gen != lane.ws_gen || it->rope_gen != e->rope_gen) {
             destroy_graph(*it);
-            it = e->ln->graphs.erase(it);
+            it = lane.graphs.erase(it);
             continue;
         }
         if (it->B == B && it->L == L && it->K == K) gr = &*it;
@@ -2162,22 +2185,21 @@ static int graph_encode(mimi_engine* e, const float* audio, int B, int64_t L, in
     }
     if (!gr) {
         const auto key = std::make_tuple(B, L, K);
-        if (e->ln->graph_seen.size() > 256) e->ln->graph_seen.clear();
-        if (++e->ln->graph_seen[key] < 2) return MIMI_OK;  // a shape seen once runs eagerly
-        gr = capture_graph(e, audio, B, L, K, codes);
+        if (lane.graph_seen.size() > 256) lane.graph_seen.clear();
+        if (++lane.graph_seen[key] < 2) return MIMI_OK;  // a shape seen once runs eagerly
+        gr = capture_graph(e, lane, audio, B, L, K, codes);
         if (!gr) {
             e->graphs_enabled = false;  // capture unsupported here: stay eager from now on
             return MIMI_OK;
         }
     }
     gr->used = ++e->graph_clock;
-    HIP_TRY(hipStreamWaitEvent(s, e->ln->ws_free, 0));
-    LAUNCH_TRY(launch_set_io(e->ln->io_dev, audio, codes, s, host_amax, host_flag, gr->chain_flag, gr->chain_clear),
+    HIP_TRY(hipStreamWaitEvent(s, lane.ws_free, 0));
+    LAUNCH_TRY(launch_set_io(lane.io_dev, audio, codes, s, host_amax, host_flag, gr->chain_flag, gr->chain_clear),
                "set_io");
     HIP_TRY(hipGraphLaunch(gr->x, s));
     ++e->graph_replays;
-    *replayed = true;
-    *chain_flag = gr->chain_flag;
+    *replayed = gr;
     return MIMI_OK;
 }
 
@@ -2222,20 +2244,8 @@ static int choose_lane(const mimi_engine* e) {
     return best;
 }
 
-// the active lane is lane 0 whenever no submission or wait is in progress
-struct LaneScope {
-    mimi_engine* e;
-    LaneScope(mimi_engine* x, int li) : e(x) { set(li); }
-    ~LaneScope() { set(0); }
-    void set(int li) { e->ln = &e->lanes[li]; }
-};
-
-// Enqueues one encode and returns its ticket without waiting: on its lane's stream behind the caller's stream s when
-// it takes a lane (may_lane and the "lanes" rule), else on s in lane 0.  In f16x3 the per-tensor maxima are folded
-// and copied to this ticket's pinned slot behind the encode; mimi_encode_wait checks them.
-static int encode_async_locked(mimi_engine* e, const float* audio, int B, int64_t L, int K, int32_t* codes,
-                               hipStream_t s, int64_t* ticket, const int64_t* lengths = nullptr,
-                               bool may_lane = false) {
+// A free ticket slot, with its event and pinned words (made on the slot's first use).
+static int claim_ticket(mimi_engine* e, mimi_engine::Pending** slot) {
     mimi_engine::Pending* P = nullptr;
     for (auto& q : e->pend)
         if (q.id == 0) {
@@ -2251,136 +2261,22 @@ static int encode_async_locked(mimi_engine* e, const float* audio, int B, int64_
     // a kernel of this encode writes it (amax_reduce skips its launch when there is nothing to reduce)
     P->chain_word[0] = 0u;
     P->chain = false;
-    const int prec = e->precision;
-    const bool h16 = prec == PREC_F16X3 && act_planes(e, plan_lengths(e->cfg, L), prec) == 2;
-    int rc;
-    int n = 0;
-    // Calibrate whenever f16x3 is on, not only when this batch's longest item gets planes: a ragged batch whose
-    // longest item is past the plane limit runs its short items through the planes path item by item.
-    if (prec == PREC_F16X3 && !e->calibrated && (rc = calibrate_scales(e))) return rc;
-    RaggedTable rt;
-    if (lengths) {
-        const mimi_config& c = e->cfg;
-        const bool batched = h16 && e->res0_h16 && e->res1_h16 && e->ds_fix && e->inproj_h &&
-                             c.downsample_kernel == 4 && c.downsample_stride == 2 && c.num_ratios >= 2;
-        if (!batched) {  // item by item, synchronously (the ticket's event is then already complete)
-            if ((rc = ragged_item_by_item(e, audio, B, L, lengths, K, codes, s, prec))) return rc;
-            HIP_TRY(hipEventRecord(P->done, s));
-            P->lane = 0;
-            ++e->lanes[0].tickets;
-            ++e->lanes[0].encodes;
-            e->lanes[0].excl = false;
-            P->nslots = 0;
-            P->h16 = false;
-            P->ragged = false;
-            P->audio = audio;
-            P->B = B;
-            P->L = L;
-            P->K = K;
-            P->codes = codes;
-            P->s = s;
-            P->claimed = false;
-            P->id = e->next_ticket++;
-            *ticket = P->id;
-            return MIMI_OK;
-        }
-        rt.B = B;
-        rt.len.assign(lengths, lengths + B);
-        rt.plan.resize(B);
-        for (int b = 0; b < B; ++b) rt.plan[b] = plan_lengths(c, lengths[b]);
-        rt.minT25 = rt.maxT25 = (int)rt.plan[0].frames25;
-        for (const auto& pb : rt.plan) {
-            rt.minT25 = std::min<int>(rt.minT25, (int)pb.frames25);
-            rt.maxT25 = std::max<int>(rt.maxT25, (int)pb.frames25);
-            rt.R += pb.frames25;
-        }
-        const size_t need = RaggedTable::ints(B) * sizeof(int);
-        if (P->rg_cap < need) {
-            if (P->rg_pinned) HIP_TRY(hipHostFree(P->rg_pinned));
-            P->rg_pinned = nullptr;
-            P->rg_cap = 0;
-            HIP_TRY(hipHostMalloc(&P->rg_pinned, need, hipHostMallocDefault));
-            P->rg_cap = need;
-        }
-        rt.fill(P->rg_pinned);
-    }
-    // ---- the lane.  By default only what gains: f16x3 uniform batches on the per-level RVQ kernels (large grids).
-    // The persistent RVQ chain's slice workgroups spin on their peers and need the whole grid resident; another lane's
-    // LDS-heavy kernels on the same CUs would push it into give-ups and re-runs, so an encode that may launch it stays on
-    // the caller's stream in lane 0 and runs with the other lane idle.  Taps, per-stage profiling and every caller that
-    // goes on using s behind the call (may_lane false) stay there too.
-    const int64_t rvq_frames = (int64_t)B * plan_lengths(e->cfg, L).frames12;
-    const bool chain_el = h16 && e->rvq_chain != 0 && (rvq_frames + 31) / 32 * 8 < 256;  // (launch_rvq's small grids)
-    bool laned = may_lane && e->lanes_opt > 0 && h16 && !e->taps && e->profiling != 1 &&
-                 (e->lanes_opt == 2 || (!lengths && !chain_el));
-    int li = laned ? choose_lane(e) : 0;
-    LaneScope lane_scope(e, li);
-    if (laned && !lane_prepare(e, li)) {
-        if (li != 0 && lane_prepare(e, 0)) {
-            lane_scope.set(li = 0);
-        } else {
-            laned = false;
-            lane_scope.set(li = 0);
-        }
-    }
-    if (laned && li != 0) {  // lane 1's workspace, on its first use and when it grows: never at the encode's cost
-        const size_t need = ws_layout(e, B, plan_lengths(e->cfg, L), nullptr, PREC_F16X3, lengths != nullptr);
-        if (ensure_ws(e, need, e->ln->stream) != MIMI_OK) {
-            (void)hipGetLastError();
-            lane_scope.set(li = 0);
-            if (!lane_prepare(e, 0)) laned = false;
-        }
-    }
-    mimi_engine::Lane& lane = *e->ln;
-    if (laned) {  // the whole encode on the lane's stream, behind everything enqueued on the caller's so far
-        HIP_TRY(hipEventRecord(lane.in_ready, s));
-        s = lane.stream;
-        HIP_TRY(hipStreamWaitEvent(s, lane.in_ready, 0));
-    }
-    // an encode that may hold the chain wants the GPU to itself: it waits for the other lane, and the other lane's next
-    // encode waits for it
-    const bool excl = chain_el && !laned && e->lanes_opt > 0;
-    for (auto& o : e->lanes)
-        if (&o != &lane && o.ws_free && (excl || o.excl)) HIP_TRY(hipStreamWaitEvent(s, o.ws_free, 0));
-    if (h16) {
-        bool replayed = false;
-        unsigned* cflag = nullptr;
-        struct ChainScope {  // the chain is allowed inside this pass only (its flag is read back below)
-            mimi_engine* e;
-            explicit ChainScope(mimi_engine* x) : e(x) { e->chain_ok = true; }
-            ~ChainScope() { e->chain_ok = false; }
-        } chain_scope(e);
-        if (!lengths &&
-            (rc = graph_encode(e, audio, B, L, K, codes, s, &replayed, &cflag, P->amax, P->chain_word)))
-            return rc;
-        n = (int)e->slot_of.size();
-        if (!replayed) {
-            HIP_TRY(hipStreamWaitEvent(s, e->ln->ws_free, 0));  // the maxima buffers are part of the workspace
-            HIP_TRY(hipMemsetAsync(e->ln->amax_dev, 0, (size_t)kMaxActSlots * AMAX_SLOT_WORDS * sizeof(unsigned), s));
-            e->uncalibrated_slot = false;
-            if ((rc = encode_pass(e, audio, B, L, K, codes, s, PREC_F16X3, lengths ? &rt : nullptr, P->rg_pinned)))
-                return rc;
-            if (e->uncalibrated_slot) {  // this encode only: the next one starts clean
-                e->uncalibrated_slot = false;
-                return set_err(MIMI_ERR_STATE, "f16x3: an activation has no calibrated scale");
-            }
-            cflag = e->chain_flag;
-            // the maxima and (chain) the give-up flag also into the ticket's pinned words, before ws_free (the next
-            // encode's memset node zeroes the flag); a replay's graph ends with the same kernel (capture_graph)
-            LAUNCH_TRY(launch_amax_reduce(e->ln->amax_dev, n, e->ln->amax_red, s, P->amax, cflag, cflag ? P->chain_word : nullptr),
-                       "amax_reduce");
-        }
-        P->chain = cflag != nullptr;
-        HIP_TRY(hipEventRecord(e->ln->ws_free, s));
-    } else if ((rc = encode_pass(e, audio, B, L, K, codes, s, prec))) {
-        return rc;
-    }
+    *slot = P;
+    return MIMI_OK;
+}
+
+// Makes P the ticket of the encode just enqueued on s in lane li (lengths: a ragged batch's, kept for the fallbacks
+// at the wait).
+static int issue_ticket(mimi_engine* e, mimi_engine::Pending* P, int li, bool excl, hipStream_t s, const float* audio,
+                        int B, int64_t L, int K, int32_t* codes, int nslots, bool h16, const int64_t* lengths,
+                        int64_t* ticket) {
     HIP_TRY(hipEventRecord(P->done, s));
+    mimi_engine::Lane& lane = e->lanes[li];
     P->lane = li;
     ++lane.tickets;
     ++lane.encodes;
     lane.excl = excl;
-    P->nslots = n;
+    P->nslots = nslots;
     P->h16 = h16;
     P->audio = audio;
     P->B = B;
@@ -2394,6 +2290,114 @@ static int encode_async_locked(mimi_engine* e, const float* audio, int B, int64_
     P->id = e->next_ticket++;
     *ticket = P->id;
     return MIMI_OK;
+}
+
+// The length table of a ragged batch, and its device image into the ticket's pinned buffer.
+static int fill_ragged(const mimi_config& c, const int64_t* lengths, int B, RaggedTable* rt, mimi_engine::Pending* P) {
+    rt->B = B;
+    rt->len.assign(lengths, lengths + B);
+    rt->plan.resize(B);
+    for (int b = 0; b < B; ++b) rt->plan[b] = plan_lengths(c, lengths[b]);
+    rt->minT25 = rt->maxT25 = (int)rt->plan[0].frames25;
+    for (const auto& pb : rt->plan) {
+        rt->minT25 = std::min<int>(rt->minT25, (int)pb.frames25);
+        rt->maxT25 = std::max<int>(rt->maxT25, (int)pb.frames25);
+        rt->R += pb.frames25;
+    }
+    const size_t need = RaggedTable::ints(B) * sizeof(int);
+    if (P->rg_cap < need) {
+        if (P->rg_pinned) HIP_TRY(hipHostFree(P->rg_pinned));
+        P->rg_pinned = nullptr;
+        P->rg_cap = 0;
+        HIP_TRY(hipHostMalloc(&P->rg_pinned, need, hipHostMallocDefault));
+        P->rg_cap = need;
+    }
+    rt->fill(P->rg_pinned);
+    return MIMI_OK;
+}
+
+// Enqueues one encode and returns its ticket without waiting: on its lane's stream behind the caller's stream s when
+// it takes a lane (may_lane and the "lanes" rule), else on s in lane 0.  In f16x3 the per-tensor maxima are folded
+// and copied to this ticket's pinned slot behind the encode; mimi_encode_wait checks them.
+static int encode_async_locked(mimi_engine* e, const float* audio, int B, int64_t L, int K, int32_t* codes,
+                               hipStream_t s, int64_t* ticket, const int64_t* lengths = nullptr,
+                               bool may_lane = false) {
+    mimi_engine::Pending* P = nullptr;
+    int rc = claim_ticket(e, &P);
+    if (rc) return rc;
+    const int prec = e->precision;
+    const bool h16 = prec == PREC_F16X3 && act_planes(e, plan_lengths(e->cfg, L), prec) == 2;
+    int n = 0;
+    // Calibrate whenever f16x3 is on, not only when this batch's longest item gets planes: a ragged batch whose
+    // longest item is past the plane limit runs its short items through the planes path item by item.
+    if (prec == PREC_F16X3 && !e->calibrated && (rc = calibrate_scales(e))) return rc;
+    RaggedTable rt;
+    if (lengths) {
+        const mimi_config& c = e->cfg;
+        const bool batched = h16 && e->res0_h16 && e->res1_h16 && e->ds_fix && e->inproj_h &&
+                             c.downsample_kernel == 4 && c.downsample_stride == 2 && c.num_ratios >= 2;
+        if (!batched) {  // item by item, synchronously (the ticket's event is then already complete)
+            if ((rc = ragged_item_by_item(e, e->lanes[0], s, audio, B, L, lengths, K, codes, prec))) return rc;
+            return issue_ticket(e, P, 0, false, s, audio, B, L, K, codes, 0, false, nullptr, ticket);
+        }
+        if ((rc = fill_ragged(c, lengths, B, &rt, P))) return rc;
+    }
+    // ---- the lane.  By default only what gains: f16x3 uniform batches on the per-level RVQ kernels (large grids).
+    // The persistent RVQ chain's slice workgroups spin on their peers and need the whole grid resident; another lane's
+    // LDS-heavy kernels on the same CUs would push it into give-ups and re-runs, so an encode that may launch it stays on
+    // the caller's stream in lane 0 and runs with the other lane idle.  Taps, per-stage profiling and every caller that
+    // goes on using s behind the call (may_lane false) stay there too.
+    const int64_t rvq_frames = (int64_t)B * plan_lengths(e->cfg, L).frames12;
+    const bool chain_el = h16 && e->rvq_chain != 0 && (rvq_frames + 31) / 32 * 8 < 256;  // (launch_rvq's small grids)
+    bool laned = may_lane && e->lanes_opt > 0 && h16 && !e->taps && e->profiling != 1 &&
+                 (e->lanes_opt == 2 || (!lengths && !chain_el));
+    int li = laned ? choose_lane(e) : 0;
+    if (laned && !lane_prepare(e, li)) {  // (without a stream for lane 0 either: on the caller's)
+        if (li == 0 || !lane_prepare(e, 0)) laned = false;
+        li = 0;
+    }
+    if (laned && li != 0) {  // lane 1's workspace, on its first use and when it grows: never at the encode's cost
+        const size_t need = ws_layout(e, B, plan_lengths(e->cfg, L), PREC_F16X3, lengths != nullptr);
+        if (ensure_ws(e->lanes[li], need, e->lanes[li].stream) != MIMI_OK) {
+            (void)hipGetLastError();
+            li = 0;
+            if (!lane_prepare(e, 0)) laned = false;
+        }
+    }
+    mimi_engine::Lane& lane = e->lanes[li];
+    if (laned) {  // the whole encode on the lane's stream, behind everything enqueued on the caller's so far
+        HIP_TRY(hipEventRecord(lane.in_ready, s));
+        s = lane.stream;
+        HIP_TRY(hipStreamWaitEvent(s, lane.in_ready, 0));
+    }
+    // an encode that may hold the chain wants the GPU to itself: it waits for the other lane, and the other lane's next
+    // encode waits for it
+    const bool excl = chain_el && !laned && e->lanes_opt > 0;
+    for (auto& o : e->lanes)
+        if (&o != &lane && o.ws_free && (excl || o.excl)) HIP_TRY(hipStreamWaitEvent(s, o.ws_free, 0));
+    if (h16) {
+        mimi_engine::Graph* replayed = nullptr;
+        if (!lengths && (rc = graph_encode(e, lane, audio, B, L, K, codes, s, &replayed, P->amax, P->chain_word)))
+            return rc;
+        unsigned* cflag = replayed ? replayed->chain_flag : nullptr;
+        n = (int)e->slot_of.size();
+        if (!replayed) {
+            PassCtx ctx{lane, s, PREC_F16X3, lengths ? &rt : nullptr, P->rg_pinned};
+            ctx.chain_ok = true;  // the chain is allowed inside this pass only (its flag is read back through the ticket)
+            PassOut out;
+            if ((rc = encode_pass(e, ctx, audio, B, L, K, codes, &out))) return rc;
+            cflag = out.chain_flag;
+            // the maxima and (chain) the give-up flag also into the ticket's pinned words, before ws_free (the next
+            // encode's memset node zeroes the flag); a replay's graph ends with the same kernel (capture_graph)
+            LAUNCH_TRY(launch_amax_reduce(lane.amax_dev, n, lane.amax_red, s, P->amax, cflag, cflag ? P->chain_word : nullptr),
+                       "amax_reduce");
+        }
+        P->chain = cflag != nullptr;
+        HIP_TRY(hipEventRecord(lane.ws_free, s));
+    } else if ((rc = encode_pass(e, PassCtx{lane, s, prec}, audio, B, L, K, codes))) {
+        return rc;
+    }
+    return issue_ticket(e, P, li, excl, s, audio, B, L, K, codes, n, h16, lengths, ticket);
 }
 
 // Waits for ticket's encode and runs its f16x3 overflow check.  The engine lock is NOT held while the host
@@ -2420,38 +2424,29 @@ static int encode_wait(mimi_engine* e, int64_t ticket) {
     bool ovf = false;
     const bool chain_gave_up = q.chain && se == hipSuccess && P->chain_word[0] != 0u;
     if (q.h16 && se == hipSuccess) {
-        e->last_amax.assign(q.nslots, 0.0f);
-        for (int i = 0; i < q.nslots; ++i) {
-            float a;
-            std::memcpy(&a, &P->amax[i], 4);
-            e->last_amax[i] = a;
-            if (std::isfinite(a) && a * e->act_scale[i] >= kF16Overflow) ovf = true;
-        }
+        e->last_amax.resize(q.nslots);
+        for (int i = 0; i < q.nslots; ++i) e->last_amax[i] = amax_word(P->amax, i);
+        ovf = f16_overflow(P->amax, q.nslots, e->act_scale);
     }
     P->claimed = false;
     P->id = 0;
-    --e->lanes[q.lane].tickets;
-    LaneScope lane_scope(e, q.lane);  // the re-runs below: on the encode's stream, in its lane's workspace
+    mimi_engine::Lane& lane = e->lanes[q.lane];  // the re-runs below: on the encode's stream, in its lane's workspace
+    --lane.tickets;
     if (se != hipSuccess)
         return set_err(se == hipErrorOutOfMemory ? MIMI_ERR_OUT_OF_MEMORY : MIMI_ERR_HIP, "hipEventSynchronize: %s",
                        hipGetErrorString(se));
-    if (chain_gave_up) {  // the persistent RVQ gave up (its codes are not kept): the whole encode again, without it
-        ++e->chain_reruns;
-        HIP_TRY(hipSetDevice(e->device));
-        if (q.ragged) return ragged_item_by_item(e, q.audio, q.B, q.L, q.lens.data(), q.K, q.codes, q.s, PREC_F16X3);
-        bool ovf2 = false;
-        int rc = f16_pass(e, q.audio, q.B, q.L, q.K, q.codes, q.s, &ovf2);
-        if (rc) return rc;
-        if (!ovf2) return MIMI_OK;
-        return overflow_fallback(e, q.audio, q.B, q.L, q.K, q.codes, q.s);
-    }
-    if (!ovf) return MIMI_OK;
+    if (!chain_gave_up && !ovf) return MIMI_OK;
     HIP_TRY(hipSetDevice(e->device));
+    if (chain_gave_up) ++e->chain_reruns;  // the persistent RVQ gave up (its codes are not kept)
     if (q.ragged) {  // each item alone at its own length (the ragged result's definition), bf16x6 if it overflows
-        ++e->f16_reruns;
-        return ragged_item_by_item(e, q.audio, q.B, q.L, q.lens.data(), q.K, q.codes, q.s, PREC_F16X3);
+        if (!chain_gave_up) ++e->f16_reruns;
+        return ragged_item_by_item(e, lane, q.s, q.audio, q.B, q.L, q.lens.data(), q.K, q.codes, PREC_F16X3);
     }
-    return overflow_fallback(e, q.audio, q.B, q.L, q.K, q.codes, q.s);
+    if (chain_gave_up) {  // the whole encode again, without the chain
+        const int rc = f16_pass(e, lane, q.s, q.audio, q.B, q.L, q.K, q.codes, &ovf);
+        if (rc || !ovf) return rc;
+    }
+    return overflow_fallback(e, lane, q.s, q.audio, q.B, q.L, q.K, q.codes);
 }
 
 static int check_encode_args(mimi_engine* e, const float* audio, int32_t batch, int64_t length, int32_t* K,
@@ -2663,31 +2658,33 @@ extern "C" int mimi_rvq_encode(mimi_engine* e, const float* emb, int64_t frames,
     const int Hd = e->cfg.hidden_size, Dq = e->cfg.vq_hidden_dim;
     const size_t projb = ((size_t)frames * 2 * Dq * sizeof(float) + 255) / 256 * 256;
     const size_t need = projb + rvq_work_bytes(frames);
-    int rc = ensure_ws(e, std::max(need, e->ln->ws_bytes), s);
+    mimi_engine::Lane& lane = e->lanes[0];  // it borrows lane 0's workspace, ordered by ws_free like an encode there
+    int rc = ensure_ws(lane, std::max(need, lane.ws_bytes), s);
     if (rc) return rc;
-    float* proj = reinterpret_cast<float*>(e->ln->ws);
-    HIP_TRY(hipStreamWaitEvent(s, e->ln->ws_free, 0));
+    float* proj = reinterpret_cast<float*>(lane.ws);
+    void* work = reinterpret_cast<char*>(lane.ws) + projb;
+    HIP_TRY(hipStreamWaitEvent(s, lane.ws_free, 0));
     Recorder rec{e, s};
     rec.begin();
     GemmArgs ap = linear_args(emb, frames, Hd, e->inproj, 2 * Dq, proj);
     const char* kname = "?";
     LAUNCH_TRY(launch_gemm(ROLE_INPROJ, ap, s, &kname), "input_proj");
     rec.mark("input_proj", 2.0 * frames * Hd * 2 * Dq, 0, kname);
-    e->chain_ok = true;  // (checked right here: a give-up re-runs the levels on the per-level kernels)
-    rc = run_rvq(e, proj, frames, K, codes, 0, reinterpret_cast<char*>(e->ln->ws) + projb, s, rec);
-    e->chain_ok = false;
-    if (rc) return rc;
-    if (e->chain_flag) {
+    PassCtx ctx{lane, s, e->precision};
+    ctx.chain_ok = true;  // (checked right here: a give-up re-runs the levels on the per-level kernels)
+    PassOut out;
+    if ((rc = run_rvq(e, ctx, proj, frames, K, codes, 0, work, rec, &out))) return rc;
+    if (out.chain_flag) {
         unsigned flag = 0;
-        HIP_TRY(hipMemcpyAsync(&flag, e->chain_flag, sizeof flag, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&flag, out.chain_flag, sizeof flag, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        e->chain_flag = nullptr;
         if (flag) {
             ++e->chain_reruns;
-            if ((rc = run_rvq(e, proj, frames, K, codes, 0, reinterpret_cast<char*>(e->ln->ws) + projb, s, rec))) return rc;
+            ctx.chain_ok = false;
+            if ((rc = run_rvq(e, ctx, proj, frames, K, codes, 0, work, rec, &out))) return rc;
         }
     }
-    HIP_TRY(hipEventRecord(e->ln->ws_free, s));
+    HIP_TRY(hipEventRecord(lane.ws_free, s));
     return MIMI_OK;
 }
 

@@ -2,6 +2,10 @@
 gpurun_out/<tag>_codes.npz with B = 32 x 10 s (K = 32), a ragged 17-item batch and a batch-1 clip, and every stage tap
 (sha-256 of the fp32 values, planes reconstructed) of a B = 32 x 1 s batch (the fused q/k/v + attention path) and a B = 2 x 3 s batch
 (the two-kernel path), so builds that must give the same bits can be compared file to file (tools/cmp_codes.py).
+Beside them the profiled launch sequence and records of one pass each of the three batches, and the engine's counters
+(f16_reruns, rvq_chain_reruns, graph_replays, graph_captures, lane_encodes) with every result of a fixed script on a
+fresh engine: three synchronous encodes of one shape (eager, capture, replay), four asynchronous ones kept two in flight,
+a ragged batch, the quantizer alone, and a loud clip and a loud pair that take the overflow fallback.
 
 `lib_codes.py <tag> decode` writes the decode path's entries instead: the uniform decode of B = 3 x T = 13 x K = 8 and of
 B = 2 x T = 129 x K = 1, the ragged decode of T = [13, 1, 129, 2, 64, 65, 5, 3] at K = 8 (an odd T, 1- to 3-frame items,
@@ -28,6 +32,55 @@ def tap_sha(m, t):
     return np.array([hashlib.sha256(a.tobytes()).hexdigest() + f" {a.shape}"])
 
 
+def text(rows):
+    return np.array([repr(r) for r in rows])
+
+
+def profiled(m, name, fn):
+    """One pass with per-stage profiling on: the launch sequence and the records (no times: they are not bits)."""
+    m.set_profiling(1)
+    m.profile_reset()
+    fn()
+    prof = m.profile_read()
+    out[f"{name}_sequence"] = text(m.profile_sequence())
+    out[f"{name}_records"] = text((k, v["kernel"], v["launches"], v["flops"], v["bytes"]) for k, v in prof.items())
+    m.set_profiling(0)
+    m.profile_reset()
+
+
+def counters_script():
+    m = MimiHipModel(synthetic.make_state_dict(seed=0), device="cuda:0")
+
+    def clip(B, L, seed):
+        return torch.from_numpy(synthetic.clip_batch(B, L, seed=seed)).cuda()
+
+    x = clip(2, 24000, 510)  # (a small grid: the persistent RVQ chain, also inside the captured graph)
+    for i in range(3):
+        out[f"script_sync{i}"] = m.encode_int32(x, 8).cpu().numpy()
+    fly = []
+    for i in range(4):  # (large grids: the per-level RVQ kernels, so both lanes take encodes)
+        fly.append(m.encode_async(clip(32, 72000, 520 + i), 8))
+        if len(fly) == 2:
+            out[f"script_async{i - 1}"] = fly.pop(0).wait().cpu().numpy()
+    out["script_async3"] = fly.pop(0).wait().cpu().numpy()
+    lens = [48000, 1, 13441, 24000, 30001]
+    xr = np.zeros((len(lens), max(lens)), np.float32)
+    for i, n in enumerate(lens):
+        xr[i, :n] = synthetic.speech_like(n, 530, i)
+    out["script_ragged"] = m.encode_ragged(torch.from_numpy(xr).cuda(), lens, 8).cpu().numpy()
+    emb = torch.from_numpy(np.random.default_rng(540).standard_normal((1, 512, 13)).astype(np.float32)).cuda()
+    out["script_quantize"] = m.quantize(emb, 8).cpu().numpy()
+    loud = synthetic.speech_like(48000, 5, 1) * np.float32(3e4)
+    out["script_loud"] = m.encode_int32(torch.from_numpy(loud)[None].cuda(), 8).cpu().numpy()
+    pair = np.stack([loud, synthetic.speech_like(48000, 5, 2)])
+    out["script_loud_pair"] = m.encode_int32(torch.from_numpy(pair).cuda(), 8).cpu().numpy()
+    out["script_counters"] = np.array([m.f16_reruns, m.rvq_chain_reruns, m.graph_replays, m.graph_captures,
+                                       *m.lane_encodes], dtype=np.int64)
+    print(tag, "counters (f16_reruns, rvq_chain_reruns, graph_replays, graph_captures, lane_encodes)",
+          out["script_counters"].tolist())
+    m.close()
+
+
 def encode_section():
     m = MimiHipModel(synthetic.make_state_dict(seed=0), device="cuda:0")
     x = torch.from_numpy(synthetic.clip_batch(32, 240000, seed=501)).cuda()
@@ -38,8 +91,13 @@ def encode_section():
     xr = np.zeros((len(clips), max(lengths)), np.float32)
     for i, c in enumerate(clips):
         xr[i, :len(c)] = c
-    out["ragged"] = m.encode_ragged(torch.from_numpy(xr).cuda(), lengths, 32).cpu().numpy()
-    out["b1"] = m.encode_int32(torch.from_numpy(synthetic.clip_batch(1, 240000, seed=504)).cuda(), 32).cpu().numpy()
+    xr = torch.from_numpy(xr).cuda()
+    out["ragged"] = m.encode_ragged(xr, lengths, 32).cpu().numpy()
+    x1 = torch.from_numpy(synthetic.clip_batch(1, 240000, seed=504)).cuda()
+    out["b1"] = m.encode_int32(x1, 32).cpu().numpy()
+    profiled(m, "b32", lambda: m.encode_int32(x, 32))
+    profiled(m, "ragged", lambda: m.encode_ragged(xr, lengths, 32))
+    profiled(m, "b1", lambda: m.encode_int32(x1, 32))
     TAPS = (["conv0", "encoder", "ds_gemm", "downsample", "proj"] + [f"res{i}_elu" for i in range(4)] +
             [f"down{i}" for i in range(3)] + ["down3_elu"] +
             [f"{n}{l}" for l in range(8) for n in ("qkv", "att", "oproj", "ff", "xfmr")])
@@ -52,6 +110,7 @@ def encode_section():
             except Exception:  # (a tap the path does not produce, e.g. q/k/v under the fused attention)
                 pass
         m.set_taps(False)
+    counters_script()
 
 
 def decode_section():
@@ -65,9 +124,6 @@ def decode_section():
 
     def codes(B, K, T):
         return torch.from_numpy(rng.integers(0, m.config.codebook_size, (B, K, T)).astype(np.int32)).cuda()
-
-    def text(rows):
-        return np.array([repr(r) for r in rows])
 
     def traced(name, fn):
         """One pass with taps and profiling on: every tap's sha-256, the launch sequence and the records."""
