@@ -378,6 +378,43 @@ int mimi_bpe_merge(mimi_bpe* h, int32_t left, int32_t right, int32_t new_id, int
 void mimi_bpe_destroy(mimi_bpe* h);
 
 /*
+ * Codec-BPE encoding: words of symbol ids -> token ids (replaces the tokenizer call of
+ * pretraining-data/estimate_tokens.py:75, tokenizer(text)["input_ids"]; driven by mimi_hip/bpe.py Encoder).  The
+ * rule is HF tokenizers' BPE model for one word (no dropout, ignore_merges off): among the adjacent pairs that
+ * have a merge take the lowest rank, on equal rank the leftmost, merge that one occurrence, repeat.
+ *
+ * mimi_bpe_model_create: merges[n_merges][3] = (left id, right id, new id) in rank order, ids in the trainer's
+ * convention (special tokens, then the alphabet, then the learned tokens; a new id may be the id of an existing
+ * token with the same spelling), all in [0, n_tokens), n_tokens <= 131072; host memory, copied into a device hash
+ * table.  A pair that occurs twice keeps its last rank, as tokenizers' merge map does.
+ *
+ * mimi_bpe_encode: word w = symbols[word_offsets[w] .. word_offsets[w+1]) (host arrays, word_offsets[0] = 0);
+ * its ids are written to out_ids + word_offsets[w] (out_ids has the capacity of symbols) and their number to
+ * out_lens[w]; a word of length 0 gives nothing, a word of length 1 itself.  Runs on `stream` (a hipStream_t, NULL =
+ * the default stream) and synchronises it before returning.  A symbol id outside [0, n_tokens) returns
+ * MIMI_ERR_INVALID_ARGUMENT (checked on the device before any table access; the outputs are then undefined); a
+ * failed allocation returns MIMI_ERR_OUT_OF_MEMORY and leaves the model usable.  One encode at a time per model
+ * (calls on one model are serialised).  Words up to MIMI_BPE_ENCODE_LDS_MAX_SYMBOLS symbols run with their state in
+ * LDS, longer words on a device workspace sized from the longest word of the call.
+ *
+ * mimi_bpe_model_info: *value = the model property or last-encode figure named by `what` (MIMI_BPE_INFO_*).
+ */
+#define MIMI_BPE_ENCODE_LDS_MAX_SYMBOLS 8192
+#define MIMI_BPE_INFO_PAIRS 0                 /* distinct pairs in the merge table */
+#define MIMI_BPE_INFO_FORMED_PAIR_OUTRANKS 1  /* 1: some merge forms a pair of lower rank than its own */
+#define MIMI_BPE_INFO_TABLE_SLOTS 2           /* capacity of the merge table */
+#define MIMI_BPE_INFO_LAST_WORDS_LDS_SMALL 3  /* last encode: words run by the 3072-symbol LDS form */
+#define MIMI_BPE_INFO_LAST_WORDS_LDS 4        /* last encode: words run by the MIMI_BPE_ENCODE_LDS_MAX_SYMBOLS form */
+#define MIMI_BPE_INFO_LAST_WORDS_GLOBAL 5     /* last encode: words run on the global workspace */
+typedef struct mimi_bpe_model mimi_bpe_model;
+int mimi_bpe_model_create(int device, const int32_t* merges, int64_t n_merges, int32_t n_tokens,
+                          mimi_bpe_model** out);
+void mimi_bpe_model_destroy(mimi_bpe_model* m);
+int mimi_bpe_encode(mimi_bpe_model* m, const int32_t* symbols, const int64_t* word_offsets, int64_t n_words,
+                    int32_t* out_ids, int32_t* out_lens, void* stream);
+int mimi_bpe_model_info(const mimi_bpe_model* m, int32_t what, int64_t* value);
+
+/*
  * Diagnostic: the fp16 plane split the kernels use (two v_fma_mix per value: hi = fp16(v s), lo = fp16(v s - hi))
  * against the conversion form it replaces, on npairs value pairs of dev_in (device f32 [2 npairs], s a power of two):
  * dev_out (device u32 [npairs][4]) = the kernels' (hi, lo) words and the conversion form's (hi, lo) words.  Tests

@@ -363,3 +363,200 @@ def train_words_gpu(words: Sequence[np.ndarray], counts: np.ndarray, n_base: int
         stats.update({"seconds": time.perf_counter() - t0, "merges": len(merges), "symbols": int(sym.size),
                       "words": len(words)})
     return tokens, merges
+
+
+class Encoder:
+    """Apply a trained codec-BPE model on the GPU: codes (or ``codes_to_chars`` strings) -> token ids.
+
+    Replaces the tokenizer call of the reference's ``pretraining-data/estimate_tokens.py:75``
+    (``tokenizer(text)["input_ids"]``) for code strings.  The result equals
+    ``tok.encode(codes_to_chars(...), add_special_tokens=False).ids`` of the tokenizer ``Trainer`` assembles with
+    ``unk_token=None`` (the recipe's setting: ``train_bpe_recipe.txt`` passes only ``--pad_token``).  In that
+    model the characters NFKC rewrites and the Metaspace ``▁`` are not in the vocabulary and give no id, so
+    ``CharModel`` (drop, split, mark reordering) is the whole host model; the merges run in ``bpe_encode.hip``
+    (``mimi_bpe_encode``), one workgroup per word, all words of a call in one launch per kernel form.
+
+    A model with an ``unk_token`` raises ``NotImplementedError`` at construction: there every dropped character
+    would give the unknown id, which this host model does not produce.  Characters outside the
+    ``num_codebooks x codebook_size`` code alphabet raise ``ValueError`` (``CharModel.words``).  Codes are read
+    from host arrays, not from device memory, and merging the vocabulary into a text tokenizer (the reference's
+    ``extend_tokenizer`` step) is not part of this class.
+
+    merges: ``(left id, right id, new id)`` in rank order; ids count the special tokens first, then the alphabet in
+    code point order, then the learned tokens -- the trainer's convention.
+    """
+
+    LDS_MAX_SYMBOLS = 8192  # _lib.BPE_ENCODE_LDS_MAX_SYMBOLS: longer words run on a global workspace
+
+    def __init__(self, num_codebooks: int, codebook_size: int, merges, n_tokens: int, n_special: int,
+                 unicode_offset: int = UNICODE_OFFSET, device: Union[int, str] = 0, unk_token: Optional[str] = None):
+        from . import _lib
+        if unk_token is not None:
+            raise NotImplementedError("bpe.Encoder supports models without an unk_token only (the recipe's setting)")
+        self.num_codebooks, self.codebook_size = num_codebooks, codebook_size
+        self.unicode_offset = validate_unicode_offset(unicode_offset, num_codebooks, codebook_size)
+        self.n_special, self.n_tokens = int(n_special), int(n_tokens)
+        n_base = num_codebooks * codebook_size
+        if self.n_special < 0 or self.n_tokens < self.n_special + n_base:
+            raise ValueError(f"n_tokens {n_tokens} is below {n_special} special tokens + {n_base} code characters")
+        if self.n_tokens > (1 << 17):
+            raise ValueError("token ids above 131071 are not supported by the GPU encoder")
+        self.merges = np.ascontiguousarray(np.asarray(merges, dtype=np.int64).reshape(-1, 3).astype(np.int32))
+        if self.merges.size and (self.merges.min() < 0 or self.merges.max() >= self.n_tokens):
+            raise ValueError("merge ids outside [0, n_tokens)")
+        self.device = device if isinstance(device, int) else int(str(device).split(":")[-1] or 0)
+        self._chars = CharModel(self.unicode_offset, n_base)
+        self._lib = _lib.load()
+        self._h = ctypes.c_void_p()  # the device model (merge table), made on first use
+        self.last_stats: Dict[str, float] = {}
+
+    def _model(self):
+        from . import _lib
+        if not self._h:
+            _lib.check(self._lib.mimi_bpe_model_create(self.device, self.merges.ctypes.data, len(self.merges),
+                                                       self.n_tokens, ctypes.byref(self._h)))
+        return self._h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.mimi_bpe_model_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    # ---- construction ----------------------------------------------------------------------------
+    @classmethod
+    def from_trainer(cls, trainer: "Trainer") -> "Encoder":
+        """The model of ``trainer``'s last training (``last_tokens`` / ``last_merges``); no ``tokenizers`` import."""
+        n_sp, n_base = len(trainer.special_tokens), trainer.num_codebooks * trainer.codebook_size
+        spell: List[Tuple[int, ...]] = [()] * n_sp + [(i,) for i in range(n_base)] + list(trainer.last_tokens)
+        tok_id: Dict[Tuple[int, ...], int] = {}
+        for i in range(n_sp, len(spell)):
+            tok_id.setdefault(spell[i], i)
+        merges = [(a, b, tok_id[spell[a] + spell[b]]) for a, b in trainer.last_merges]
+        return cls(trainer.num_codebooks, trainer.codebook_size, merges, len(spell), n_sp,
+                   unicode_offset=trainer.unicode_offset, device=trainer.device, unk_token=trainer.unk_token)
+
+    @classmethod
+    def from_tokenizer(cls, tokenizer, num_codebooks: int, codebook_size: int,
+                       unicode_offset: int = UNICODE_OFFSET, device: Union[int, str] = 0) -> "Encoder":
+        """From a ``tokenizers.Tokenizer``, a ``PreTrainedTokenizerFast`` or the path of a ``tokenizer.json``: the
+        BPE model's vocab and merges are read from the JSON."""
+        if isinstance(tokenizer, (str, os.PathLike)):
+            with open(tokenizer, encoding="utf-8") as f:
+                j = json.load(f)
+        else:
+            backend = getattr(tokenizer, "backend_tokenizer", tokenizer)
+            j = json.loads(backend.to_str())
+        model = j["model"]
+        if model.get("type", "BPE") != "BPE":
+            raise ValueError(f"not a BPE model: {model.get('type')}")
+        if model.get("unk_token") is not None:
+            raise NotImplementedError("bpe.Encoder supports models without an unk_token only (the recipe's setting)")
+        for key in ("dropout", "continuing_subword_prefix", "end_of_word_suffix"):
+            if model.get(key):
+                raise NotImplementedError(f"BPE model option {key} is not supported")
+        if model.get("byte_fallback") or model.get("ignore_merges"):
+            raise NotImplementedError("byte_fallback / ignore_merges models are not supported")
+        vocab = model["vocab"]
+        n_base = num_codebooks * codebook_size
+        validate_unicode_offset(unicode_offset, num_codebooks, codebook_size)
+        n_sp = vocab.get(chr(unicode_offset))
+        if n_sp is None or any(vocab.get(chr(unicode_offset + i)) != n_sp + i for i in range(n_base)):
+            raise ValueError("the vocabulary does not hold the code characters in code point order after the "
+                             "special tokens")
+        n_tokens = max(max(vocab.values()), max((t["id"] for t in j.get("added_tokens", [])), default=0)) + 1
+        merges = []
+        for m in model["merges"]:
+            a, b = m.split(" ") if isinstance(m, str) else m
+            merges.append((vocab[a], vocab[b], vocab[a + b]))
+        return cls(num_codebooks, codebook_size, merges, n_tokens, n_sp, unicode_offset=unicode_offset,
+                   device=device)
+
+    # ---- model properties --------------------------------------------------------------------------
+    def info(self, key: str) -> int:
+        """``mimi_bpe_model_info``: "pairs", "formed_pair_outranks", "table_slots", and of the last encode
+        "last_words_lds_small", "last_words_lds", "last_words_global" (words run by each kernel form)."""
+        from . import _lib
+        v = ctypes.c_int64()
+        _lib.check(self._lib.mimi_bpe_model_info(self._model(), _lib.BPE_INFO[key], ctypes.byref(v)))
+        return v.value
+
+    @property
+    def formed_pair_outranks(self) -> bool:
+        """Some merge forms a pair whose own merge has a lower rank (an id reused by a later merge): merging
+        every occurrence of a round's pair at once would be wrong for this model."""
+        return bool(self.info("formed_pair_outranks"))
+
+    # ---- encoding ----------------------------------------------------------------------------------
+    def _encode_flat(self, sym: np.ndarray, offs: np.ndarray, stream=None) -> Tuple[np.ndarray, np.ndarray]:
+        """``mimi_bpe_encode``: (out_ids with word w's ids at offs[w], out_lens)."""
+        from . import _lib
+        n_words = len(offs) - 1
+        out = np.empty(max(sym.size, 1), dtype=np.int32)
+        out_lens = np.zeros(max(n_words, 1), dtype=np.int32)
+        s = getattr(stream, "cuda_stream", stream)
+        try:
+            _lib.check(self._lib.mimi_bpe_encode(self._model(), sym.ctypes.data, offs.ctypes.data, n_words,
+                                                 out.ctypes.data, out_lens.ctypes.data,
+                                                 ctypes.c_void_p(int(s)) if s else None))
+        except _lib.MimiHipError as e:
+            if e.status == 1:
+                raise ValueError(str(e)) from None
+            raise
+        return out, out_lens[:n_words]
+
+    def encode_words(self, words: Sequence[np.ndarray], stream=None) -> List[np.ndarray]:
+        """Words of symbol ids (special tokens first, then the alphabet) -> each word's token ids; one GPU call.
+        stream: a ``torch.cuda.Stream`` or a raw ``hipStream_t`` value (default: the default stream)."""
+        lens = np.array([len(w) for w in words], dtype=np.int64)
+        offs = np.zeros(len(words) + 1, dtype=np.int64)
+        np.cumsum(lens, out=offs[1:])
+        sym = np.ascontiguousarray(np.concatenate([np.asarray(w, dtype=np.int32) for w in words])
+                                   if len(words) else np.zeros(0, np.int32), dtype=np.int32)
+        out, out_lens = self._encode_flat(sym, offs, stream)
+        return [out[offs[w]:offs[w] + out_lens[w]].copy() for w in range(len(words))]
+
+    def _encode_codepoints(self, seqs: Sequence[np.ndarray], stream=None) -> List[np.ndarray]:
+        # (per sequence: one pass over all sequences' characters at once was measured slower, its arrays leave
+        # the cache)
+        t0 = time.perf_counter()
+        words: List[np.ndarray] = []
+        nwords = []
+        for cps in seqs:
+            ws = self._chars.words(cps)
+            nwords.append(len(ws))
+            words.extend(w.astype(np.int32) + np.int32(self.n_special) for w in ws)
+        t1 = time.perf_counter()
+        ids = self.encode_words(words, stream)
+        out, at = [], 0
+        for n in nwords:
+            out.append(np.concatenate(ids[at:at + n]).astype(np.int32) if n else np.zeros(0, np.int32))
+            at += n
+        self.last_stats = {"host_words_s": t1 - t0, "encode_s": time.perf_counter() - t1, "words": len(words),
+                           "symbols": int(sum(len(w) for w in words)), "tokens": int(sum(len(o) for o in out))}
+        return out
+
+    def encode_codes(self, codes_list: Iterable[np.ndarray], stream=None) -> List[np.ndarray]:
+        """Each ``[K', T]`` code array (first ``num_codebooks`` rows; leading batch dimensions as
+        ``Trainer.iterate_codepoints``) is one sequence -> its ``int32`` token ids."""
+        seqs = []
+        for codes in codes_list:
+            if len(codes.shape) == 4:
+                codes = codes[0, 0]
+            elif len(codes.shape) == 3:
+                codes = codes[0]
+            # (a copy: the caller's codes stay as they are; the offsets are still added in the codes' own dtype)
+            seqs.append(codes_to_codepoints(codes[:self.num_codebooks], self.codebook_size,
+                                            unicode_offset=self.unicode_offset))
+        return self._encode_codepoints(seqs, stream)
+
+    def encode_strs(self, strings: Iterable[str], stream=None) -> List[np.ndarray]:
+        """``codes_to_chars`` strings -> ``int32`` token ids, one array per string."""
+        return self._encode_codepoints(
+            [np.frombuffer(s.encode("utf-32-le", "surrogatepass"), dtype="<u4").astype(np.int64) for s in strings],
+            stream)
