@@ -1606,6 +1606,8 @@ static int encode_pass(mimi_engine* e, const PassCtx& ctx, const float* audio, i
             LAUNCH_TRY(launch_gemm(ROLE_RES3P, a3, s, &kname, prec), "res3");
             snprintf(nm, sizeof nm, "res3_s%d", si);
             rec.mark(nm, gemm_flops(a3) * rows_of(si, (double)B * T) / ((double)B * T), gemm_bytes(a3, false), kname);
+            // (taps only) h, so that the k3 and the k1 conv of an unfused block can each be checked on its own input
+            if ((rc = save_tap_planes(e, nmf("h%d", si).c_str(), w.h, ns, B, T, Hh, s, hact.scale))) return rc;
             GemmArgs a1 = conv_args(e->res1[si], nullptr, T, nullptr, T, B);
             planes_in(a1, w.h, (long long)B * T * Hh);
             use_h(a1, e->res1[si].wh, e->res1[si].wscale, hact);
