@@ -415,6 +415,44 @@ int mimi_bpe_encode(mimi_bpe_model* m, const int32_t* symbols, const int64_t* wo
 int mimi_bpe_model_info(const mimi_bpe_model* m, int32_t what, int64_t* value);
 
 /*
+ * Codec-BPE encoding of codes that are already in device memory: the word model (what tokenizers' NFKC normalizer and
+ * Metaspace pre-tokenizer do to a string of code characters; mimi_hip/bpe.py CharModel.words) runs on the device, then
+ * the merge kernels of mimi_bpe_encode, then the ids are packed per sequence -- device memory in, device memory out.
+ *
+ * mimi_bpe_model_set_alphabet: the code alphabet of the model: num_codebooks x codebook_size characters, character
+ * k * codebook_size + code has symbol id n_special + its index, class cls[index] (0 keep starter, 1 keep mark, 2 drop
+ * starter, 3 drop mark, 4 split) and combining class ccc[index]; cls and ccc are host arrays, copied into one device
+ * table of 2 bytes per character.  A class above 4 or n_special + num_codebooks * codebook_size > n_tokens returns
+ * MIMI_ERR_INVALID_ARGUMENT.  Call it once before mimi_bpe_encode_codes (else MIMI_ERR_STATE).
+ *
+ * mimi_bpe_encode_codes: dev_codes is device int32, codebook k of item b at dev_codes + b * item_stride +
+ * k * row_stride, frame_lengths[b] frames of it (host array; frames beyond are never read), k < num_codebooks (an
+ * item may have more rows: an engine's [B][K'][Tmax] output is used as it stands).  Item b gives
+ * max(1, ceil(T_b / chunk_frames)) sequences of chunk_frames frames (the last one shorter), chunk_frames = 0: the
+ * whole item; an empty item gives one empty sequence; sequences count in item order, then chunk order, and n_seq
+ * must equal their number.  Each sequence is a string of its own: position (frame t, codebook k) is character t *
+ * num_codebooks + k.  Inside each run of marks (classes 1 and 3 between starter-class characters or the ends of the
+ * sequence) the kept marks are stably sorted by ccc; then dropped characters vanish, split characters vanish and
+ * cut the word, and the words are encoded as by mimi_bpe_encode.  On return dev_out_ids (device int32, out_capacity
+ * >= num_codebooks * sum of frame_lengths, which bounds the token count) holds the ids of sequence s, packed, at
+ * [seq_offsets[s], seq_offsets[s + 1]) (seq_offsets: host, n_seq + 1 entries).  Runs on `stream` and synchronises it
+ * twice: once mid-way to read back 32 bytes (flags, the word count of each kernel form, the longest word), once at
+ * the end.  A code outside [0, codebook_size) returns MIMI_ERR_INVALID_ARGUMENT (checked on the device before the
+ * table load); a run of more than MIMI_BPE_WORDS_MAX_RUN marks returns MIMI_ERR_UNSUPPORTED (the caller may run the
+ * host word model instead); in both cases the outputs are undefined and the model stays usable.  Serialised with
+ * mimi_bpe_encode by the model's mutex; MIMI_BPE_INFO_LAST_WORDS_* report this call as they do that one.  The device
+ * buffers grow with the call and are kept: 40 bytes per character.
+ */
+#define MIMI_BPE_WORDS_MAX_RUN 64     /* longest run of marks the device word model orders */
+#define MIMI_BPE_WORDS_SCAN_TILE 2048 /* characters per workgroup of the classify / scan kernels */
+int mimi_bpe_model_set_alphabet(mimi_bpe_model* m, int32_t n_special, int32_t num_codebooks, int32_t codebook_size,
+                                const uint8_t* cls, const uint8_t* ccc);
+int mimi_bpe_encode_codes(mimi_bpe_model* m, const int32_t* dev_codes, int32_t batch, int64_t item_stride,
+                          int64_t row_stride, const int64_t* frame_lengths, int64_t chunk_frames,
+                          int32_t* dev_out_ids, int64_t out_capacity, int64_t* seq_offsets, int64_t n_seq,
+                          void* stream);
+
+/*
  * Diagnostic: the fp16 plane split the kernels use (two v_fma_mix per value: hi = fp16(v s), lo = fp16(v s - hi))
  * against the conversion form it replaces, on npairs value pairs of dev_in (device f32 [2 npairs], s a power of two):
  * dev_out (device u32 [npairs][4]) = the kernels' (hi, lo) words and the conversion form's (hi, lo) words.  Tests

@@ -27,25 +27,23 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <memory>
-#include <mutex>
 #include <vector>
 
-#include "../../include/mimi_hip.h"
-#include "kernels.h"
+#include "bpe_model.h"
 
 namespace {
+
+using mimi::bpe::fail;
+using mimi::bpe::kLdsCap;
+using mimi::bpe::kSmallCap;
 
 constexpr unsigned kNoRank = 0xffffffffu;
 constexpr unsigned long long kEmptyKey = ~0ull;
 constexpr unsigned long long kMiss = ~0ull;  // rank half = kNoRank
 constexpr unsigned kMaxId = (1u << 17) - 1;
 constexpr int kThreads = 256;
-constexpr int kSmallCap = 3072;
-constexpr int kLdsCap = MIMI_BPE_ENCODE_LDS_MAX_SYMBOLS;
 constexpr int kMaxGlobalGroups = 1024;  // workgroups (and workspace slabs) of the global form
 
 struct Slot {
@@ -236,68 +234,14 @@ __global__ __launch_bounds__(kThreads) void bpe_encode_global_kernel(EncodeArgs 
     }
 }
 
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return mimi::set_error_message(code, buf);
-}
-
-// a device buffer that grows on demand; a failed growth leaves it empty and usable
-struct Buffer {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return e;
-        }
-        cap = bytes;
-        return hipSuccess;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 }  // namespace
-
-struct mimi_bpe_model {
-    int device = 0;
-    int n_tokens = 0;
-    int64_t n_merges = 0, n_pairs = 0;
-    bool outranks = false;
-    ulonglong2* slots = nullptr;
-    unsigned mask = 0;
-    std::mutex mu;  // one encode at a time per model (the buffers below)
-    Buffer symbols, offsets, words, out_ids, out_lens, bad, ws;
-    int64_t last_words[3] = {0, 0, 0};  // of the last encode: small LDS form, large LDS form, global form
-};
-
-#define ENC_TRY(expr)                                                                                       \
-    do {                                                                                                    \
-        hipError_t _e = (expr);                                                                             \
-        if (_e != hipSuccess) {                                                                             \
-            (void)hipGetLastError();                                                                        \
-            return fail(_e == hipErrorOutOfMemory ? MIMI_ERR_OUT_OF_MEMORY : MIMI_ERR_HIP, "%s: %s (%s:%d)", \
-                        #expr, hipGetErrorString(_e), __FILE__, __LINE__);                                  \
-        }                                                                                                   \
-    } while (0)
 
 extern "C" void mimi_bpe_model_destroy(mimi_bpe_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    for (Buffer* b : {&m->symbols, &m->offsets, &m->words, &m->out_ids, &m->out_lens, &m->bad, &m->ws}) b->release();
+    m->release_buffers();
     if (m->slots) (void)hipFree(m->slots);
+    if (m->alphabet) (void)hipFree(m->alphabet);
     delete m;
 }
 
@@ -372,6 +316,38 @@ extern "C" int mimi_bpe_model_info(const mimi_bpe_model* m, int32_t what, int64_
     return MIMI_OK;
 }
 
+// (declared in bpe_model.h)
+int mimi::bpe::launch_forms(mimi_bpe_model* m, const int* const lists[3], const int64_t counts[3], int64_t longest,
+                            hipStream_t s) {
+    const long long stride = (longest + 63) / 64 * 64;
+    const int groups = (int)std::min<int64_t>(counts[2], kMaxGlobalGroups);
+    if (groups > 0) ENC_TRY(m->ws.reserve((size_t)groups * 5 * (size_t)stride * 4));
+    EncodeArgs a{};
+    a.symbols = (const int*)m->symbols.p;
+    a.offsets = (const long long*)m->offsets.p;
+    a.n_tokens = m->n_tokens;
+    a.t = TableView{m->slots, m->mask};
+    a.out_ids = (int*)m->out_ids.p;
+    a.out_lens = (int*)m->out_lens.p;
+    a.bad = (unsigned*)m->bad.p;
+    for (int f = 0; f < 3; ++f) {
+        const int64_t nw = counts[f];
+        m->last_words[f] = nw;
+        if (nw == 0) continue;
+        a.words = lists[f];
+        a.n_words = (int)nw;
+        if (f == 0)
+            hipLaunchKernelGGL(bpe_encode_lds_kernel<kSmallCap>, dim3((unsigned)nw), dim3(kThreads), 0, s, a);
+        else if (f == 1)
+            hipLaunchKernelGGL(bpe_encode_lds_kernel<kLdsCap>, dim3((unsigned)nw), dim3(kThreads), 0, s, a);
+        else
+            hipLaunchKernelGGL(bpe_encode_global_kernel, dim3((unsigned)groups), dim3(kThreads), 0, s, a,
+                               (int*)m->ws.p, stride);
+        ENC_TRY(hipGetLastError());
+    }
+    return MIMI_OK;
+}
+
 // the copies in, the launches and the copies out, all on s; `lists` and `bad` are the caller's so that they
 // outlive every copy queued here (the caller synchronises s, also when this fails half way)
 static int encode_on_stream(mimi_bpe_model* m, const int32_t* symbols, const int64_t* word_offsets, int64_t n_words,
@@ -397,39 +373,21 @@ static int encode_on_stream(mimi_bpe_model* m, const int32_t* symbols, const int
     ENC_TRY(m->words.reserve((size_t)n_words * 4));
     ENC_TRY(m->out_lens.reserve((size_t)n_words * 4));
     ENC_TRY(m->bad.reserve(4));
-    const long long stride = (longest + 63) / 64 * 64;
-    const int groups = (int)std::min<size_t>(list[2].size(), kMaxGlobalGroups);
-    if (groups > 0) ENC_TRY(m->ws.reserve((size_t)groups * 5 * (size_t)stride * 4));
     if (n_symbols > 0) ENC_TRY(hipMemcpyAsync(m->symbols.p, symbols, (size_t)n_symbols * 4, hipMemcpyHostToDevice, s));
     ENC_TRY(hipMemcpyAsync(m->offsets.p, word_offsets, (size_t)(n_words + 1) * 8, hipMemcpyHostToDevice, s));
     ENC_TRY(hipMemsetAsync(m->bad.p, 0, 4, s));
-    EncodeArgs a{};
-    a.symbols = (const int*)m->symbols.p;
-    a.offsets = (const long long*)m->offsets.p;
-    a.n_tokens = m->n_tokens;
-    a.t = TableView{m->slots, m->mask};
-    a.out_ids = (int*)m->out_ids.p;
-    a.out_lens = (int*)m->out_lens.p;
-    a.bad = (unsigned*)m->bad.p;
+    const int* lists[3];
+    int64_t counts[3];
     size_t at = 0;
     for (int f = 0; f < 3; ++f) {
         const size_t nw = list[f].size();
-        m->last_words[f] = (int64_t)nw;
-        if (nw == 0) continue;
-        int* dev_list = (int*)m->words.p + at;
+        lists[f] = (const int*)m->words.p + at;
+        counts[f] = (int64_t)nw;
+        if (nw > 0) ENC_TRY(hipMemcpyAsync((int*)m->words.p + at, list[f].data(), nw * 4, hipMemcpyHostToDevice, s));
         at += nw;
-        ENC_TRY(hipMemcpyAsync(dev_list, list[f].data(), nw * 4, hipMemcpyHostToDevice, s));
-        a.words = dev_list;
-        a.n_words = (int)nw;
-        if (f == 0)
-            hipLaunchKernelGGL(bpe_encode_lds_kernel<kSmallCap>, dim3((unsigned)nw), dim3(kThreads), 0, s, a);
-        else if (f == 1)
-            hipLaunchKernelGGL(bpe_encode_lds_kernel<kLdsCap>, dim3((unsigned)nw), dim3(kThreads), 0, s, a);
-        else
-            hipLaunchKernelGGL(bpe_encode_global_kernel, dim3((unsigned)groups), dim3(kThreads), 0, s, a,
-                               (int*)m->ws.p, stride);
-        ENC_TRY(hipGetLastError());
     }
+    const int rc = mimi::bpe::launch_forms(m, lists, counts, longest, s);
+    if (rc != MIMI_OK) return rc;
     ENC_TRY(hipMemcpyAsync(bad, m->bad.p, 4, hipMemcpyDeviceToHost, s));
     ENC_TRY(hipMemcpyAsync(out_lens, m->out_lens.p, (size_t)n_words * 4, hipMemcpyDeviceToHost, s));
     if (n_symbols > 0) ENC_TRY(hipMemcpyAsync(out_ids, m->out_ids.p, (size_t)n_symbols * 4, hipMemcpyDeviceToHost, s));

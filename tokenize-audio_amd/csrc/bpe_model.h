@@ -1,0 +1,98 @@
+// The device BPE model shared by bpe_encode.hip (merge table, merge kernels, host-word entry) and bpe_words.hip
+// (device word model, device-to-device entry).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <mutex>
+
+#include "../../include/mimi_hip.h"
+#include "kernels.h"
+
+namespace mimi {
+namespace bpe {
+
+inline int fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return mimi::set_error_message(code, buf);
+}
+
+// a device buffer that grows on demand; a failed growth leaves it empty and usable
+struct Buffer {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t reserve(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return e;
+        }
+        cap = bytes;
+        return hipSuccess;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// words of each merge-kernel form: at most kSmallCap symbols, at most MIMI_BPE_ENCODE_LDS_MAX_SYMBOLS, longer
+constexpr int kSmallCap = 3072;
+constexpr int kLdsCap = MIMI_BPE_ENCODE_LDS_MAX_SYMBOLS;
+
+}  // namespace bpe
+}  // namespace mimi
+
+struct mimi_bpe_model {
+    int device = 0;
+    int n_tokens = 0;
+    int64_t n_merges = 0, n_pairs = 0;
+    bool outranks = false;
+    ulonglong2* slots = nullptr;
+    unsigned mask = 0;
+    std::mutex mu;  // one encode at a time per model (the buffers below)
+    mimi::bpe::Buffer symbols, offsets, words, out_ids, out_lens, bad, ws;
+    int64_t last_words[3] = {0, 0, 0};  // of the last encode: small LDS form, large LDS form, global form
+    // device word model (bpe_words.hip): the alphabet table (class | ccc << 8 per code character) and its buffers
+    unsigned short* alphabet = nullptr;
+    int n_special = 0, num_codebooks = 0, codebook_size = 0;
+    mimi::bpe::Buffer seqs, info, scan, partials, symword, word_first, seq_out;
+    void release_buffers() {
+        for (mimi::bpe::Buffer* b : {&symbols, &offsets, &words, &out_ids, &out_lens, &bad, &ws, &seqs, &info, &scan,
+                                     &partials, &symword, &word_first, &seq_out})
+            b->release();
+    }
+};
+
+#define ENC_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t _e = (expr);                                                                         \
+        if (_e != hipSuccess) {                                                                         \
+            (void)hipGetLastError();                                                                    \
+            return mimi::bpe::fail(_e == hipErrorOutOfMemory ? MIMI_ERR_OUT_OF_MEMORY : MIMI_ERR_HIP,   \
+                                   "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+        }                                                                                               \
+    } while (0)
+
+namespace mimi {
+namespace bpe {
+
+// The merge kernels over the model's device buffers, on s: symbols, offsets, out_ids, out_lens and bad hold the
+// call's words (bad cleared); lists[f] is the device list of the counts[f] words of form f, `longest` the longest
+// word of the call.  Sizes the global workspace and sets last_words.
+int launch_forms(mimi_bpe_model* m, const int* const lists[3], const int64_t counts[3], int64_t longest,
+                 hipStream_t s);
+
+}  // namespace bpe
+}  // namespace mimi

@@ -34,10 +34,13 @@ EXPORTED_SYMBOLS = (
     "mimi_rvq_decode", "mimi_decode_workspace_bytes", "mimi_upconv_relayout",
     "mimi_decode_ragged", "mimi_decode_ragged_workspace_bytes",
     "mimi_bpe_model_create", "mimi_bpe_model_destroy", "mimi_bpe_encode", "mimi_bpe_model_info",
+    "mimi_bpe_model_set_alphabet", "mimi_bpe_encode_codes",
 )
 CREATE_DECODE = 1  # MIMI_CREATE_DECODE
 RESAMPLE_MAX_TAPS = 65536  # MIMI_RESAMPLE_MAX_TAPS
 BPE_ENCODE_LDS_MAX_SYMBOLS = 8192  # MIMI_BPE_ENCODE_LDS_MAX_SYMBOLS
+BPE_WORDS_MAX_RUN = 64  # MIMI_BPE_WORDS_MAX_RUN
+BPE_WORDS_SCAN_TILE = 2048  # MIMI_BPE_WORDS_SCAN_TILE
 # MIMI_BPE_INFO_*
 BPE_INFO = {"pairs": 0, "formed_pair_outranks": 1, "table_slots": 2, "last_words_lds_small": 3, "last_words_lds": 4,
             "last_words_global": 5}
@@ -133,6 +136,9 @@ def _declare(lib):
         "mimi_bpe_model_destroy": (None, [vp]),
         "mimi_bpe_encode": (c.c_int, [vp, vp, vp, c.c_int64, vp, vp, vp]),
         "mimi_bpe_model_info": (c.c_int, [vp, c.c_int32, c.POINTER(c.c_int64)]),
+        "mimi_bpe_model_set_alphabet": (c.c_int, [vp, c.c_int32, c.c_int32, c.c_int32, vp, vp]),
+        "mimi_bpe_encode_codes": (c.c_int, [vp, vp, c.c_int32, c.c_int64, c.c_int64, vp, c.c_int64, vp, c.c_int64, vp,
+                                            c.c_int64, vp]),
         "mimi_flac_info": (c.c_int, [vp, c.c_int64, c.POINTER(c.c_int32), c.POINTER(c.c_int32),
                                      c.POINTER(c.c_int32), c.POINTER(c.c_int64)]),
         "mimi_flac_decode": (c.c_int, [vp, c.c_int64, vp, c.c_int64, c.POINTER(c.c_int64)]),

@@ -378,15 +378,18 @@ class Encoder:
 
     A model with an ``unk_token`` raises ``NotImplementedError`` at construction: there every dropped character
     would give the unknown id, which this host model does not produce.  Characters outside the
-    ``num_codebooks x codebook_size`` code alphabet raise ``ValueError`` (``CharModel.words``).  Codes are read
-    from host arrays, not from device memory, and merging the vocabulary into a text tokenizer (the reference's
-    ``extend_tokenizer`` step) is not part of this class.
+    ``num_codebooks x codebook_size`` code alphabet raise ``ValueError`` (``CharModel.words``).  ``encode_codes``
+    / ``encode_strs`` / ``encode_words`` read host arrays and run ``CharModel`` on the host; ``encode_device``
+    takes codes in device memory, runs the same word model in ``bpe_words.hip`` and leaves the ids on the device.
+    Merging the vocabulary into a text tokenizer (the reference's ``extend_tokenizer`` step) is not part of this
+    class.
 
     merges: ``(left id, right id, new id)`` in rank order; ids count the special tokens first, then the alphabet in
     code point order, then the learned tokens -- the trainer's convention.
     """
 
     LDS_MAX_SYMBOLS = 8192  # _lib.BPE_ENCODE_LDS_MAX_SYMBOLS: longer words run on a global workspace
+    WORDS_MAX_RUN = 64  # _lib.BPE_WORDS_MAX_RUN: the longest run of marks the device word model orders
 
     def __init__(self, num_codebooks: int, codebook_size: int, merges, n_tokens: int, n_special: int,
                  unicode_offset: int = UNICODE_OFFSET, device: Union[int, str] = 0, unk_token: Optional[str] = None):
@@ -415,6 +418,10 @@ class Encoder:
         if not self._h:
             _lib.check(self._lib.mimi_bpe_model_create(self.device, self.merges.ctypes.data, len(self.merges),
                                                        self.n_tokens, ctypes.byref(self._h)))
+            # the device word model's alphabet (encode_device): class and combining class of every code character
+            cls, ccc = np.ascontiguousarray(self._chars.cls), np.ascontiguousarray(self._chars.ccc)
+            _lib.check(self._lib.mimi_bpe_model_set_alphabet(self._h, self.n_special, self.num_codebooks,
+                                                             self.codebook_size, cls.ctypes.data, ccc.ctypes.data))
         return self._h
 
     def close(self) -> None:
@@ -560,3 +567,114 @@ class Encoder:
         return self._encode_codepoints(
             [np.frombuffer(s.encode("utf-32-le", "surrogatepass"), dtype="<u4").astype(np.int64) for s in strings],
             stream)
+
+    def encode_device(self, codes, lengths=None, chunk_frames: int = 0, stream=None, to_host: bool = False):
+        """Codes in device memory -> token ids in device memory: the word model, the merges and the packing all run
+        on the GPU (``mimi_bpe_encode_codes``), so ``MimiHipModel.encode(...).audio_codes`` can be passed as it is.
+
+        codes: a CUDA ``torch.Tensor`` ``[B, K', T]`` or ``[K', T]``, int32 or int64 (int64 is narrowed by a torch
+        op), ``K' >= num_codebooks`` (further rows are ignored).  lengths: frames of each item (default ``T``);
+        frames beyond an item's length are never read.  chunk_frames > 0 cuts every item into sequences of that many
+        frames, each a string of its own as ``Trainer.iterate_codepoints`` cuts them; 0: one sequence per item.  An
+        item of length 0 gives one empty sequence.  stream: a ``torch.cuda.Stream`` or a raw ``hipStream_t`` value
+        (default: the current stream of the codes' device); the call synchronises it.
+
+        Returns ``(ids, seq_offsets, seq_item)``: ``ids`` an int32 device tensor holding sequence s at
+        ``ids[seq_offsets[s]:seq_offsets[s + 1]]``, ``seq_offsets`` a host int64 array of ``n_seq + 1`` entries,
+        ``seq_item`` the item of each sequence (host int64 array).  With ``to_host=True``: a list of int32 numpy
+        arrays, one per sequence.  ``last_stats["word_model"]`` is ``"device"``, or ``"host"`` when a run of more
+        than ``WORDS_MAX_RUN`` marks made the call go through ``encode_codes`` on ``.cpu()`` codes instead (same
+        result; the recipe's alphabet has runs of at most 5).
+
+        Unlike ``encode_codes``, a code outside ``[0, codebook_size)`` is always a ``ValueError``: there the offset
+        add can carry such a code into a neighbouring codebook's characters, here it is checked on the device
+        before any table is read.  Argument errors raise ``ValueError`` before any device call."""
+        import torch
+
+        from . import _lib
+        if not isinstance(codes, torch.Tensor):
+            raise ValueError("codes must be a CUDA torch.Tensor (host arrays: encode_codes)")
+        if codes.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"codes must be int32 or int64, not {codes.dtype}")
+        if codes.dim() == 2:
+            codes = codes[None]
+        if codes.dim() != 3:
+            raise ValueError("codes must have shape [B, K', T] or [K', T]")
+        B, Kp, T = codes.shape
+        if Kp < self.num_codebooks:
+            raise ValueError(f"codes have {Kp} codebook rows, the model needs {self.num_codebooks}")
+        chunk_frames = int(chunk_frames)
+        if chunk_frames < 0:
+            raise ValueError("chunk_frames must be >= 0")
+        if lengths is None:
+            lens = np.full(B, T, dtype=np.int64)
+        else:
+            if isinstance(lengths, torch.Tensor):
+                lengths = lengths.cpu().numpy()
+            lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+            if lens.size != B:
+                raise ValueError(f"{lens.size} lengths for {B} items")
+            if B and (lens.min() < 0 or lens.max() > T):
+                raise ValueError(f"lengths must be in [0, {T}]")
+        if not codes.is_cuda:
+            raise ValueError("codes must be a CUDA torch.Tensor (host arrays: encode_codes)")
+        if codes.device.index != self.device:
+            raise ValueError(f"codes are on {codes.device}, the encoder on device {self.device}")
+        if chunk_frames:
+            per_item = np.maximum(1, -(-lens // chunk_frames))
+        else:
+            per_item = np.ones(B, dtype=np.int64)
+        seq_item = np.repeat(np.arange(B, dtype=np.int64), per_item)
+        n_seq = int(seq_item.size)
+        seq_offsets = np.zeros(n_seq + 1, dtype=np.int64)
+        capacity = self.num_codebooks * int(lens.sum())
+        t0 = time.perf_counter()
+        with torch.cuda.device(codes.device):
+            if codes.dtype != torch.int32:
+                codes = codes.to(torch.int32)
+            if T and codes.stride(2) != 1:
+                codes = codes.contiguous()
+            ids = torch.empty(max(capacity, 1), dtype=torch.int32, device=codes.device)
+            if stream is None:
+                stream = torch.cuda.current_stream(codes.device)
+            s = getattr(stream, "cuda_stream", stream)
+            current = torch.cuda.current_stream(codes.device)
+            if int(s or 0) != current.cuda_stream:
+                current.synchronize()  # the narrowing / copy above ran there
+            model_mode = "device"
+            if n_seq:
+                try:
+                    _lib.check(self._lib.mimi_bpe_encode_codes(
+                        self._model(), ctypes.c_void_p(codes.data_ptr()), B, codes.stride(0), codes.stride(1),
+                        lens.ctypes.data, chunk_frames, ctypes.c_void_p(ids.data_ptr()), capacity,
+                        seq_offsets.ctypes.data, n_seq, ctypes.c_void_p(int(s)) if s else None))
+                except _lib.MimiHipError as e:
+                    if e.status == 1:
+                        raise ValueError(str(e)) from None
+                    if e.status != 5 or "MIMI_BPE_WORDS_MAX_RUN" not in str(e):
+                        raise
+                    # a run of marks above the device cap: the host word model on the same chunks
+                    model_mode = "host"
+                    host = codes[:, :self.num_codebooks].cpu().numpy()
+                    chunks = []
+                    for b in range(B):
+                        Tb = int(lens[b])
+                        step = chunk_frames or max(Tb, 1)
+                        chunks += [host[b][:, f:min(f + step, Tb)] for f in range(0, max(Tb, 1), step)]
+                    out = self.encode_codes(chunks)
+                    np.cumsum([len(o) for o in out], out=seq_offsets[1:])
+                    flat = np.concatenate(out) if out else np.zeros(0, np.int32)
+                    ids[:flat.size].copy_(torch.from_numpy(flat))
+            ids = ids[:int(seq_offsets[-1])]
+        stats = {"word_model": model_mode, "device_call_s": time.perf_counter() - t0, "sequences": n_seq,
+                 "tokens": int(seq_offsets[-1])}
+        if model_mode == "host":
+            self.last_stats.update(stats)
+        else:
+            stats.update(words=sum(self.info(k) for k in ("last_words_lds_small", "last_words_lds",
+                                                          "last_words_global")) if n_seq else 0)
+            self.last_stats = stats
+        if to_host:
+            flat = ids.cpu().numpy()
+            return [flat[seq_offsets[i]:seq_offsets[i + 1]].copy() for i in range(n_seq)]
+        return ids, seq_offsets, seq_item

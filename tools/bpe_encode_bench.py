@@ -7,9 +7,15 @@ merges trained on them by the GPU trainer; the chunks, ``--repeat`` times over, 
 
     python tools/bpe_encode_bench.py --out profiles/bpe_encode_bench.txt
 
-Three stages, each a child process under its own time limit (a failed stage ends the run): ``corpus`` (GPU: engine
-encode + BPE training), ``gpu`` (the encoder: HIP events around the device work of ``mimi_bpe_encode``, wall time
-including the host word preparation), ``cpu`` (tokenizers with ``--threads`` threads; ids compared with the GPU's).
+Four stages, each a child process under its own time limit (a failed stage ends the run): ``corpus`` (GPU: engine
+encode + BPE training), ``gpu`` (the encoder with the host word model: HIP events around the device work of
+``mimi_bpe_encode``, wall time including the host word preparation), ``device`` (``Encoder.encode_device`` on the same
+chunks, uploaded once as one padded int32 tensor: wall time with the ids left on the device, wall time with
+``to_host=True``, HIP events around the call; ids asserted equal to the ``gpu`` stage's), ``cpu`` (tokenizers with
+``--threads`` threads; ids compared with the GPU's).
+
+    python tools/bpe_encode_bench.py --out profiles/bpe_encode_device_bench.txt
+
 ``--stage gpu --work DIR`` runs the encoder stage alone on a saved corpus (e.g. under ``rocprofv3 --kernel-trace
 --stats`` for the per-kernel split).
 """
@@ -106,6 +112,61 @@ def stage_gpu(args):
                      "what": "encode_codes: code points, NFKC word model, the GPU call, per-sequence arrays"}}
 
 
+def stage_device(args):
+    import torch
+
+    from mimi_hip import bpe
+    chunks = load_chunks(args)
+    enc = bpe.Encoder.from_tokenizer(os.path.join(args.work, "tokenizer.json"), K, CBS)
+    frames = [c.shape[1] for c in chunks]
+    padded = np.zeros((len(chunks), K, max(frames)), np.int32)
+    for b, c in enumerate(chunks):
+        padded[b, :, :c.shape[1]] = c
+    codes = torch.from_numpy(padded).cuda()  # uploaded once: the engine's output is already there
+    enc.encode_device(codes[:8], frames[:8])  # model upload
+    enc.encode_device(codes, frames)          # buffers
+    torch.cuda.synchronize()
+    wall, wall_host, dev_ms = [], [], []
+    for _ in range(args.runs):
+        t0 = time.perf_counter()
+        ids, offs, _ = enc.encode_device(codes, frames)
+        wall.append(time.perf_counter() - t0)
+    stats = dict(enc.last_stats)
+    forms = [enc.info("last_words_lds_small"), enc.info("last_words_lds"), enc.info("last_words_global")]
+    for _ in range(args.runs):
+        t0 = time.perf_counter()
+        seqs = enc.encode_device(codes, frames, to_host=True)
+        wall_host.append(time.perf_counter() - t0)
+    stream = torch.cuda.Stream()
+    for _ in range(args.runs):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        enc.encode_device(codes, frames, stream=stream)
+        b.record(stream)
+        b.synchronize()
+        dev_ms.append(a.elapsed_time(b))
+    with np.load(os.path.join(args.work, "gpu_ids.npz")) as z:
+        want_lens, want_ids = z["lens"], z["ids"]
+    assert np.array_equal(np.diff(offs), want_lens) and np.array_equal(ids.cpu().numpy(), want_ids), \
+        "encode_device ids differ from the gpu stage's"
+    assert np.array_equal([len(x) for x in seqs], want_lens) and np.array_equal(np.concatenate(seqs), want_ids)
+    tokens = int(offs[-1])
+    audio_s = sum(frames) / FR
+
+    def rate(seconds):
+        return {"seconds": round(seconds, 5), "tokens_per_s": round(tokens / seconds),
+                "audio_s_per_s": round(audio_s / seconds)}
+    return {"sequences": len(chunks), "words": stats["words"], "tokens": tokens, "word_model": stats["word_model"],
+            "words_by_form": forms, "same_ids_as_gpu": True,
+            "wall": dict(rate(min(wall)), all_runs_ms=[round(x * 1e3, 2) for x in wall],
+                         what="encode_device, ids left on the device (the call synchronises its stream)"),
+            "wall_to_host": dict(rate(min(wall_host)), all_runs_ms=[round(x * 1e3, 2) for x in wall_host],
+                                 what="encode_device(to_host=True): plus the copy out and one numpy array per sequence"),
+            "device": dict(rate(min(dev_ms) / 1e3), all_runs_ms=[round(x, 2) for x in dev_ms],
+                           what="HIP events around encode_device on its stream: kernels, the mid-way read-back, "
+                                "the offsets copy")}
+
+
 def stage_cpu(args):
     os.environ["RAYON_NUM_THREADS"] = str(args.threads)
     os.environ["TOKENIZERS_PARALLELISM"] = "true"
@@ -137,7 +198,8 @@ def stage_cpu(args):
     return out
 
 
-STAGES = {"corpus": (stage_corpus, 420), "gpu": (stage_gpu, 240), "cpu": (stage_cpu, 420)}
+STAGES = {"corpus": (stage_corpus, 420), "gpu": (stage_gpu, 240), "device": (stage_device, 240),
+          "cpu": (stage_cpu, 420)}
 
 
 def main():
@@ -173,6 +235,12 @@ def main():
     if "gpu" in report and "device" in report["gpu"] and report.get("cpu", {}).get("tokens_per_s"):
         report["gpu_device_over_tokenizers"] = round(report["gpu"]["device"]["tokens_per_s"] / report["cpu"]["tokens_per_s"], 2)
         report["gpu_wall_over_tokenizers"] = round(report["gpu"]["wall"]["tokens_per_s"] / report["cpu"]["tokens_per_s"], 2)
+    if "wall" in report.get("device", {}) and report.get("cpu", {}).get("tokens_per_s"):
+        cpu = report["cpu"]["tokens_per_s"]
+        for key in ("wall", "wall_to_host", "device"):
+            report[f"device_{key}_over_tokenizers"] = round(report["device"][key]["tokens_per_s"] / cpu, 2)
+        report["device_wall_over_gpu_wall"] = round(report["device"]["wall"]["tokens_per_s"] /
+                                                    report["gpu"]["wall"]["tokens_per_s"], 2)
     text = json.dumps(report, indent=1)
     print(text)
     if args.out:
