@@ -31,7 +31,9 @@ Stages (output tap <- inputs: operation; n = accumulated terms + epilogue operat
                       (``Stage.interior``, ``ds_interior``: the rows that read no padding)      n = K + 2
     downsample     <- xfmr7: the same conv replicate-padded at each item's ends                          n = K + 2
     proj           <- downsample: [W_sem | W_ac] input projections                                       n = K + 2
-(K = taps x input channels.)  RVQ is not here: proj -> codes is held bit-exact by the quantizer tests.
+(K = taps x input channels.)  RVQ is not here: proj -> codes is audited in float64 by tests/rvq_ref.py and
+tests/test_rvq_kernels.py (adversarial residuals and codebooks on every kernel form), beside the bit-exact quantizer
+tests on natural embeddings (tests/test_gpu_parity.py).
 
 CONDITION SUMS (derived, not fitted).  A stage's mag64 bounds, element by element, the first-order error of ANY
 evaluation of it in units of u = 2^-24: every partial result's rounding error is at most its own n_i u times a

@@ -2672,6 +2672,7 @@ extern "C" int mimi_rvq_encode(mimi_engine* e, const float* emb, int64_t frames,
     const char* kname = "?";
     LAUNCH_TRY(launch_gemm(ROLE_INPROJ, ap, s, &kname), "input_proj");
     rec.mark("input_proj", 2.0 * frames * Hd * 2 * Dq, 0, kname);
+    if ((rc = save_tap(e, "proj", proj, 1, frames, 2 * Dq, s))) return rc;  // (the quantizer's own input)
     PassCtx ctx{lane, s, e->precision};
     ctx.chain_ok = true;  // (checked right here: a give-up re-runs the levels on the per-level kernels)
     PassOut out;
