@@ -1,13 +1,16 @@
 // Host-ingest resampler on the GPU: the polyphase (upfirdn) resampling of librosa's res_type='polyphase'
 // (= scipy.signal.resample_poly, Kaiser(5.0) low-pass of 2*10*max(up,down)+1 taps), bit-exact with scipy on
-// float32 input.  Ref call sites: librosa.load(path, sr=24000) in librispeech-mimi/utils.py:84-87,
-// emilia-mimi/process_shard.py:479-482, yodas2-mimi/process_shard.py:389 (their default soxr_hq mode is
-// libsoxr, absent here: unpinned).
+// float32 input, subnormal, Inf and NaN samples included.  Ref call sites: librosa.load(path, sr=24000)
+// in librispeech-mimi/utils.py:84-87, emilia-mimi/process_shard.py:479-482, yodas2-mimi/process_shard.py:389
+// (their default soxr_hq mode is libsoxr, absent here: unpinned).
 //
 // Output m of a clip sits at up-sampled position p = (m + pre_remove) * down and is the sum over input
-// samples j in [ceil((p - (lh-1)) / up), min(p / up, n_in - 1)] of x[j] * h[p - j*up], added in ASCENDING j
+// samples j in [ceil((p - (lhp-1)) / up), min(p / up, n_in - 1)] of x[j] * h[p - j*up], added in ASCENDING j
 // to a 0-initialised fp32 accumulator with one rounding per product and per add -- the inner-loop order of
-// scipy's upfirdn (_upfirdn_apply.pyx), which is what makes the result bitwise equal.
+// scipy's upfirdn (_upfirdn_apply.pyx), which is what makes the result bitwise equal.  lhp = ceil(lh / up) * up:
+// upfirdn pads every filter phase with zeros to ceil(lh / up) taps, so where up does not divide lh the first term
+// of some outputs is x[j] * 0 with a padding tap (index >= lh).  It adds +0 for a finite sample and NaN for an
+// Inf / NaN one, and is computed here as scipy computes it, never read from the filter.
 //
 // HBM-bound byte work: 4 B read per input sample, 4 B written per output (x re-reads of neighbouring outputs
 // are served from LDS: each pass stages its input window once, coalesced); the filter sits in LDS too.  One
@@ -37,7 +40,8 @@ __device__ __forceinline__ long long pass_w0(long long m0, long long pre_remove,
 
 // WPT > 0: the next pass's window (<= WPT * 256 samples) is loaded into registers while this pass computes, then
 // stored into the other half of a double-buffered LDS window (one barrier per pass, HBM latency hidden);
-// WPT == 0: load-then-compute (windows over 1024 samples: extreme ratios only)
+// WPT == 0: load-then-compute, the window derived from m0 at the top of every pass (windows over 1024 samples:
+// extreme ratios only)
 // UPC > 0: the up-sampling factor as a compile-time constant (1: 48/72/96 -> 24 kHz, 3: 8/16 -> 24 kHz), so the
 // unrolled tap loop's LDS addresses are immediate offsets from two bases (2 ds_read + mul + add per tap); 0:
 // any factor, read at run time
@@ -64,16 +68,18 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_poly_kernel(const float* __
     const long long n_in = in_len[c], n_out = out_len[c];
     const float* __restrict__ xc = x + in_off[c];
     float* __restrict__ yc = y + out_off[c];
-    // jlo(p) = max(ceil((p - (lh-1)) / up), 0), jhi(p) = min(floor(p / up), n_in - 1).  64-bit divisions only
-    // once per pass (wave-uniform); per output, p = q0*up + pr with pr = r0 + tid*down < 2^31, so the rest is
-    // 32-bit: ceil((pr - (lh-1)) / up) = (pr - (lh-1) + kc*up + up-1) / up - kc with kc*up >= lh-1
-    const int kc = (lh - 1 + up - 1) / up;
+    // jlo(p) = max(ceil((p - (lhp-1)) / up), 0), jhi(p) = min(floor(p / up), n_in - 1), lhp the filter length with
+    // scipy's phase padding.  64-bit divisions only once per pass (wave-uniform); per output, p = q0*up + pr with
+    // pr = r0 + tid*down < 2^31, so the rest is 32-bit:
+    // ceil((pr - (lhp-1)) / up) = (pr - (lhp-1) + kc*up + up-1) / up - kc with kc*up >= lhp-1
+    const int lhp = (lh + up - 1) / up * up;
+    const int kc = (lhp - 1 + up - 1) / up;
     const long long mstep = (long long)gridDim.x * RS_BLOCK;
     long long m0 = (long long)blockIdx.x * RS_BLOCK;
     if (m0 >= n_out) return;  // whole workgroup: uniform
     long long q0;
     int r0;
-    long long w0 = pass_w0(m0, pre_remove, lh, up, down, kc, &q0, &r0);
+    long long w0 = pass_w0(m0, pre_remove, lhp, up, down, kc, &q0, &r0);
     float pf[WPT > 0 ? WPT : 1];
     if (WPT > 0) {
 #pragma unroll
@@ -90,7 +96,7 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_poly_kernel(const float* __
         int rn = 0;
         if (WPT > 0) {
             // issue the next pass's window loads now; they land while this pass computes
-            if (mn < n_out) wn = pass_w0(mn, pre_remove, lh, up, down, kc, &qn, &rn);
+            if (mn < n_out) wn = pass_w0(mn, pre_remove, lhp, up, down, kc, &qn, &rn);
 #pragma unroll
             for (int u = 0; u < WPT; ++u) {
                 const int i = tid + u * RS_BLOCK;
@@ -98,6 +104,8 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_poly_kernel(const float* __
                 pf[u] = (mn < n_out && i < W && j < n_in) ? xc[j] : 0.0f;
             }
         } else {
+            // no prefetch hands this pass its window: derive it from m0 (wave-uniform)
+            w0 = pass_w0(m0, pre_remove, lhp, up, down, kc, &q0, &r0);
             __syncthreads();  // previous pass done with xs
             for (int i = tid; i < W; i += RS_BLOCK) {
                 const long long j = w0 + i;
@@ -109,14 +117,19 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_poly_kernel(const float* __
         if (m < n_out) {
             const int pr = r0 + tid * down;
             const long long jhi = min(q0 + pr / up, n_in - 1);
-            const long long jlo = max(q0 + (pr - (lh - 1) + kc * up + up - 1) / up - kc, 0LL);
+            const long long jlo = max(q0 + (pr - (lhp - 1) + kc * up + up - 1) / up - kc, 0LL);
             float acc = 0.0f;
-            const int k = pr - (int)(jlo - q0) * up;  // filter index of the first term (< lh)
+            const int k = pr - (int)(jlo - q0) * up;  // filter index of the first term (< lhp; the others < lh)
             const float* xp = xs + (int)(jlo - w0);
             const float* hp = hs + k;
             const int cnt = (int)(jhi - jlo + 1);
+            int t = 0;
+            if (k >= lh && cnt > 0) {  // scipy's padding tap: +0 unless the sample is Inf / NaN
+                acc = __fadd_rn(acc, __fmul_rn(xp[0], 0.0f));
+                t = 1;
+            }
 #pragma unroll 8
-            for (int t = 0; t < cnt; ++t) acc = __fadd_rn(acc, __fmul_rn(xp[t], hp[-t * up]));
+            for (; t < cnt; ++t) acc = __fadd_rn(acc, __fmul_rn(xp[t], hp[-t * up]));
             yc[m] = acc;
         }
         if (WPT > 0) {
@@ -151,10 +164,11 @@ struct RsFir {
     static constexpr int HALF = 10 * MR;
     static constexpr int PREPAD = DOWN - HALF % DOWN;
     static constexpr int LH = 2 * HALF + 1 + PREPAD;     // filter taps incl. the zero pre-padding
+    static constexpr int LHP = (LH + UP - 1) / UP * UP;  // ... and scipy's zero padding of every phase to LHP / UP taps
     static constexpr int PRE = (HALF + PREPAD) / DOWN;   // n_pre_remove
     static constexpr int C0 = (PRE * DOWN) % UP;         // p(m0) mod up for m0 = 0 (mod up)
     // output r of a thread's group (its first output at m = 0 mod up):
-    static constexpr int jlo(int r) { return rs_cdiv(C0 + r * DOWN - (LH - 1), UP); }  // relative to floor(p0/up)
+    static constexpr int jlo(int r) { return rs_cdiv(C0 + r * DOWN - (LHP - 1), UP); }  // relative to floor(p0/up)
     static constexpr int jhi(int r) { return rs_fdiv(C0 + r * DOWN, UP); }
     static constexpr int off(int r) { return jlo(r) - jlo(0); }                          // input offset of output r
     static constexpr int cnt(int r) { return jhi(r) - jlo(r) + 1; }                      // its taps
@@ -187,7 +201,8 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_fir_kernel(const float* __r
 #pragma unroll
     for (int r = 0; r < UP; ++r)
 #pragma unroll
-        for (int i = 0; i < NT; ++i) hr[r][i] = i < F::cnt(r) ? h[F::kfirst(r) - i * UP] : 0.0f;
+        for (int i = 0; i < NT; ++i)  // (a first index >= LH is a padding tap: zero)
+            hr[r][i] = (i < F::cnt(r) && F::kfirst(r) - i * UP < LH) ? h[F::kfirst(r) - i * UP] : 0.0f;
     const int c = blockIdx.y;
     const long long n_in = in_len[c], n_out = out_len[c];
     const float* __restrict__ xc = x + in_off[c];
@@ -217,16 +232,19 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_fir_kernel(const float* __r
             }
         } else {
             // edge pass: each output on its own (clamped j range, taps from LDS, inputs from global)
-            const int kc = (LH - 1 + UP - 1) / UP;
+            const int kc = (F::LHP - 1 + UP - 1) / UP;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const long long m = m0 + (long long)tid * R + r;
                 if (m >= n_out) continue;
                 const long long p = (m + PRE) * DOWN;
                 const long long jhi = min(p / UP, n_in - 1);
-                const long long jlo = max((p - (LH - 1) + (long long)kc * UP + UP - 1) / UP - kc, 0LL);  // ceil
+                const long long jlo = max((p - (F::LHP - 1) + (long long)kc * UP + UP - 1) / UP - kc, 0LL);  // ceil
                 float acc = 0.0f;
-                for (long long j = jlo; j <= jhi; ++j) acc = __fadd_rn(acc, __fmul_rn(xc[j], hs[p - j * UP]));
+                for (long long j = jlo; j <= jhi; ++j) {
+                    const long long k = p - j * UP;  // >= LH: a padding tap
+                    acc = __fadd_rn(acc, __fmul_rn(xc[j], k < LH ? hs[k] : 0.0f));
+                }
                 yc[m] = acc;
             }
         }
