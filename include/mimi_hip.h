@@ -368,11 +368,47 @@ int mimi_flac_decode(const uint8_t* data, int64_t nbytes, int32_t* out, int64_t 
  * highest count (ties: smallest (left, right); count 0 when none is left), the caller decides the new token's
  * id (a new one, or the id of an existing token with the same spelling) and length, and mimi_bpe_merge applies
  * it to every word.  Ids up to 131071.
+ *
+ * mimi_bpe_create_opts: the same with options (NULL or all zero: mimi_bpe_create exactly).  min_table_slots: the
+ * floor of the pair table's size and the room it gets beyond 4x the initial pairs (default 2^20); a power of two,
+ * at least 8 * vocab_size: one merge forms at most 2 * vocab_size distinct new pairs, mimi_bpe_best doubles the
+ * table once more than half its slots hold a key, so the load stays <= 1/2 + 2/8 = 3/4 and an update never meets a
+ * full table (it would be dropped).  grid_blocks: workgroups of every launch (default: 8 per compute unit); >= 1.
+ * Anything else returns MIMI_ERR_INVALID_ARGUMENT before any device call.  Both exist so that tests reach the
+ * table's growth and the kernels' grid-stride loops on small corpora.
+ *
+ * mimi_bpe_info: *value = the figure named by `what` (MIMI_BPE_TRAIN_INFO_*).
+ *
+ * Read-back for tests; both synchronise the handle's stream and change nothing.  mimi_bpe_read_pairs: every pair
+ * with a positive count, unordered, into left / right / count (capacity `cap` entries each); *n_pairs receives
+ * their number; all three arrays NULL: the number alone; cap too small: MIMI_ERR_INVALID_ARGUMENT.
+ * mimi_bpe_read_words: the current symbols of every word, concatenated in word order into symbols (capacity cap),
+ * word w's current length into word_lengths[w] (n_words = the corpus's), *n_symbols = the live symbols; both arrays
+ * NULL: the number alone.  The host walks the forward links from each word's first position and returns
+ * MIMI_ERR_STATE when a back link disagrees (prv[nxt[p]] != p), a dead symbol is linked, a link leaves its word or
+ * cycles, or a live symbol is unreachable.
  */
 typedef struct mimi_bpe mimi_bpe;
+typedef struct mimi_bpe_options {
+    int64_t min_table_slots; /* 0: 2^20 */
+    int32_t grid_blocks;     /* 0: 8 per compute unit */
+    int32_t reserved;        /* 0 */
+} mimi_bpe_options;
+#define MIMI_BPE_TRAIN_INFO_TABLE_SLOTS 0     /* capacity of the pair table */
+#define MIMI_BPE_TRAIN_INFO_NKEYS 1           /* keys inserted since the table was last rebuilt (dead ones included) */
+#define MIMI_BPE_TRAIN_INFO_GROWTH_REHASHES 2 /* doublings by mimi_bpe_best so far */
+#define MIMI_BPE_TRAIN_INFO_GRID_BLOCKS 3     /* workgroups per launch */
+#define MIMI_BPE_TRAIN_INFO_SYMBOLS 4         /* symbols of the corpus (positions, live or dead) */
 int mimi_bpe_create(int device, const int32_t* symbols, int64_t n_symbols, const int64_t* word_offsets,
                     const int64_t* word_counts, int64_t n_words, int32_t n_initial_tokens, int32_t vocab_size,
                     int32_t max_token_length, mimi_bpe** out);
+int mimi_bpe_create_opts(int device, const int32_t* symbols, int64_t n_symbols, const int64_t* word_offsets,
+                         const int64_t* word_counts, int64_t n_words, int32_t n_initial_tokens, int32_t vocab_size,
+                         int32_t max_token_length, const mimi_bpe_options* opts, mimi_bpe** out);
+int mimi_bpe_info(mimi_bpe* h, int32_t what, int64_t* value);
+int mimi_bpe_read_pairs(mimi_bpe* h, int32_t* left, int32_t* right, int64_t* count, int64_t cap, int64_t* n_pairs);
+int mimi_bpe_read_words(mimi_bpe* h, int32_t* symbols, int64_t cap, int64_t* word_lengths, int64_t n_words,
+                        int64_t* n_symbols);
 int mimi_bpe_best(mimi_bpe* h, int32_t* left, int32_t* right, int64_t* count);
 int mimi_bpe_merge(mimi_bpe* h, int32_t left, int32_t right, int32_t new_id, int32_t new_len);
 void mimi_bpe_destroy(mimi_bpe* h);

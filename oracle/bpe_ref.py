@@ -23,11 +23,12 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 
 def train_bpe(words: Sequence[Sequence[int]], counts: Sequence[int], n_base: int, n_special: int, vocab_size: int,
-              min_frequency: int = 2, max_token_length: Optional[int] = None, trace: Optional[list] = None
-              ) -> Tuple[List[Tuple[int, ...]], List[Tuple[int, int]]]:
+              min_frequency: int = 2, max_token_length: Optional[int] = None, trace: Optional[list] = None,
+              pairs_trace: Optional[list] = None) -> Tuple[List[Tuple[int, ...]], List[Tuple[int, int]]]:
     """words: symbol ids (ids n_special .. n_special + n_base - 1 are the alphabet, in code point order).
     Returns (tokens, merges): tokens[i] = the alphabet indices (0-based) spelling token i >= n_special;
-    merges = (left id, right id) in merge order."""
+    merges = (left id, right id) in merge order.  pairs_trace receives the positive pair counts before every merge
+    and after the last one (entry s: the state after s merges)."""
     tokens: List[Tuple[int, ...]] = [()] * n_special + [(i,) for i in range(n_base)]
     tok_id: Dict[Tuple[int, ...], int] = {t: i for i, t in enumerate(tokens) if i >= n_special}
     words = [list(w) for w in words]
@@ -65,6 +66,8 @@ def train_bpe(words: Sequence[Sequence[int]], counts: Sequence[int], n_base: int
         merges.append(pair)
         if trace is not None:
             trace.append((cur, dict(pc)) if len(trace) < 3 else cur)
+        if pairs_trace is not None:
+            pairs_trace.append({p: c for p, c in pc.items() if c > 0})
         touched = {}
         for wi in sorted(where.get(pair, ())):
             w = words[wi]
@@ -97,4 +100,6 @@ def train_bpe(words: Sequence[Sequence[int]], counts: Sequence[int], n_base: int
             where.setdefault(p, set()).update(ws)
             if pc.get(p, 0) > 0:
                 heapq.heappush(heap, (-pc[p], p))
+    if pairs_trace is not None:
+        pairs_trace.append({p: c for p, c in pc.items() if c > 0})
     return tokens, merges

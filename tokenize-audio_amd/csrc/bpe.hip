@@ -239,6 +239,10 @@ struct mimi_bpe {
     Table t{};
     unsigned long long* host = nullptr;  // pinned: best count, best pair, nkeys
     int grid = 1024;
+    unsigned long long min_slots = 1024;   // floor of every table size (pow2_at_least)
+    unsigned long long room_slots = 1ull << 20;  // the constant term of the post-count size
+    long long growth_rehashes = 0;         // doublings by mimi_bpe_best
+    std::vector<int64_t> first, wlen;      // each word's first position and initial length (mimi_bpe_read_words)
 };
 
 #define BPE_TRY(expr)                                                                                       \
@@ -271,8 +275,8 @@ static void table_free(Table& t) {
     t = Table{};
 }
 
-static unsigned long long pow2_at_least(unsigned long long x) {
-    unsigned long long c = 1024;
+static unsigned long long pow2_at_least(unsigned long long x, unsigned long long floor) {
+    unsigned long long c = floor;
     while (c < x) c <<= 1;
     return c;
 }
@@ -309,17 +313,41 @@ extern "C" void mimi_bpe_destroy(mimi_bpe* h) {
 extern "C" int mimi_bpe_create(int device, const int32_t* symbols, int64_t n_symbols, const int64_t* word_offsets,
                                const int64_t* word_counts, int64_t n_words, int32_t n_initial_tokens,
                                int32_t vocab_size, int32_t max_token_length, mimi_bpe** out) {
+    return mimi_bpe_create_opts(device, symbols, n_symbols, word_offsets, word_counts, n_words, n_initial_tokens,
+                                vocab_size, max_token_length, nullptr, out);
+}
+
+extern "C" int mimi_bpe_create_opts(int device, const int32_t* symbols, int64_t n_symbols,
+                                    const int64_t* word_offsets, const int64_t* word_counts, int64_t n_words,
+                                    int32_t n_initial_tokens, int32_t vocab_size, int32_t max_token_length,
+                                    const mimi_bpe_options* opts, mimi_bpe** out) {
     if (!out) return fail(MIMI_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
-    if (n_symbols < 0 || n_words < 0 || (n_symbols > 0 && (!symbols || !word_offsets || !word_counts)))
+    if (n_symbols < 0 || n_words < 0 || (n_symbols > 0 && (!symbols || !word_offsets || !word_counts)) ||
+        (n_words > 0 && (!word_offsets || !word_counts)))
         return fail(MIMI_ERR_INVALID_ARGUMENT, "bad corpus arguments");
     if (n_initial_tokens < 1 || vocab_size < n_initial_tokens || (unsigned)vocab_size > kMaxId)
         return fail(MIMI_ERR_INVALID_ARGUMENT, "vocab_size %d must be in [%d, %u]", vocab_size, n_initial_tokens,
                     kMaxId);
     if (n_symbols >= (1ll << 31)) return fail(MIMI_ERR_UNSUPPORTED, "more than 2^31 symbols");
+    // The table's invariant.  table_add drops an update silently when it probes a full table, so the table must
+    // never fill.  One merge forms at most 2 * vocab_size distinct new keys, (x, new) and (new, y).  mimi_bpe_best
+    // doubles the table when more than half its slots hold a key, so a merge starts at load <= 1/2; with at least
+    // 8 * vocab_size slots it ends at load <= 1/2 + 2 / 8 = 3/4.  Hence min_table_slots >= 8 * vocab_size; the
+    // default 2^20 = 8 * 131072 covers every vocab_size the id packing allows.
+    const int64_t min_table_slots = opts ? opts->min_table_slots : 0;
+    const int32_t grid_blocks = opts ? opts->grid_blocks : 0;
+    if (min_table_slots < 0 || (min_table_slots & (min_table_slots - 1)) != 0 || min_table_slots > (1ll << 40))
+        return fail(MIMI_ERR_INVALID_ARGUMENT, "min_table_slots %lld must be a power of two (0: the default)",
+                    (long long)min_table_slots);
+    if (min_table_slots && min_table_slots < 8ll * vocab_size)
+        return fail(MIMI_ERR_INVALID_ARGUMENT, "min_table_slots %lld is below 8 x vocab_size = %lld",
+                    (long long)min_table_slots, 8ll * vocab_size);
+    if (grid_blocks < 0 || grid_blocks > (1 << 20))
+        return fail(MIMI_ERR_INVALID_ARGUMENT, "grid_blocks %d must be in [1, 2^20] (0: the default)", grid_blocks);
     // host: links and per-symbol word counts (pair counts are int64 on the device: no corpus-size limit)
     std::vector<int> nxt(n_symbols), prv(n_symbols), wc(n_symbols);
-    if (n_words > 0 && (word_offsets[0] != 0 || word_offsets[n_words] != n_symbols))
+    if (n_words == 0 ? n_symbols != 0 : (word_offsets[0] != 0 || word_offsets[n_words] != n_symbols))
         return fail(MIMI_ERR_INVALID_ARGUMENT, "word offsets must run from 0 to n_symbols");
     for (int64_t w = 0; w < n_words; ++w) {
         const int64_t b0 = word_offsets[w], b1 = word_offsets[w + 1];
@@ -336,6 +364,9 @@ extern "C" int mimi_bpe_create(int device, const int32_t* symbols, int64_t n_sym
     }
     std::unique_ptr<mimi_bpe> h(new mimi_bpe());
     mimi_bpe* H = h.get();
+    H->first.assign(word_offsets, word_offsets + n_words);
+    H->wlen.resize((size_t)n_words);
+    for (int64_t w = 0; w < n_words; ++w) H->wlen[w] = word_offsets[w + 1] - word_offsets[w];
     H->device = device;
     H->n = n_symbols;
     H->vocab = vocab_size;
@@ -366,15 +397,16 @@ extern "C" int mimi_bpe_create(int device, const int32_t* symbols, int64_t n_sym
     }
     int dev_cu = 256;
     (void)hipDeviceGetAttribute(&dev_cu, hipDeviceAttributeMultiprocessorCount, device);
-    H->grid = std::max(64, dev_cu * 8);
-    int rc = table_alloc(H->t, pow2_at_least(2ull * (unsigned long long)nb + 1024), H->s);
+    H->grid = grid_blocks ? grid_blocks : std::max(64, dev_cu * 8);
+    if (min_table_slots) H->min_slots = H->room_slots = (unsigned long long)min_table_slots;
+    int rc = table_alloc(H->t, pow2_at_least(2ull * (unsigned long long)nb + 1024, H->min_slots), H->s);
     if (rc) return rc;
     hipLaunchKernelGGL(count_pairs_kernel, dim3(H->grid), dim3(256), 0, H->s, H->sym, H->nxt, H->wc, H->n, H->t);
     BPE_TRY(hipGetLastError());
     BPE_TRY(hipMemcpyAsync(H->host + 1, H->t.nkeys, 8, hipMemcpyDeviceToHost, H->s));
     BPE_TRY(hipStreamSynchronize(H->s));
-    // room for the pairs the merges will form: 4x the distinct initial pairs, at least 2^20 slots
-    if ((rc = rehash(H, pow2_at_least(4ull * H->host[1] + (1ull << 20))))) return rc;
+    // room for the pairs the merges will form: 4x the distinct initial pairs, at least 2^20 slots (min_table_slots)
+    if ((rc = rehash(H, pow2_at_least(4ull * H->host[1] + H->room_slots, H->min_slots)))) return rc;
     *out = h.release();
     return MIMI_OK;
 }
@@ -400,6 +432,7 @@ extern "C" int mimi_bpe_best(mimi_bpe* h, int32_t* left, int32_t* right, int64_t
     if (2 * h->host[2] > slots) {
         int rc = rehash(h, slots * 2);
         if (rc) return rc;
+        ++h->growth_rehashes;
     }
     return MIMI_OK;
 }
@@ -427,5 +460,103 @@ extern "C" int mimi_bpe_merge(mimi_bpe* h, int32_t left, int32_t right, int32_t 
     hipLaunchKernelGGL(zero_pair_kernel, dim3(1), dim3(1), 0, h->s, h->t,
                        ((unsigned long long)(unsigned)left << 32) | (unsigned)right);
     BPE_TRY(hipGetLastError());
+    return MIMI_OK;
+}
+
+extern "C" int mimi_bpe_info(mimi_bpe* h, int32_t what, int64_t* value) {
+    if (!h || !value) return fail(MIMI_ERR_INVALID_ARGUMENT, "null argument");
+    switch (what) {
+        case MIMI_BPE_TRAIN_INFO_TABLE_SLOTS: *value = (int64_t)(h->t.mask + 1); return MIMI_OK;
+        case MIMI_BPE_TRAIN_INFO_GROWTH_REHASHES: *value = h->growth_rehashes; return MIMI_OK;
+        case MIMI_BPE_TRAIN_INFO_GRID_BLOCKS: *value = h->grid; return MIMI_OK;
+        case MIMI_BPE_TRAIN_INFO_SYMBOLS: *value = h->n; return MIMI_OK;
+        case MIMI_BPE_TRAIN_INFO_NKEYS: {
+            unsigned long long nk = 0;
+            BPE_TRY(hipSetDevice(h->device));
+            BPE_TRY(hipStreamSynchronize(h->s));
+            BPE_TRY(hipMemcpy(&nk, h->t.nkeys, 8, hipMemcpyDeviceToHost));
+            *value = (int64_t)nk;
+            return MIMI_OK;
+        }
+    }
+    return fail(MIMI_ERR_INVALID_ARGUMENT, "no training info %d", what);
+}
+
+extern "C" int mimi_bpe_read_pairs(mimi_bpe* h, int32_t* left, int32_t* right, int64_t* count, int64_t cap,
+                                   int64_t* n_pairs) {
+    if (!h || !n_pairs) return fail(MIMI_ERR_INVALID_ARGUMENT, "null argument");
+    BPE_TRY(hipSetDevice(h->device));
+    BPE_TRY(hipStreamSynchronize(h->s));
+    const size_t slots = (size_t)(h->t.mask + 1);
+    std::vector<unsigned long long> keys(slots), vals(slots);
+    BPE_TRY(hipMemcpy(keys.data(), h->t.keys, slots * 8, hipMemcpyDeviceToHost));
+    BPE_TRY(hipMemcpy(vals.data(), h->t.vals, slots * 8, hipMemcpyDeviceToHost));
+    int64_t n = 0;
+    for (size_t i = 0; i < slots; ++i) n += keys[i] != kEmpty && (long long)vals[i] > 0;
+    *n_pairs = n;
+    if (!left && !right && !count) return MIMI_OK;  // the count alone
+    if (!left || !right || !count) return fail(MIMI_ERR_INVALID_ARGUMENT, "null argument");
+    if (cap < n) return fail(MIMI_ERR_INVALID_ARGUMENT, "the table holds %lld live pairs", (long long)n);
+    int64_t o = 0;
+    for (size_t i = 0; i < slots; ++i)
+        if (keys[i] != kEmpty && (long long)vals[i] > 0) {
+            left[o] = (int32_t)(keys[i] >> 32);
+            right[o] = (int32_t)(unsigned)keys[i];
+            count[o++] = (int64_t)vals[i];
+        }
+    return MIMI_OK;
+}
+
+extern "C" int mimi_bpe_read_words(mimi_bpe* h, int32_t* symbols, int64_t cap, int64_t* word_lengths,
+                                   int64_t n_words, int64_t* n_symbols) {
+    if (!h || !n_symbols) return fail(MIMI_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_words != (int64_t)h->first.size())
+        return fail(MIMI_ERR_INVALID_ARGUMENT, "the corpus has %lld words", (long long)h->first.size());
+    BPE_TRY(hipSetDevice(h->device));
+    BPE_TRY(hipStreamSynchronize(h->s));
+    const size_t n = (size_t)h->n;
+    std::vector<int> sym(n), nxt(n), prv(n);
+    if (n) {
+        BPE_TRY(hipMemcpy(sym.data(), h->sym, n * 4, hipMemcpyDeviceToHost));
+        BPE_TRY(hipMemcpy(nxt.data(), h->nxt, n * 4, hipMemcpyDeviceToHost));
+        BPE_TRY(hipMemcpy(prv.data(), h->prv, n * 4, hipMemcpyDeviceToHost));
+    }
+    int64_t live = 0;
+    for (size_t p = 0; p < n; ++p) {
+        if (sym[p] >= 0) {
+            ++live;
+            continue;
+        }
+        if (nxt[p] != -1 || prv[p] != -1)
+            return fail(MIMI_ERR_STATE, "dead symbol %lld is linked (nxt %d, prv %d)", (long long)p, nxt[p], prv[p]);
+    }
+    *n_symbols = live;
+    if (!symbols && !word_lengths) return MIMI_OK;  // the count alone (dead symbols checked)
+    if (!symbols || !word_lengths) return fail(MIMI_ERR_INVALID_ARGUMENT, "null argument");
+    if (cap < live) return fail(MIMI_ERR_INVALID_ARGUMENT, "the words hold %lld symbols", (long long)live);
+    // walk nxt from each word's first position (always alive: a first position can start an occurrence, never be
+    // its partner); at most `live` steps in all, so a cycle ends the walk
+    int64_t o = 0;
+    for (int64_t w = 0; w < n_words; ++w) {
+        const int64_t p0 = h->first[w], p1 = h->first[w] + h->wlen[w];
+        int64_t len = 0;
+        if (p1 > p0 && prv[p0] != -1) return fail(MIMI_ERR_STATE, "word %lld: its first symbol has prv %d",
+                                                  (long long)w, prv[p0]);
+        for (int64_t p = p1 > p0 ? p0 : -1; p >= 0; p = nxt[p]) {
+            if (p < p0 || p >= p1) return fail(MIMI_ERR_STATE, "word %lld: link to %lld leaves the word",
+                                               (long long)w, (long long)p);
+            if (sym[p] < 0) return fail(MIMI_ERR_STATE, "word %lld: dead symbol %lld is linked", (long long)w,
+                                        (long long)p);
+            if (o >= live) return fail(MIMI_ERR_STATE, "word %lld: the links cycle", (long long)w);
+            const int q = nxt[p];
+            if (q >= 0 && (q >= (int64_t)n || prv[q] != p))
+                return fail(MIMI_ERR_STATE, "word %lld: prv[nxt[%lld]] = %d", (long long)w, (long long)p,
+                            q < (int64_t)n ? prv[q] : -2);
+            symbols[o++] = sym[p];
+            ++len;
+        }
+        word_lengths[w] = len;
+    }
+    if (o != live) return fail(MIMI_ERR_STATE, "%lld live symbols are unreachable", (long long)(live - o));
     return MIMI_OK;
 }

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "mimi_decode_ragged", "mimi_decode_ragged_workspace_bytes",
     "mimi_bpe_model_create", "mimi_bpe_model_destroy", "mimi_bpe_encode", "mimi_bpe_model_info",
     "mimi_bpe_model_set_alphabet", "mimi_bpe_encode_codes",
+    "mimi_bpe_create_opts", "mimi_bpe_info", "mimi_bpe_read_pairs", "mimi_bpe_read_words",
 )
 CREATE_DECODE = 1  # MIMI_CREATE_DECODE
 RESAMPLE_MAX_TAPS = 65536  # MIMI_RESAMPLE_MAX_TAPS
@@ -44,6 +45,13 @@ BPE_WORDS_SCAN_TILE = 2048  # MIMI_BPE_WORDS_SCAN_TILE
 # MIMI_BPE_INFO_*
 BPE_INFO = {"pairs": 0, "formed_pair_outranks": 1, "table_slots": 2, "last_words_lds_small": 3, "last_words_lds": 4,
             "last_words_global": 5}
+# MIMI_BPE_TRAIN_INFO_*
+BPE_TRAIN_INFO = {"table_slots": 0, "nkeys": 1, "growth_rehashes": 2, "grid_blocks": 3, "symbols": 4}
+
+
+class BpeOptionsC(ctypes.Structure):
+    """mimi_bpe_options"""
+    _fields_ = [("min_table_slots", ctypes.c_int64), ("grid_blocks", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class MimiConfigC(ctypes.Structure):
@@ -129,6 +137,11 @@ def _declare(lib):
         "mimi_get_tap": (c.c_int, [vp, c.c_char_p, vp, c.c_int64, c.POINTER(c.c_int64), c.POINTER(c.c_int64)]),
         "mimi_bpe_create": (c.c_int, [c.c_int, vp, c.c_int64, vp, vp, c.c_int64, c.c_int32, c.c_int32, c.c_int32,
                                       c.POINTER(vp)]),
+        "mimi_bpe_create_opts": (c.c_int, [c.c_int, vp, c.c_int64, vp, vp, c.c_int64, c.c_int32, c.c_int32, c.c_int32,
+                                           c.POINTER(BpeOptionsC), c.POINTER(vp)]),
+        "mimi_bpe_info": (c.c_int, [vp, c.c_int32, c.POINTER(c.c_int64)]),
+        "mimi_bpe_read_pairs": (c.c_int, [vp, vp, vp, vp, c.c_int64, c.POINTER(c.c_int64)]),
+        "mimi_bpe_read_words": (c.c_int, [vp, vp, c.c_int64, vp, c.c_int64, c.POINTER(c.c_int64)]),
         "mimi_bpe_best": (c.c_int, [vp, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(c.c_int64)]),
         "mimi_bpe_merge": (c.c_int, [vp, c.c_int32, c.c_int32, c.c_int32, c.c_int32]),
         "mimi_bpe_destroy": (None, [vp]),

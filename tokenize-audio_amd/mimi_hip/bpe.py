@@ -317,10 +317,13 @@ class Trainer:
 
 def train_words_gpu(words: Sequence[np.ndarray], counts: np.ndarray, n_base: int, n_special: int, vocab_size: int,
                     min_frequency: int, max_token_length: Optional[int], device: int = 0,
-                    stats: Optional[dict] = None) -> Tuple[List[Tuple[int, ...]], List[Tuple[int, int]]]:
+                    stats: Optional[dict] = None, *, min_table_slots: Optional[int] = None,
+                    grid_blocks: Optional[int] = None) -> Tuple[List[Tuple[int, ...]], List[Tuple[int, int]]]:
     """The merge loop on the GPU (``mimi_bpe_*``).  words: alphabet indices (0 .. n_base-1).  Returns
     (tokens beyond the alphabet as tuples of alphabet indices, merges as (left id, right id)) with ids counted
-    from the special tokens, as ``oracle/bpe_ref.train_bpe``."""
+    from the special tokens, as ``oracle/bpe_ref.train_bpe``.  min_table_slots / grid_blocks: the options of
+    ``mimi_bpe_create_opts`` (None: the defaults; a value it refuses raises ``ValueError`` before any device call);
+    with a dict in ``stats`` the table's final ``table_slots`` and ``growth_rehashes`` are recorded too."""
     import time
 
     from . import _lib
@@ -334,8 +337,17 @@ def train_words_gpu(words: Sequence[np.ndarray], counts: np.ndarray, n_base: int
         raise ValueError("vocab_size above 131071 is not supported by the GPU trainer")
     h = ctypes.c_void_p()
     t0 = time.perf_counter()
-    _lib.check(lib.mimi_bpe_create(device, sym.ctypes.data, sym.size, offs.ctypes.data, cnt.ctypes.data, len(words),
-                                   n_special + n_base, vocab_size, max_token_length or 0, ctypes.byref(h)))
+    opts = _lib.BpeOptionsC(int(min_table_slots or 0), int(grid_blocks or 0), 0)
+    if (min_table_slots is not None and min_table_slots < 1) or (grid_blocks is not None and grid_blocks < 1):
+        raise ValueError("min_table_slots and grid_blocks must be >= 1 (None: the default)")
+    try:
+        _lib.check(lib.mimi_bpe_create_opts(device, sym.ctypes.data, sym.size, offs.ctypes.data, cnt.ctypes.data,
+                                            len(words), n_special + n_base, vocab_size, max_token_length or 0,
+                                            ctypes.byref(opts), ctypes.byref(h)))
+    except _lib.MimiHipError as e:
+        if e.status == 1:
+            raise ValueError(str(e)) from None
+        raise
     tokens: List[Tuple[int, ...]] = []
     merges: List[Tuple[int, int]] = []
     spell: List[Tuple[int, ...]] = [()] * n_special + [(i,) for i in range(n_base)]
@@ -357,6 +369,11 @@ def train_words_gpu(words: Sequence[np.ndarray], counts: np.ndarray, n_base: int
             if stats is not None and "trace" in stats:
                 stats["trace"].append(c.value)
             _lib.check(lib.mimi_bpe_merge(h, a.value, b.value, nid, len(new)))
+        if stats is not None:
+            v = ctypes.c_int64()
+            for key in ("table_slots", "growth_rehashes"):
+                _lib.check(lib.mimi_bpe_info(h, _lib.BPE_TRAIN_INFO[key], ctypes.byref(v)))
+                stats[key] = v.value
     finally:
         lib.mimi_bpe_destroy(h)
     if stats is not None:
