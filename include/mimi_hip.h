@@ -323,7 +323,8 @@ int mimi_set_option(mimi_engine* e, const char* key, int64_t value);
 /* Encodes submitted to lane 0 / 1 so far (diagnostic; -1: no such lane).  Encodes that take no lane count in lane 0. */
 int64_t mimi_lane_encodes(const mimi_engine* e, int32_t lane);
 /* MIMI_PRECISION_F16X3 diagnostics: per plane tensor (64-char names), its fixed activation scale and the max|x|
- * of the last waited encode (-1: not produced by it); an overflow is max * scale >= 2^15. */
+ * of the last waited encode (-1: not produced by it, or a LayerNorm output whose range check the engine skips: its
+ * bound times its scale is below 2^14, so no maximum is recorded); an overflow is max * scale >= 2^15. */
 int mimi_act_scales(mimi_engine* e, int32_t max_n, char* names, float* scales, float* last_max, int32_t* n);
 
 /* Frames produced for `length` samples with the default config (reference float32 length math). */

@@ -3,7 +3,9 @@
 normalised value (x_c - mean) / sqrt(var + eps) never exceeds sqrt(D - 1) in magnitude (equality for a one-hot row,
 eps = 0).  Checked here in float32 with torch's layer_norm (the reference's op, TF/modeling_mimi.py:737-738) on the
 rows that come closest to the bound: one-hot rows of every scale, the same with a constant offset, rows with two
-outliers, and random rows -- the engine's 1.001 margin must cover the rounding."""
+outliers, and random rows.  torch is held here to sqrt(D - 1) x 1.001; the engine's own bound is the looser
+sqrt(D) (1 + 2^-10) (a rounded mean: engine.cpp DevXfmr::ln1_bound), inside the same window below, and the device
+kernels run the one-hot rows in tests/test_encode_adversarial.py (checkpoint ``onehot``)."""
 import numpy as np
 import torch
 
