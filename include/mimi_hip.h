@@ -490,6 +490,46 @@ int mimi_bpe_encode_codes(mimi_bpe_model* m, const int32_t* dev_codes, int32_t b
                           void* stream);
 
 /*
+ * Codec-BPE decoding of token ids that are already in device memory, the inverse of mimi_bpe_encode_codes: ids ->
+ * the code characters they spell -> the drop rules of the reference's pretraining-data/converter.py chars_to_codes
+ * (default flags) -> codes laid out as mimi_decode_ragged takes them; device memory in, device memory out
+ * (mimi_hip/bpe.py Encoder.decode_device drives it, Encoder.decode_ids is the host statement of the same rules).
+ *
+ * mimi_bpe_model_set_spellings: token id i spells the alphabet indices spell_index[spell_offsets[i] ..
+ * spell_offsets[i + 1]) (host arrays, n_tokens + 1 offsets starting at 0; an id that gives no character -- a special
+ * token -- has an empty spelling).  Requires mimi_bpe_model_set_alphabet (else MIMI_ERR_STATE; a later set_alphabet
+ * drops the spellings); an index outside [0, num_codebooks * codebook_size) or decreasing offsets return
+ * MIMI_ERR_INVALID_ARGUMENT.  Copied into device memory.
+ *
+ * mimi_bpe_decode_plan: sequence s is dev_ids[seq_offsets[s] .. seq_offsets[s + 1]) (dev_ids: device int32;
+ * seq_offsets: host, n_seq + 1 entries from 0, non-decreasing).  Per sequence the spellings are concatenated (character
+ * i has codebook cb_i = index_i / codebook_size), then with expected = cb_0 a character is kept iff cb_i == expected,
+ * a kept one advancing expected to (expected + 1) % num_codebooks; of the kept characters the first
+ * min((num_codebooks - cb_0) % num_codebooks, kept) and then the last remaining % num_codebooks are dropped; the rest
+ * are frame_lengths[s] = remaining / num_codebooks frames (host out, n_seq entries; 0 for a sequence that spells
+ * nothing).  The plan (every character's alphabet index, keep bit and kept rank, every sequence's first rank and frame
+ * count) stays in the model's buffers, 8 bytes per character and 4 per id.  Runs on `stream` and synchronises it
+ * twice: once to read back the character count that sizes those buffers (with the bad-id flag), once for the frame
+ * counts.  An id outside [0, n_tokens) returns MIMI_ERR_INVALID_ARGUMENT (checked on the device before any table
+ * load) and the model stays usable; num_codebooks > 16 (a filter state map is 16 nibbles) or 2^31 characters or more
+ * return MIMI_ERR_UNSUPPORTED (the caller may run the host rules instead); without spellings: MIMI_ERR_STATE.
+ *
+ * mimi_bpe_decode_write: writes the last plan's codes: frame t of codebook k of sequence s to dev_codes +
+ * s * item_stride + k * row_stride + t (device int32), t < frame_lengths[s]; nothing else is written (rows past a
+ * sequence's frames keep what they held; mimi_decode_ragged never reads them).  Without a plan -- none made, the last
+ * one failed, or any other call on the model since -- it returns MIMI_ERR_STATE; max_frames (the frames a row of
+ * dev_codes holds) below the plan's largest frame count returns MIMI_ERR_INVALID_ARGUMENT with nothing launched.  A
+ * plan may be written more than once.  Runs on `stream` and synchronises it.  Both calls are serialised with the
+ * encode calls by the model's mutex.
+ */
+#define MIMI_BPE_DECODE_SCAN_TILE 2048 /* ids / characters per workgroup of the decode scan kernels */
+int mimi_bpe_model_set_spellings(mimi_bpe_model* m, const int64_t* spell_offsets, const int32_t* spell_index);
+int mimi_bpe_decode_plan(mimi_bpe_model* m, const int32_t* dev_ids, const int64_t* seq_offsets, int64_t n_seq,
+                         int64_t* frame_lengths, void* stream);
+int mimi_bpe_decode_write(mimi_bpe_model* m, int32_t* dev_codes, int64_t item_stride, int64_t row_stride,
+                          int64_t max_frames, void* stream);
+
+/*
  * Diagnostic: the fp16 plane split the kernels use (two v_fma_mix per value: hi = fp16(v s), lo = fp16(v s - hi))
  * against the conversion form it replaces, on npairs value pairs of dev_in (device f32 [2 npairs], s a power of two):
  * dev_out (device u32 [npairs][4]) = the kernels' (hi, lo) words and the conversion form's (hi, lo) words.  Tests

@@ -242,6 +242,8 @@ extern "C" void mimi_bpe_model_destroy(mimi_bpe_model* m) {
     m->release_buffers();
     if (m->slots) (void)hipFree(m->slots);
     if (m->alphabet) (void)hipFree(m->alphabet);
+    if (m->spell_off) (void)hipFree(m->spell_off);
+    if (m->spell_idx) (void)hipFree(m->spell_idx);
     delete m;
 }
 
@@ -401,6 +403,7 @@ extern "C" int mimi_bpe_encode(mimi_bpe_model* m, const int32_t* symbols, const 
         return fail(MIMI_ERR_INVALID_ARGUMENT, "bad word arguments");
     if (n_words > 0x7ffffffell) return fail(MIMI_ERR_UNSUPPORTED, "more than 2^31 - 2 words");
     std::lock_guard<std::mutex> lock(m->mu);
+    m->plan_valid = false;
     m->last_words[0] = m->last_words[1] = m->last_words[2] = 0;
     if (n_words == 0) return MIMI_OK;
     hipStream_t s = (hipStream_t)stream;

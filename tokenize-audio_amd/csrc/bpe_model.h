@@ -1,5 +1,5 @@
-// The device BPE model shared by bpe_encode.hip (merge table, merge kernels, host-word entry) and bpe_words.hip
-// (device word model, device-to-device entry).
+// The device BPE model shared by bpe_encode.hip (merge table, merge kernels, host-word entry), bpe_words.hip
+// (device word model, device-to-device entry) and bpe_decode.hip (ids back to codes).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -68,9 +68,19 @@ struct mimi_bpe_model {
     unsigned short* alphabet = nullptr;
     int n_special = 0, num_codebooks = 0, codebook_size = 0;
     mimi::bpe::Buffer seqs, info, scan, partials, symword, word_first, seq_out;
+    // decoder (bpe_decode.hip): the spelling of every id (offsets [n_tokens + 1], alphabet indices), the buffers of
+    // the last mimi_bpe_decode_plan and what mimi_bpe_decode_write needs of it.  Any other call clears plan_valid
+    int* spell_off = nullptr;
+    int* spell_idx = nullptr;
+    mimi::bpe::Buffer dec_seq_ids, dec_id_start, dec_cpos, dec_info, dec_rank, dec_begin, dec_frames, dec_partials,
+        dec_ctl;
+    bool plan_valid = false;
+    int plan_chars = 0, plan_seqs = 0;
+    int64_t plan_max_frames = 0;
     void release_buffers() {
         for (mimi::bpe::Buffer* b : {&symbols, &offsets, &words, &out_ids, &out_lens, &bad, &ws, &seqs, &info, &scan,
-                                     &partials, &symword, &word_first, &seq_out})
+                                     &partials, &symword, &word_first, &seq_out, &dec_seq_ids, &dec_id_start, &dec_cpos,
+                                     &dec_info, &dec_rank, &dec_begin, &dec_frames, &dec_partials, &dec_ctl})
             b->release();
     }
 };

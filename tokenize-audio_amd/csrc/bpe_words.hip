@@ -417,6 +417,7 @@ extern "C" int mimi_bpe_model_set_alphabet(mimi_bpe_model* m, int32_t n_special,
         table[i] = (unsigned short)(cls[i] | (ccc[i] << 8));
     }
     std::lock_guard<std::mutex> lock(m->mu);
+    m->plan_valid = false;
     ENC_TRY(hipSetDevice(m->device));
     unsigned short* dev = nullptr;
     ENC_TRY(hipMalloc(&dev, (size_t)n_base * 2));
@@ -426,6 +427,10 @@ extern "C" int mimi_bpe_model_set_alphabet(mimi_bpe_model* m, int32_t n_special,
         ENC_TRY(e);
     }
     if (m->alphabet) (void)hipFree(m->alphabet);
+    // spellings were checked against the alphabet they were set under (bpe_decode.hip): a new one drops them
+    if (m->spell_off) (void)hipFree(m->spell_off);
+    if (m->spell_idx) (void)hipFree(m->spell_idx);
+    m->spell_off = m->spell_idx = nullptr;
     m->alphabet = dev;
     m->n_special = n_special;
     m->num_codebooks = num_codebooks;
@@ -443,6 +448,7 @@ extern "C" int mimi_bpe_encode_codes(mimi_bpe_model* m, const int32_t* dev_codes
         return fail(MIMI_ERR_INVALID_ARGUMENT, "bad batch arguments");
     if (n_seq > 0x3fffffffll) return fail(MIMI_ERR_UNSUPPORTED, "more than 2^30 sequences");
     std::lock_guard<std::mutex> lock(m->mu);
+    m->plan_valid = false;
     if (!m->alphabet) return fail(MIMI_ERR_STATE, "mimi_bpe_model_set_alphabet has not been called");
     const int K = m->num_codebooks;
     // the sequences: pos [n_seq + 1] | item [n_seq] | first frame [n_seq]

@@ -36,12 +36,14 @@ EXPORTED_SYMBOLS = (
     "mimi_bpe_model_create", "mimi_bpe_model_destroy", "mimi_bpe_encode", "mimi_bpe_model_info",
     "mimi_bpe_model_set_alphabet", "mimi_bpe_encode_codes",
     "mimi_bpe_create_opts", "mimi_bpe_info", "mimi_bpe_read_pairs", "mimi_bpe_read_words",
+    "mimi_bpe_model_set_spellings", "mimi_bpe_decode_plan", "mimi_bpe_decode_write",
 )
 CREATE_DECODE = 1  # MIMI_CREATE_DECODE
 RESAMPLE_MAX_TAPS = 65536  # MIMI_RESAMPLE_MAX_TAPS
 BPE_ENCODE_LDS_MAX_SYMBOLS = 8192  # MIMI_BPE_ENCODE_LDS_MAX_SYMBOLS
 BPE_WORDS_MAX_RUN = 64  # MIMI_BPE_WORDS_MAX_RUN
 BPE_WORDS_SCAN_TILE = 2048  # MIMI_BPE_WORDS_SCAN_TILE
+BPE_DECODE_SCAN_TILE = 2048  # MIMI_BPE_DECODE_SCAN_TILE
 # MIMI_BPE_INFO_*
 BPE_INFO = {"pairs": 0, "formed_pair_outranks": 1, "table_slots": 2, "last_words_lds_small": 3, "last_words_lds": 4,
             "last_words_global": 5}
@@ -152,6 +154,9 @@ def _declare(lib):
         "mimi_bpe_model_set_alphabet": (c.c_int, [vp, c.c_int32, c.c_int32, c.c_int32, vp, vp]),
         "mimi_bpe_encode_codes": (c.c_int, [vp, vp, c.c_int32, c.c_int64, c.c_int64, vp, c.c_int64, vp, c.c_int64, vp,
                                             c.c_int64, vp]),
+        "mimi_bpe_model_set_spellings": (c.c_int, [vp, vp, vp]),
+        "mimi_bpe_decode_plan": (c.c_int, [vp, vp, vp, c.c_int64, vp, vp]),
+        "mimi_bpe_decode_write": (c.c_int, [vp, vp, c.c_int64, c.c_int64, c.c_int64, vp]),
         "mimi_flac_info": (c.c_int, [vp, c.c_int64, c.POINTER(c.c_int32), c.POINTER(c.c_int32),
                                      c.POINTER(c.c_int32), c.POINTER(c.c_int64)]),
         "mimi_flac_decode": (c.c_int, [vp, c.c_int64, vp, c.c_int64, c.POINTER(c.c_int64)]),

@@ -382,6 +382,45 @@ def train_words_gpu(words: Sequence[np.ndarray], counts: np.ndarray, n_base: int
     return tokens, merges
 
 
+def spelling_table(spellings: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
+    """Per-id spellings (alphabet indices) -> (offsets int64 [n + 1], indices int32), the layout of
+    ``mimi_bpe_model_set_spellings``."""
+    lens = np.fromiter((len(t) for t in spellings), dtype=np.int64, count=len(spellings))
+    off = np.zeros(len(spellings) + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    idx = np.fromiter((i for t in spellings for i in t), dtype=np.int32, count=int(off[-1]))
+    return off, idx
+
+
+def filter_keep(cb: np.ndarray, num_codebooks: int, commuted: bool = False) -> np.ndarray:
+    """The keep mask of ``Encoder.decode_ids``' step 2 for the codebooks ``cb`` of one sequence's characters, as a
+    scan: character i is the map ``f_i(e) = (e + 1) % K if e == cb_i else e`` on ``[0, K)``, the first character the
+    constant map to ``(cb_0 + 1) % K`` (``expected`` starts as ``cb_0``, so it is kept), ``expected`` before
+    character i is ``(f_{i-1} o ... o f_0)`` of anything, and a character is kept iff it equals its codebook.  The
+    inclusive scan doubles its reach per pass (log2 n passes of one fancy-index each).  The operator does not
+    commute; ``commuted=True`` composes in the wrong order, which tests use to show that their streams tell the two
+    apart."""
+    K = int(num_codebooks)
+    cb = np.asarray(cb, dtype=np.int64)
+    n = cb.size
+    if n == 0:
+        return np.zeros(0, dtype=bool)
+    maps = np.tile(np.arange(K, dtype=np.int64), (n, 1))
+    maps[np.arange(n), cb] = (cb + 1) % K
+    maps[0, :] = (cb[0] + 1) % K
+    o = 1
+    while o < n:
+        earlier, later = maps[:-o], maps[o:]
+        if commuted:
+            earlier, later = later, earlier
+        maps[o:] = np.take_along_axis(later, earlier, axis=1)  # later(earlier(e))
+        o *= 2
+    expected = np.empty(n, dtype=np.int64)
+    expected[0] = cb[0]
+    expected[1:] = maps[:-1, 0]
+    return cb == expected
+
+
 class Encoder:
     """Apply a trained codec-BPE model on the GPU: codes (or ``codes_to_chars`` strings) -> token ids.
 
@@ -409,7 +448,8 @@ class Encoder:
     WORDS_MAX_RUN = 64  # _lib.BPE_WORDS_MAX_RUN: the longest run of marks the device word model orders
 
     def __init__(self, num_codebooks: int, codebook_size: int, merges, n_tokens: int, n_special: int,
-                 unicode_offset: int = UNICODE_OFFSET, device: Union[int, str] = 0, unk_token: Optional[str] = None):
+                 unicode_offset: int = UNICODE_OFFSET, device: Union[int, str] = 0, unk_token: Optional[str] = None,
+                 spellings: Optional[Sequence[Sequence[int]]] = None):
         from . import _lib
         if unk_token is not None:
             raise NotImplementedError("bpe.Encoder supports models without an unk_token only (the recipe's setting)")
@@ -429,6 +469,32 @@ class Encoder:
         self._lib = _lib.load()
         self._h = ctypes.c_void_p()  # the device model (merge table), made on first use
         self.last_stats: Dict[str, float] = {}
+        # the decoder's spelling table (decode_ids / decode_device): given (from_trainer, from_tokenizer), or built
+        # from the merges on first use
+        self._spell: Optional[Tuple[np.ndarray, np.ndarray]] = None
+        self._spell_on_device = False
+        if spellings is not None:
+            if len(spellings) != self.n_tokens:
+                raise ValueError(f"{len(spellings)} spellings for {self.n_tokens} tokens")
+            off, idx = spelling_table(spellings)
+            if idx.size and (idx.min() < 0 or idx.max() >= n_base):
+                raise ValueError("spelling indices outside the code alphabet")
+            self._spell = (off, idx)
+
+    def spellings(self) -> Tuple[np.ndarray, np.ndarray]:
+        """``(offsets int64 [n_tokens + 1], alphabet indices int32)``: id i spells ``indices[offsets[i]:offsets[i + 1]]``.
+        A special id spells nothing, an alphabet id itself; without spellings given at construction a learned id
+        spells ``spell[left] + spell[right]`` of its merge, taken in rank order (an id that no merge forms spells
+        nothing, as ``tokenizers`` decodes an id that its vocabulary lacks)."""
+        if self._spell is None:
+            n_base = self.num_codebooks * self.codebook_size
+            spell: List[Tuple[int, ...]] = [()] * self.n_special + [(i,) for i in range(n_base)]
+            spell += [()] * (self.n_tokens - len(spell))
+            for a, b, c in self.merges.tolist():
+                if c >= self.n_special + n_base:
+                    spell[c] = spell[a] + spell[b]
+            self._spell = spelling_table(spell)
+        return self._spell
 
     def _model(self):
         from . import _lib
@@ -441,10 +507,20 @@ class Encoder:
                                                              self.codebook_size, cls.ctypes.data, ccc.ctypes.data))
         return self._h
 
+    def _decode_model(self):
+        from . import _lib
+        h = self._model()
+        if not self._spell_on_device:
+            off, idx = self.spellings()
+            _lib.check(self._lib.mimi_bpe_model_set_spellings(h, off.ctypes.data, idx.ctypes.data))
+            self._spell_on_device = True
+        return h
+
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h:
             self._lib.mimi_bpe_model_destroy(self._h)
             self._h = ctypes.c_void_p()
+            self._spell_on_device = False
 
     def __del__(self):
         try:
@@ -463,7 +539,8 @@ class Encoder:
             tok_id.setdefault(spell[i], i)
         merges = [(a, b, tok_id[spell[a] + spell[b]]) for a, b in trainer.last_merges]
         return cls(trainer.num_codebooks, trainer.codebook_size, merges, len(spell), n_sp,
-                   unicode_offset=trainer.unicode_offset, device=trainer.device, unk_token=trainer.unk_token)
+                   unicode_offset=trainer.unicode_offset, device=trainer.device, unk_token=trainer.unk_token,
+                   spellings=spell)
 
     @classmethod
     def from_tokenizer(cls, tokenizer, num_codebooks: int, codebook_size: int,
@@ -498,8 +575,20 @@ class Encoder:
         for m in model["merges"]:
             a, b = m.split(" ") if isinstance(m, str) else m
             merges.append((vocab[a], vocab[b], vocab[a + b]))
+        # what each id decodes to: an id at or above n_special must be a string of code characters (an id that the
+        # vocabulary lacks decodes to nothing, in tokenizers too)
+        spell: List[Tuple[int, ...]] = [()] * n_tokens
+        entries = list(vocab.items()) + [(t["content"], t["id"]) for t in j.get("added_tokens", [])]
+        for text, i in entries:
+            if i < n_sp:
+                continue
+            t = tuple(ord(ch) - unicode_offset for ch in text)
+            if not t or min(t) < 0 or max(t) >= n_base:
+                raise NotImplementedError(f"token {i} ({text!r}) is not a string of code characters: decoding it to "
+                                          f"codes is not defined")
+            spell[i] = t
         return cls(num_codebooks, codebook_size, merges, n_tokens, n_sp, unicode_offset=unicode_offset,
-                   device=device)
+                   device=device, spellings=spell)
 
     # ---- model properties --------------------------------------------------------------------------
     def info(self, key: str) -> int:
@@ -695,3 +784,194 @@ class Encoder:
             flat = ids.cpu().numpy()
             return [flat[seq_offsets[i]:seq_offsets[i + 1]].copy() for i in range(n_seq)]
         return ids, seq_offsets, seq_item
+
+    # ---- decoding ----------------------------------------------------------------------------------
+    def _decode_one(self, ids: np.ndarray) -> np.ndarray:
+        K, cbs = self.num_codebooks, self.codebook_size
+        ids = np.asarray(ids).reshape(-1).astype(np.int64)
+        if ids.size and (ids.min() < 0 or ids.max() >= self.n_tokens):
+            raise ValueError(f"a token id is outside [0, {self.n_tokens})")
+        off, idx = self.spellings()
+        # 1. expand: the spellings, concatenated
+        first, lens = off[ids], off[ids + 1] - off[ids]
+        total = int(lens.sum())
+        if total == 0:
+            return np.zeros((K, 0), dtype=np.int64)
+        at = np.arange(total, dtype=np.int64) + np.repeat(first - (np.cumsum(lens) - lens), lens)
+        return self.indices_to_codes(idx[at])
+
+    def indices_to_codes(self, index: np.ndarray) -> np.ndarray:
+        """Steps 2-4 of ``decode_ids`` on one sequence's alphabet indices (code point - ``unicode_offset`` of each
+        character of a decoded string): the reference's drop rules, then the frames ``[num_codebooks, T]``."""
+        K, cbs = self.num_codebooks, self.codebook_size
+        index = np.asarray(index).reshape(-1).astype(np.int64)
+        total = index.size
+        if total == 0:
+            return np.zeros((K, 0), dtype=np.int64)
+        if index.min() < 0 or index.max() >= K * cbs:
+            raise ValueError("characters outside the code alphabet")
+        # 2. drop inconsistent (a stream that already cycles keeps everything)
+        cb = index // cbs
+        cb0 = int(cb[0])
+        if not np.array_equal(cb, (cb0 + np.arange(total)) % K):
+            index = index[filter_keep(cb, K)]
+        # 3. drop hanging: the kept characters cycle from cb_0
+        kept = index.size
+        begin = min((K - cb0) % K, kept)
+        T = (kept - begin) // K
+        # 4. frames
+        frames = index[begin:begin + K * T].reshape(T, K)
+        return np.ascontiguousarray((frames - np.arange(K, dtype=np.int64) * cbs).T)
+
+    def decode_ids(self, seqs: Iterable[np.ndarray]) -> List[np.ndarray]:
+        """Token ids -> codes on the host, one int64 ``[num_codebooks, T]`` array per id sequence: what
+        ``tokenizers``' ``decode(ids, skip_special_tokens=True)`` followed by the reference's
+        ``pretraining-data/converter.py`` ``chars_to_codes`` (default flags) gives, and the statement of what
+        ``decode_device`` computes.  Per sequence:
+
+        1. the ids' spellings (``spellings()``) are concatenated; special ids give nothing; an id outside
+           ``[0, n_tokens)`` is a ``ValueError``;
+        2. character i has codebook ``cb_i = index_i // codebook_size``; ``expected`` starts as ``cb_0``; a character
+           is kept iff ``cb_i == expected``; a kept one advances ``expected`` to ``(expected + 1) % K``
+           (``filter_keep``);
+        3. of the kept characters the first ``min((K - cb_0) % K, kept)`` are dropped, then the last
+           ``remaining % K``;
+        4. the ``T = remaining // K`` frames give ``codes[k][t] = index - k * codebook_size``.  A sequence that spells
+           nothing gives ``T = 0`` (the reference raises ``IndexError`` on an empty string)."""
+        return [self._decode_one(ids) for ids in seqs]
+
+    def decode_device(self, ids, seq_offsets=None, stream=None, to_host: bool = False, lengths=None, out=None):
+        """Token ids in device memory -> codes in device memory (``mimi_bpe_decode_plan`` / ``_write``): the rules of
+        ``decode_ids`` on the GPU, the codes laid out as ``MimiHipModel.decode_ragged`` takes them.
+
+        ids: a CUDA ``torch.Tensor``, int32 or int64 (int64 is narrowed by a torch op), either 1-D with
+        ``seq_offsets`` (host, ``n_seq + 1`` entries from 0: sequence s is ``ids[seq_offsets[s]:seq_offsets[s + 1]]``;
+        default: one sequence of all ids) -- what ``encode_device`` returns, as it stands -- or 2-D ``[B, L]`` with
+        ``lengths`` (ids of each row, default ``L``; ids past a row's length are never decoded, whatever they are).
+        stream: a ``torch.cuda.Stream`` or a raw ``hipStream_t`` value (default: the current stream of the ids'
+        device); the call synchronises it.  out: an int32 CUDA tensor ``[n_seq, K, >= Tmax]`` with unit stride along
+        frames to write into instead of a new one; only the frames of each sequence are written.
+
+        Returns ``(codes, frame_lengths)``: ``codes`` int32 ``[n_seq, K, Tmax]`` on the device (rows past a
+        sequence's frames are zero in a tensor made here), ``frame_lengths`` a host int64 array.  With
+        ``to_host=True``: a list of ``[K, T]`` int64 numpy arrays, equal to ``decode_ids``'.  ``last_stats["filter"]``
+        is ``"device"``, or ``"host"`` when the library answered ``MIMI_ERR_UNSUPPORTED`` (more than 16 codebooks, 2^31
+        characters) and the call went through ``decode_ids`` on ``.cpu()`` ids instead: same result.  An id outside
+        ``[0, n_tokens)`` inside a sequence is a ``ValueError`` (checked on the device before any table is read).
+        Argument errors raise ``ValueError`` before any device call."""
+        import torch
+
+        from . import _lib
+        K = self.num_codebooks
+        if not isinstance(ids, torch.Tensor):
+            raise ValueError("ids must be a CUDA torch.Tensor (host arrays: decode_ids)")
+        if ids.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"ids must be int32 or int64, not {ids.dtype}")
+        if ids.dim() == 1:
+            if lengths is not None:
+                raise ValueError("lengths go with 2-D ids; 1-D ids take seq_offsets")
+            if seq_offsets is None:
+                offs = np.array([0, ids.numel()], dtype=np.int64)
+            else:
+                if isinstance(seq_offsets, torch.Tensor):
+                    seq_offsets = seq_offsets.cpu().numpy()
+                offs = np.ascontiguousarray(np.asarray(seq_offsets, dtype=np.int64).reshape(-1))
+                if offs.size < 1 or offs[0] != 0 or (np.diff(offs) < 0).any() or offs[-1] > ids.numel():
+                    raise ValueError("seq_offsets must start at 0, not decrease and end inside ids")
+            row_lens = None
+        elif ids.dim() == 2:
+            if seq_offsets is not None:
+                raise ValueError("seq_offsets go with 1-D ids; 2-D ids take lengths")
+            B, L = ids.shape
+            if lengths is None:
+                row_lens = np.full(B, L, dtype=np.int64)
+            else:
+                if isinstance(lengths, torch.Tensor):
+                    lengths = lengths.cpu().numpy()
+                row_lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+                if row_lens.size != B:
+                    raise ValueError(f"{row_lens.size} lengths for {B} rows")
+                if B and (row_lens.min() < 0 or row_lens.max() > L):
+                    raise ValueError(f"lengths must be in [0, {L}]")
+            offs = np.zeros(B + 1, dtype=np.int64)
+            np.cumsum(row_lens, out=offs[1:])
+        else:
+            raise ValueError("ids must have shape [n] or [B, L]")
+        n_seq = int(offs.size - 1)
+        if not ids.is_cuda:
+            raise ValueError("ids must be a CUDA torch.Tensor (host arrays: decode_ids)")
+        if ids.device.index != self.device:
+            raise ValueError(f"ids are on {ids.device}, the encoder on device {self.device}")
+        if out is not None:
+            if (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.dim() != 3 or not out.is_cuda
+                    or out.device != ids.device or out.shape[0] < n_seq or out.shape[1] < K
+                    or (out.shape[2] > 1 and out.stride(2) != 1)):
+                raise ValueError(f"out must be an int32 CUDA tensor [>= {n_seq}, >= {K}, T] with unit frame stride")
+        frames = np.zeros(n_seq, dtype=np.int64)
+        t0 = time.perf_counter()
+        with torch.cuda.device(ids.device):
+            if row_lens is not None:  # the rows' ids end to end
+                if (row_lens == ids.shape[1]).all():
+                    ids = ids.reshape(-1)
+                else:
+                    keep = torch.arange(ids.shape[1], device=ids.device)[None, :] < \
+                        torch.from_numpy(row_lens).to(ids.device)[:, None]
+                    ids = ids[keep]
+            if ids.dtype != torch.int32:  # (an id beyond int32 stays outside [0, n_tokens))
+                ids = ids.clamp(-1, 0x7fffffff).to(torch.int32)
+            if not ids.is_contiguous():
+                ids = ids.contiguous()
+            if stream is None:
+                stream = torch.cuda.current_stream(ids.device)
+            s = getattr(stream, "cuda_stream", stream)
+            sp = ctypes.c_void_p(int(s)) if s else None
+            current = torch.cuda.current_stream(ids.device)
+            if int(s or 0) != current.cuda_stream:
+                current.synchronize()  # the narrowing / copy above ran there
+            mode = "device"
+            host: Optional[List[np.ndarray]] = None
+            if n_seq:
+                try:
+                    _lib.check(self._lib.mimi_bpe_decode_plan(self._decode_model(), ctypes.c_void_p(ids.data_ptr()),
+                                                              offs.ctypes.data, n_seq, frames.ctypes.data, sp))
+                except _lib.MimiHipError as e:
+                    if e.status == 1:
+                        raise ValueError(str(e)) from None
+                    if e.status != 5:
+                        raise
+                    mode = "host"
+                    flat = ids.cpu().numpy()
+                    host = self.decode_ids([flat[offs[i]:offs[i + 1]] for i in range(n_seq)])
+                    frames = np.array([c.shape[1] for c in host], dtype=np.int64)
+            t_max = int(frames.max()) if n_seq else 0
+            if out is None:
+                codes = torch.zeros((n_seq, K, t_max), dtype=torch.int32, device=ids.device)
+                if int(s or 0) != current.cuda_stream:
+                    current.synchronize()  # the fill ran there
+            else:
+                if out.shape[2] < t_max:
+                    raise ValueError(f"out holds {out.shape[2]} frames per row, the longest sequence has {t_max}")
+                codes = out
+            if n_seq and t_max:
+                if host is None:
+                    try:
+                        _lib.check(self._lib.mimi_bpe_decode_write(self._decode_model(),
+                                                                   ctypes.c_void_p(codes.data_ptr()), codes.stride(0),
+                                                                   codes.stride(1), codes.shape[2], sp))
+                    except _lib.MimiHipError as e:
+                        if e.status == 1:
+                            raise ValueError(str(e)) from None
+                        raise
+                else:
+                    for i, c in enumerate(host):
+                        codes[i, :K, :c.shape[1]].copy_(torch.from_numpy(c.astype(np.int32)))
+            if out is not None:
+                codes = out[:n_seq, :K, :t_max]
+        self.last_stats = {"filter": mode, "device_call_s": time.perf_counter() - t0, "sequences": n_seq,
+                           "ids": int(offs[-1]), "frames": int(frames.sum())}
+        if to_host:
+            if host is not None:
+                return host
+            h = codes.cpu().numpy().astype(np.int64)
+            return [np.ascontiguousarray(h[i, :, :int(frames[i])]) for i in range(n_seq)]
+        return codes, frames

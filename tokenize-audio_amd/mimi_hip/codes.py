@@ -132,3 +132,45 @@ def strs_to_audio(audio_strs: Sequence[str], mimi_model, device: str,
         frames += T
     flush()
     return out
+
+
+def ids_to_audio(ids, seq_offsets, encoder, mimi_model, max_batch_frames: int = MAX_BATCH_FRAMES) -> List[np.ndarray]:
+    """BPE token ids in device memory -> audio, without the ids or the codes leaving the device:
+    ``encoder.decode_device(ids, seq_offsets)`` (a ``bpe.Encoder`` of 8 codebooks; ``ids`` / ``seq_offsets`` as
+    ``encode_device`` returns them), then the sequences are cut, in order, into consecutive ragged batches exactly as
+    ``strs_to_audio`` cuts its strings, each batch one ``mimi_model.decode_ragged`` on a slice of the device codes.
+    Returns float32 arrays ``[1, 1920 T_i]`` in input order; a sequence of zero frames gives a ``(1, 0)`` array and is
+    not sent to the engine.  Bit for bit ``strs_to_audio`` of the strings of ``encoder.decode_ids``' codes."""
+    if max_batch_frames < 1:
+        raise ValueError("max_batch_frames must be at least 1")
+    if encoder.num_codebooks != NUM_CODEBOOKS or encoder.codebook_size != CODEBOOK_SIZE:
+        raise ValueError(f"the encoder must have {NUM_CODEBOOKS} codebooks of {CODEBOOK_SIZE} codes")
+    codes, lens = encoder.decode_device(ids, seq_offsets)
+    out: List[Optional[np.ndarray]] = [None] * len(lens)
+    batch: List[int] = []
+
+    def flush():
+        if not batch:
+            return
+        blens = [int(lens[i]) for i in batch]
+        # a batch is consecutive but for zero-frame sequences: a slice when it has none inside, else a gather
+        rows = codes[batch[0]:batch[-1] + 1] if batch[-1] - batch[0] + 1 == len(batch) else codes[batch]
+        with torch.no_grad():
+            audio = mimi_model.decode_ragged(rows[:, :, :max(blens)], blens)
+        for j, i in enumerate(batch):
+            out[i] = audio[j].cpu().numpy()
+        batch.clear()
+
+    frames = 0
+    for i, T in enumerate(lens):
+        T = int(T)
+        if T == 0:
+            out[i] = np.zeros((1, 0), dtype=np.float32)
+            continue
+        if batch and frames + T > max_batch_frames:
+            flush()
+            frames = 0
+        batch.append(i)
+        frames += T
+    flush()
+    return out
