@@ -195,8 +195,8 @@ int mimi_rvq_encode(mimi_engine* e, const float* dev_embedding, int64_t frames, 
  *
  * ARITHMETIC: decode always runs the fp32-MFMA form of the GEMMs (MIMI_PRECISION_F32) and the fp32 attention and
  * residual-block kernels, whatever mimi_set_precision says -- no activation scales, hence no calibration, overflow
- * read-back or fallback.  Mixed-length batches: mimi_decode_ragged.  Not provided: f16x3 decode, hipGraph replay of
- * decode, streaming (KV-cache / padding-cache) decode.
+ * read-back or fallback.  Mixed-length batches: mimi_decode_ragged.  Chunk by chunk on a KV cache:
+ * mimi_decode_stream_*.  Not provided: f16x3 decode, hipGraph replay of decode.
  */
 enum { MIMI_CREATE_DECODE = 1 };
 int mimi_enable_decode(mimi_engine* e);
@@ -253,6 +253,42 @@ int mimi_decode_ragged(mimi_engine* e, const int32_t* dev_codes, const int64_t* 
 /* Device bytes mimi_decode_ragged's workspace needs: mimi_decode_workspace_bytes(e, 1, sum of frame_lengths) plus the
  * int tables (under 4096 + 256 x batch bytes).  -1 on a NULL argument, batch <= 0 or a length < 1. */
 int64_t mimi_decode_ragged_workspace_bytes(const mimi_engine* e, const int64_t* frame_lengths, int32_t batch);
+
+/*
+ * Streaming decode: codes to audio chunk by chunk on a KV cache.  A decode stream holds the decoder's state for `batch`
+ * items advancing in lock-step: per item the few rows every causal stage reads from in front of a chunk (1 row of the
+ * embedding for the upsample, 6 of the transformer output for decoder.layers.0, 1 per up conv, 2 per residual block,
+ * 2 for the last conv) and, per transformer layer, a ring of the rotated key / value rows of the last
+ * sliding_window - 1 + 2 max_step_frames 25 Hz rows.  All of it is device memory owned by the stream
+ * (mimi_decode_stream_state_bytes: constant over the stream's life); a step's cost does not depend on the position.
+ *
+ * mimi_decode_stream_step: dev_codes device int32 [batch][num_quantizers][n], 1 <= n <= max_step_frames, the next n
+ * frames of every item; dev_audio device f32 [batch][mimi_decoded_length(n)].
+ * CONTRACT: the samples of frames [p, p + n) are bitwise the same under ANY split of the sequence into steps (one
+ * step of everything included), and an item's do not depend on its batch-mates or on other streams; against
+ * MimiModel.decode of the whole sequence they are within the project's activation tolerance (the per-row arithmetic
+ * is mimi_decode's; the attention reduces in another order).
+ * Errors: an engine without decode weights and num_quantizers as mimi_decode; n outside [1, max_step_frames]:
+ * MIMI_ERR_INVALID_ARGUMENT, state untouched; a code outside [0, codebook_size): MIMI_ERR_INVALID_ARGUMENT as
+ * mimi_decode (never used as an index), after which the stream returns MIMI_ERR_STATE until mimi_decode_stream_reset
+ * (the engine and other streams stay usable); a position whose 25 Hz row no longer fits a float32 exactly (2^24 rows,
+ * 7.8 days of audio): MIMI_ERR_UNSUPPORTED.  Synchronises `stream` once to read the bounds flag.  Serialised by the
+ * engine's mutex: steps of several streams may interleave with each other and with mimi_decode, mimi_decode_ragged and
+ * mimi_encode*; a step runs in mimi_decode's workspace and never grows the engine's shared RoPE tables (captured
+ * encode graphs survive).  Taps and profiling as mimi_decode, holding the step's rows; the history forms record as
+ * upsample_dw_hist_kernel, resblock_hist_kernel<...>, final_conv_hist_kernel and attention_stream_kernel.
+ * mimi_decode_stream_reset: back to position 0 with zero state (a fresh stream).  Destroy every stream before its
+ * engine.  Not provided: per-item positions (a ragged stream), hipGraph capture of a step, f16x3 arithmetic.
+ */
+typedef struct mimi_decode_stream mimi_decode_stream;
+int mimi_decode_stream_create(mimi_engine* e, int32_t batch, int32_t num_quantizers, int32_t max_step_frames,
+                              mimi_decode_stream** out);
+int mimi_decode_stream_step(mimi_decode_stream* st, const int32_t* dev_codes /* [batch][num_quantizers][n] */, int32_t n,
+                            float* dev_audio /* [batch][1920 n] */, void* stream);
+int mimi_decode_stream_reset(mimi_decode_stream* st);
+int64_t mimi_decode_stream_position(const mimi_decode_stream* st);    /* frames decoded so far */
+int64_t mimi_decode_stream_state_bytes(const mimi_decode_stream* st); /* constant over the stream's life */
+void mimi_decode_stream_destroy(mimi_decode_stream* st);
 
 /*
  * Host-only: the weight re-layout that turns a causal MimiConvTranspose1d (kernel 2 ratio, stride ratio, weight

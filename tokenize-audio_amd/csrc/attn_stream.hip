@@ -1,0 +1,171 @@
+// Streamed decode (mimi_decode_stream_*, engine.cpp "decode stream"): the attention of one step against a ring of the
+// past rows' rotated keys and values, and the strided copies that move the stages' carries.
+//
+//   attention_stream_kernel         a step's R = 2n query rows per (item, head) at absolute rows pos0 .. pos0 + R - 1
+//   attention_stream_append_kernel  the step's k / v rows into their ring slots (row r in slot r % cap)
+//   stream_carry_kernel             n strided copies in one launch, from a by-value table
+//
+// CHUNKING DOES NOT MOVE A BIT.  Query row a (absolute) attends keys jlo = max(0, a - W + 1) .. a.  One WAVE owns the
+// row.  Key jlo + t belongs to lane t % 64; a lane's score is one fmaf chain over d = 0 .. 63; the maximum is exact
+// whatever its order; lane l sums its exp(s - m) for t = l, l + 64, ... in that order and the 64 partial sums go
+// through one xor butterfly; P.V is, per output dim d = lane, one fmaf chain over t = 0 .. a - jlo, oldest key first.
+// Every one of these orders is a function of a alone: not of pos0 (where the chunk starts), not of R (how long it
+// is), not of the ring slot a key sits in, nor of whether a key is read from the ring or from the step's own rows
+// (the ring holds copies of the very words the q/k/v GEMM stored).  So a row's output is the same bits under any
+// split of the sequence into steps.
+//
+// Scores live in the wave's own slice of LDS (W floats): written and read by the same wave, LDS order, no barrier;
+// waves without a row exit before any load.
+#include "kernels.h"
+
+namespace mimi {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(256) void attention_stream_kernel(const float* __restrict__ qkv,
+                                                               const float* __restrict__ kring,
+                                                               const float* __restrict__ vring,
+                                                               float* __restrict__ out, int R, int H, int window,
+                                                               int cap, long long pos0, float scale) {
+    constexpr int D = 64;
+    extern __shared__ __attribute__((aligned(16))) float sc_all[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int i = blockIdx.x * 4 + wave;  // the query's row in the step
+    if (i >= R) return;
+    const int h = blockIdx.y, b = blockIdx.z;
+    float* sc = sc_all + wave * window;
+    const long long ld = 3LL * H * D;
+    const float* step = qkv + (long long)b * R * ld;               // the item's rows of this step
+    const long long ring = ((long long)b * H + h) * cap * D;      // the (item, head)'s ring
+    const long long a = pos0 + i;
+    const long long jlo = a - window + 1 > 0 ? a - window + 1 : 0;
+    const int cnt = (int)(a - jlo) + 1;  // 1 .. window keys, oldest first
+    // row j's key / value: the step's own rows from pos0 on, the ring before
+    auto krow = [&](long long j) {
+        return j >= pos0 ? step + (j - pos0) * ld + (long long)H * D + h * D : kring + ring + (j % cap) * D;
+    };
+    auto vrow = [&](long long j) {
+        return j >= pos0 ? step + (j - pos0) * ld + 2LL * H * D + h * D : vring + ring + (j % cap) * D;
+    };
+
+    f32x4 q[D / 4];
+    {
+        const float* qr = step + (long long)i * ld + h * D;
+#pragma unroll
+        for (int c = 0; c < D / 4; ++c) q[c] = *reinterpret_cast<const f32x4*>(qr + 4 * c) * scale;
+    }
+    float m = -INFINITY;
+    for (int t = lane; t < cnt; t += 64) {
+        const float* kr = krow(jlo + t);
+        f32x4 kv[D / 4];
+#pragma unroll
+        for (int c = 0; c < D / 4; ++c) kv[c] = *reinterpret_cast<const f32x4*>(kr + 4 * c);
+        float s = 0.0f;
+#pragma unroll
+        for (int c = 0; c < D / 4; ++c)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s = __builtin_fmaf(q[c][e], kv[c][e], s);
+        sc[t] = s;
+        m = fmaxf(m, s);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));  // (lane 0 always has key jlo: m is finite)
+    float l = 0.0f;
+    for (int t = lane; t < cnt; t += 64) {
+        const float p = __expf(sc[t] - m);
+        sc[t] = p;
+        l += p;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) l += __shfl_xor(l, o);
+    // P.V: lane = output dim; a wave reads one 256-B value row per key, four rows in flight
+    float acc = 0.0f;
+    int t = 0;
+    for (; t + 4 <= cnt; t += 4) {
+        const float v0 = vrow(jlo + t)[lane], v1 = vrow(jlo + t + 1)[lane];
+        const float v2 = vrow(jlo + t + 2)[lane], v3 = vrow(jlo + t + 3)[lane];
+        acc = __builtin_fmaf(sc[t], v0, acc);
+        acc = __builtin_fmaf(sc[t + 1], v1, acc);
+        acc = __builtin_fmaf(sc[t + 2], v2, acc);
+        acc = __builtin_fmaf(sc[t + 3], v3, acc);
+    }
+    for (; t < cnt; ++t) acc = __builtin_fmaf(sc[t], vrow(jlo + t)[lane], acc);
+    out[((long long)b * R + i) * (H * D) + h * D + lane] = acc * (1.0f / l);
+}
+
+hipError_t launch_attention_stream(const float* qkv, const float* kring, const float* vring, float* out, int batch,
+                                   int R, int H, int D, int window, int cap, long long pos0, float scale,
+                                   hipStream_t s) {
+    if (D != 64 || batch <= 0 || batch > 65535 || R <= 0 || H <= 0 || H > 65535 || window < 1 || cap < window - 1 ||
+        cap < 1 || pos0 < 0 || !qkv || !kring || !vring || !out)
+        return hipErrorInvalidValue;
+    const size_t lds = (size_t)4 * window * sizeof(float);
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attention_stream_kernel, dim3((unsigned)((R + 3) / 4), (unsigned)H, (unsigned)batch), dim3(256),
+                       lds, s, qkv, kring, vring, out, R, H, window, cap, pos0, scale);
+    return hipGetLastError();
+}
+
+// one thread per 16 B of the step's k and v rows: [b][row][k | v][head][16 float4]
+__global__ __launch_bounds__(256) void attention_stream_append_kernel(const float* __restrict__ qkv,
+                                                                      float* __restrict__ kring,
+                                                                      float* __restrict__ vring, int batch, int R, int H,
+                                                                      int cap, long long pos0) {
+    constexpr int D = 64;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long total = (long long)batch * R * 2 * H * (D / 4);
+    if (idx >= total) return;
+    const int c4 = (int)(idx % (D / 4));
+    long long r = idx / (D / 4);
+    const int h = (int)(r % H);
+    r /= H;
+    const int kv = (int)(r % 2);
+    r /= 2;
+    const int i = (int)(r % R);
+    const int b = (int)(r / R);
+    const float* src = qkv + ((long long)b * R + i) * (3LL * H * D) + (long long)(1 + kv) * H * D + h * D + 4 * c4;
+    float* dst = (kv ? vring : kring) + (((long long)b * H + h) * cap + (pos0 + i) % cap) * D + 4 * c4;
+    *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(src);
+}
+
+hipError_t launch_attention_stream_append(const float* qkv, float* kring, float* vring, int batch, int R, int H, int D,
+                                          int cap, long long pos0, hipStream_t s) {
+    // R <= cap: no two rows of the step share a slot
+    if (D != 64 || batch <= 0 || R <= 0 || R > cap || H <= 0 || pos0 < 0 || !qkv || !kring || !vring)
+        return hipErrorInvalidValue;
+    const long long total = (long long)batch * R * 2 * H * (D / 4);
+    const long long blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attention_stream_append_kernel, dim3((unsigned)blocks), dim3(256), 0, s, qkv, kring, vring, batch,
+                       R, H, cap, pos0);
+    return hipGetLastError();
+}
+
+// copy blockIdx.z of the table, item blockIdx.y; 16 B per thread, grid-stride along x
+__global__ __launch_bounds__(256) void stream_carry_kernel(CarryTable t) {
+    const CarryCopy& c = t.c[blockIdx.z];
+    const float* __restrict__ src = c.src + (long long)blockIdx.y * c.src_bstride;
+    float* __restrict__ dst = c.dst + (long long)blockIdx.y * c.dst_bstride;
+    const int n4 = c.count / 4;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256)
+        *reinterpret_cast<f32x4*>(dst + 4LL * i) = *reinterpret_cast<const f32x4*>(src + 4LL * i);
+}
+
+hipError_t launch_stream_carry(const CarryTable& t, int batch, hipStream_t s) {
+    if (t.n < 1 || t.n > CARRY_MAX || batch <= 0 || batch > 65535) return hipErrorInvalidValue;
+    int most = 0;
+    for (int d = 0; d < t.n; ++d) {
+        const CarryCopy& c = t.c[d];
+        if (!c.src || !c.dst || c.count <= 0 || c.count % 4 || c.src_bstride % 4 || c.dst_bstride % 4 ||
+            (reinterpret_cast<uintptr_t>(c.src) | reinterpret_cast<uintptr_t>(c.dst)) % 16)
+            return hipErrorInvalidValue;
+        most = c.count > most ? c.count : most;
+    }
+    const int blocks = (most / 4 + 255) / 256;
+    hipLaunchKernelGGL(stream_carry_kernel, dim3((unsigned)(blocks < 64 ? blocks : 64), (unsigned)batch, (unsigned)t.n),
+                       dim3(256), 0, s, t);
+    return hipGetLastError();
+}
+
+}  // namespace mimi

@@ -110,11 +110,14 @@ hipError_t launch_rvq_decode(const int32_t* codes, long long frames, int T, int 
 // One thread per (b, t, 4 channels): two 16-B loads of x, four of w (w[c][0..3] is one float4), two 16-B stores.
 // RG: x [sum tlen][C] -> y [2 sum tlen][C]; x[t - 1] = 0 at each item's first frame (t is the position in the item);
 // rows and T unused.
+// HS (a step of a decode stream): item b's T rows start at x + b * xbs and x[-1] is the row in front of them, the
+// stream's carry (zeros on a fresh stream): always read, never replaced by zero.  y as the uniform form.
 // ------------------------------------------------------------------------------------------------
-template <bool RG>
+template <bool RG, bool HS = false>
 __device__ __forceinline__ void upsample_dw_body(const float* __restrict__ x, const float* __restrict__ w,
                                                  float* __restrict__ y, long long rows, int T, int C4,
-                                                 const int* __restrict__ tlen, const int* __restrict__ toff) {
+                                                 const int* __restrict__ tlen, const int* __restrict__ toff,
+                                                 long long xbs = 0) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     long long row;
     int c4, t;
@@ -131,9 +134,11 @@ __device__ __forceinline__ void upsample_dw_body(const float* __restrict__ x, co
         t = (int)(row % T);
     }
     const int C = C4 * 4;
-    const f32x4 x1 = *reinterpret_cast<const f32x4*>(x + row * C + 4 * c4);
+    const float* xr = x + row * C + 4 * c4;
+    if constexpr (HS) xr = x + (row / T) * xbs + (long long)t * C + 4 * c4;
+    const f32x4 x1 = *reinterpret_cast<const f32x4*>(xr);
     f32x4 x0 = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (t > 0) x0 = *reinterpret_cast<const f32x4*>(x + (row - 1) * C + 4 * c4);
+    if (HS || t > 0) x0 = *reinterpret_cast<const f32x4*>(xr - C);
     f32x4 o0, o1;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -156,6 +161,24 @@ __global__ __launch_bounds__(256) void upsample_dw_ragged_kernel(const float* __
                                                                  const int* __restrict__ tlen,
                                                                  const int* __restrict__ toff) {
     upsample_dw_body<true>(x, w, y, 0, 0, C4, tlen, toff);
+}
+
+__global__ __launch_bounds__(256) void upsample_dw_hist_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                               float* __restrict__ y, long long rows, int T, int C4,
+                                                               long long xbs) {
+    upsample_dw_body<false, true>(x, w, y, rows, T, C4, nullptr, nullptr, xbs);
+}
+
+hipError_t launch_upsample_dw_hist(const float* x, const float* w, float* y, int batch, long long T, int C,
+                                   long long x_bstride, hipStream_t s) {
+    if (batch <= 0 || T <= 0 || T > 0x7fffffffLL || C <= 0 || C % 4 || !x || !w || !y || x_bstride < (T + 1) * C ||
+        x_bstride % 4)
+        return hipErrorInvalidValue;
+    const long long blocks = ((long long)batch * T * (C / 4) + 255) / 256;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(upsample_dw_hist_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, w, y, (long long)batch * T,
+                       (int)T, C / 4, x_bstride);
+    return hipGetLastError();
 }
 
 hipError_t launch_upsample_dw(const float* x, const float* w, float* y, int batch, long long T, int C, hipStream_t s,
@@ -186,10 +209,13 @@ hipError_t launch_upsample_dw(const float* x, const float* w, float* y, int batc
 // ------------------------------------------------------------------------------------------------
 constexpr int FC_TILE = 128, FC_C = 64, FC_LD = 68;
 
-template <bool RG>
+// HS (a step of a decode stream): item b's L rows start at x + b * xbs and rows -2, -1 in front of them are the
+// stream's carry: read instead of zeros.  y as the uniform form.
+template <bool RG, bool HS = false>
 __device__ __forceinline__ void final_conv_body(const float* __restrict__ x, const float* __restrict__ w,
                                                 const float* __restrict__ bias, float* __restrict__ y, long long Ls,
-                                                const int* __restrict__ llen, const int* __restrict__ loff) {
+                                                const int* __restrict__ llen, const int* __restrict__ loff,
+                                                long long xbs = 0) {
     __shared__ __attribute__((aligned(16))) float xs[(FC_TILE + 2) * FC_LD];
     __shared__ __attribute__((aligned(16))) float ws[3 * FC_C];
     const int tid = threadIdx.x;
@@ -202,14 +228,14 @@ __device__ __forceinline__ void final_conv_body(const float* __restrict__ x, con
         xb = x + (long long)loff[blockIdx.y] * FC_C;
     } else {
         L = Ls;  // every item fills its row
-        xb = x + (long long)blockIdx.y * L * FC_C;
+        xb = x + (long long)blockIdx.y * (HS ? xbs : L * FC_C);
     }
     for (int i = tid; i < 3 * FC_C; i += FC_TILE) ws[i] = w[i];
     for (int idx = tid; idx < (FC_TILE + 2) * (FC_C / 4); idx += FC_TILE) {
         const int r = idx >> 4, c4 = idx & 15;
         const long long g = l0 - 2 + r;
         f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (g >= 0 && g < L) v = *reinterpret_cast<const f32x4*>(xb + g * FC_C + 4 * c4);
+        if (g >= (HS ? -2 : 0) && g < L) v = *reinterpret_cast<const f32x4*>(xb + g * FC_C + 4 * c4);
         *reinterpret_cast<f32x4*>(xs + r * FC_LD + 4 * c4) = v;
     }
     __syncthreads();
@@ -239,6 +265,24 @@ __global__ __launch_bounds__(FC_TILE) void final_conv_ragged_kernel(const float*
                                                                     long long Ls, const int* __restrict__ llen,
                                                                     const int* __restrict__ loff) {
     final_conv_body<true>(x, w, bias, y, Ls, llen, loff);
+}
+
+__global__ __launch_bounds__(FC_TILE) void final_conv_hist_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                  const float* __restrict__ bias, float* __restrict__ y,
+                                                                  long long L, long long xbs) {
+    final_conv_body<false, true>(x, w, bias, y, L, nullptr, nullptr, xbs);
+}
+
+hipError_t launch_final_conv_hist(const float* x, const float* w, const float* bias, float* y, int batch, long long L,
+                                  int C, int ksize, long long x_bstride, hipStream_t s) {
+    if (C != FC_C || ksize != 3 || batch <= 0 || batch > 65535 || L <= 0 || !x || !w || !bias || !y ||
+        x_bstride < (L + 2) * FC_C || x_bstride % 4)
+        return hipErrorInvalidValue;
+    const long long tiles = (L + FC_TILE - 1) / FC_TILE;
+    if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(final_conv_hist_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(FC_TILE), 0, s, x, w, bias, y,
+                       L, x_bstride);
+    return hipGetLastError();
 }
 
 hipError_t launch_final_conv(const float* x, const float* w, const float* bias, float* y, int batch, long long L, int C,

@@ -2721,7 +2721,9 @@ extern "C" int mimi_rvq_encode(mimi_engine* e, const float* emb, int64_t frames,
 // ARITHMETIC: decode always runs the fp32-MFMA GEMMs and the fp32 attention / residual-block kernels (PREC_F32),
 // whatever mimi_set_precision says: no activation scales, so no calibration, no overflow read-back, no fallback.
 // A mixed-length batch (mimi_decode_ragged) runs the same pass (decode_pass) over packed rows: DecLayout below.
-// Not built here: f16x3 decode, hipGraph capture of decode, KV-cache / streaming decode.
+// Chunk by chunk on a KV cache: "decode stream" below (mimi_decode_stream_*).
+// Not built here: f16x3 decode, hipGraph capture of decode or of a stream's step, per-item stream positions,
+// streaming encode.
 
 static int64_t decode_upsampling(const mimi_config& c) {
     int64_t f = 2;  // upsample: 12.5 -> 25 Hz
@@ -3363,6 +3365,429 @@ extern "C" int mimi_decode_ragged(mimi_engine* e, const int32_t* dev_codes, cons
     // the tables' pinned host image and the workspace are reused by the next call: nothing of this one stays in flight
     if (rc) (void)hipStreamSynchronize(s);
     return rc;
+}
+
+// ================================================================================================
+// decode stream (mimi_decode_stream_*): the decode pass n frames at a time on a KV cache.  DESIGN.md 3.7.1.
+//
+// Every stage of the decoder is causal, so the samples of frames [p, p + n) of a sequence depend on its past only
+// through (per item) the rows each stage reads from in front of the chunk:
+//   upsample              1 row  [hidden]   of the output_proj embedding
+//   attention, per layer  the rotated k and v rows (P - W, P): a ring of cap = W - 1 + 2 max_step_frames rows
+//   decoder.layers.0      k - 1 = 6 rows [hidden] of the transformer output
+//   up conv s             1 row  [C_s]      of the ELU'd tensor it reads
+//   residual block s      2 rows [C_s / 2]  of the up conv's raw output
+//   last conv             k - 1 = 2 rows [filters] of the last block's ELU'd output
+// The stream owns these (`carry`, `kring`, `vring`: zero on a fresh or reset stream -- causal padding is zero and
+// ELU(0) = 0, so the first step is no special case) and the RoPE rows of the step.  A step runs in the engine's decode
+// workspace, which it only uses between taking and leaving the engine mutex: every stage's tensor there is, per item,
+// [H carry rows | the chunk's rows], so the GEMM convs read the carry where a one-shot pass reads padding (conv_args
+// with a_off moved by H rows) and the per-item kernels run their history forms.  One stream_carry_kernel launch in
+// front copies the carries in, one at the end copies the last H rows of every [carry | chunk] out (the two never
+// overlap, whatever n), one in the middle moves the transformer's flat rows behind decoder.layers.0's carry.
+// Per row every kernel computes what it computes in mimi_decode and attention_stream_kernel reduces in an order
+// that is a function of the row's absolute position alone (attn_stream.hip): the samples are the same bits under any
+// split of the sequence into steps.
+// ================================================================================================
+struct mimi_decode_stream {
+    mimi_engine* e = nullptr;
+    int B = 0, K = 0, max_n = 0, cap = 0;
+    int64_t pos = 0;      // frames decoded so far
+    bool failed = false;  // a step failed after it had touched the state: refuse until reset
+    float* state = nullptr;  // one allocation: carries | k rings | v rings | RoPE cos | RoPE sin
+    size_t state_bytes = 0, zero_bytes = 0;  // zero_bytes: the carries and rings, what reset clears
+    std::vector<size_t> carry_off;           // floats: per carry, in the order of the table above
+    std::vector<int> carry_h, carry_c;       // rows and channels of each
+    float *kring = nullptr, *vring = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
+    size_t ring_layer = 0;       // floats of one layer's ring
+    float* rope_host = nullptr;  // pinned: [cos | sin] of the step's rows
+};
+
+// the carries in stage order: upsample, decoder.layers.0, then per ratio (up conv, residual block), the last conv
+static void stream_carry_plan(const mimi_config& c, std::vector<int>* h, std::vector<int>* ch) {
+    h->assign(1, 1);
+    ch->assign(1, c.hidden_size);
+    h->push_back(c.kernel_size - 1);
+    ch->push_back(c.hidden_size);
+    int C = c.num_filters << c.num_ratios;
+    for (int s = 0; s < c.num_ratios; ++s) {
+        h->push_back(1);
+        ch->push_back(C);
+        C /= 2;
+        h->push_back(2);
+        ch->push_back(C);
+    }
+    h->push_back(c.last_kernel_size - 1);
+    ch->push_back(C);
+}
+
+// a step's workspace: flat-row buffers of the dequantizer and the transformer, then per stage its [B][H + rows][C]
+struct StreamWs {
+    float *sums, *emb, *t0, *t1, *qkv, *att, *ff, *xin, *tap;
+    std::vector<float*> xe, raw;  // xe[s]: ELU'd input of up conv s (xe[num_ratios]: of the last conv); raw[s]: its output
+    size_t bytes;
+};
+static StreamWs stream_ws_layout(const mimi_engine* e, int B, int n, bool taps) {
+    const mimi_config& c = e->cfg;
+    const size_t h = c.hidden_size, Bn = (size_t)B * n, R = 2 * (size_t)n;
+    StreamWs w{};
+    char* base = reinterpret_cast<char*>(e->dws);
+    size_t off = 0;
+    auto take = [&](size_t floats) {
+        float* p = reinterpret_cast<float*>(base + off);
+        off += pad256(floats * sizeof(float));
+        return p;
+    };
+    w.sums = take(Bn * 2 * c.vq_hidden_dim);
+    w.emb = take((size_t)B * (1 + n) * h);
+    w.t0 = take(B * R * h);
+    w.t1 = take(B * R * h);
+    w.qkv = take(B * R * 3 * c.num_attention_heads * c.head_dim);
+    w.att = take(B * R * h);
+    w.ff = take(B * R * c.intermediate_size);
+    w.xin = take((size_t)B * (c.kernel_size - 1 + R) * h);
+    size_t C = (size_t)c.num_filters << c.num_ratios, len = R;
+    w.tap = take(taps ? B * R * C : 0);
+    for (int s = 0; s < c.num_ratios; ++s) {
+        w.xe.push_back(take((size_t)B * (1 + len) * C));
+        len *= c.upsampling_ratios[s];
+        C /= 2;
+        w.raw.push_back(take((size_t)B * (2 + len) * C));
+    }
+    w.xe.push_back(take((size_t)B * (c.last_kernel_size - 1 + len) * C));
+    w.bytes = off;
+    return w;
+}
+
+extern "C" int mimi_decode_stream_create(mimi_engine* e, int32_t batch, int32_t K, int32_t max_step_frames,
+                                         mimi_decode_stream** out) {
+    if (!e || !out) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null engine / out");
+    *out = nullptr;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int rc = check_decode_state(e, K);
+    if (rc) return rc;
+    const mimi_config& c = e->cfg;
+    if (batch <= 0 || batch > 65535 || max_step_frames < 1 || max_step_frames > (1 << 20))
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "batch=%d max_step_frames=%d", batch, max_step_frames);
+    if (c.sliding_window < 1 || (size_t)4 * c.sliding_window * sizeof(float) > 64 * 1024)
+        return set_err(MIMI_ERR_UNSUPPORTED, "decode stream: sliding_window %d", c.sliding_window);
+    HIP_TRY(hipSetDevice(e->device));
+    std::unique_ptr<mimi_decode_stream> st(new mimi_decode_stream);
+    st->e = e;
+    st->B = batch;
+    st->K = K;
+    st->max_n = max_step_frames;
+    st->cap = c.sliding_window - 1 + 2 * max_step_frames;
+    stream_carry_plan(c, &st->carry_h, &st->carry_c);
+    size_t off = 0;  // floats; every section a multiple of 64 floats
+    auto take = [&](size_t floats) {
+        const size_t at = off;
+        off += (floats + 63) / 64 * 64;
+        return at;
+    };
+    for (size_t i = 0; i < st->carry_h.size(); ++i)
+        st->carry_off.push_back(take((size_t)batch * st->carry_h[i] * st->carry_c[i]));
+    st->ring_layer = (size_t)batch * c.num_attention_heads * st->cap * c.head_dim;
+    const size_t kr = take(st->ring_layer * c.num_hidden_layers), vr = take(st->ring_layer * c.num_hidden_layers);
+    st->zero_bytes = off * sizeof(float);
+    const size_t rope_floats = (size_t)2 * max_step_frames * (c.head_dim / 2);
+    const size_t rc_ = take(rope_floats), rs_ = take(rope_floats);
+    st->state_bytes = off * sizeof(float);
+    hipError_t err = hipMalloc(reinterpret_cast<void**>(&st->state), st->state_bytes);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(err == hipErrorOutOfMemory ? MIMI_ERR_OUT_OF_MEMORY : MIMI_ERR_HIP,
+                       "decode stream state hipMalloc(%zu bytes): %s", st->state_bytes, hipGetErrorString(err));
+    }
+    st->kring = st->state + kr;
+    st->vring = st->state + vr;
+    st->rope_cos = st->state + rc_;
+    st->rope_sin = st->state + rs_;
+    if ((err = hipMemset(st->state, 0, st->state_bytes)) != hipSuccess ||
+        (err = hipHostMalloc(reinterpret_cast<void**>(&st->rope_host), 2 * rope_floats * sizeof(float),
+                             hipHostMallocDefault)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(st->state);
+        return set_err(MIMI_ERR_HIP, "decode stream state: %s", hipGetErrorString(err));
+    }
+    *out = st.release();
+    return MIMI_OK;
+}
+
+extern "C" void mimi_decode_stream_destroy(mimi_decode_stream* st) {
+    if (!st) return;
+    {
+        std::lock_guard<std::mutex> lk(st->e->mu);  // (every step has synchronised its stream before it returned)
+        (void)hipSetDevice(st->e->device);
+        if (st->state) (void)hipFree(st->state);
+        if (st->rope_host) (void)hipHostFree(st->rope_host);
+    }
+    delete st;
+}
+
+extern "C" int mimi_decode_stream_reset(mimi_decode_stream* st) {
+    if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
+    std::lock_guard<std::mutex> lk(st->e->mu);
+    HIP_TRY(hipSetDevice(st->e->device));
+    HIP_TRY(hipMemset(st->state, 0, st->zero_bytes));
+    st->pos = 0;
+    st->failed = false;
+    return MIMI_OK;
+}
+
+extern "C" int64_t mimi_decode_stream_position(const mimi_decode_stream* st) { return st ? st->pos : -1; }
+
+extern "C" int64_t mimi_decode_stream_state_bytes(const mimi_decode_stream* st) {
+    return st ? (int64_t)st->state_bytes : -1;
+}
+
+// a tap of a step: item b's `rows` rows of C floats start at src + b * bstride
+static int save_tap_strided(mimi_engine* e, const char* name, const float* src, int64_t b, int64_t rows, int64_t ch,
+                            int64_t bstride, hipStream_t s) {
+    if (!e->taps) return MIMI_OK;
+    if (bstride == rows * ch) return save_tap(e, name, src, b, rows, ch, s);
+    auto& tp = e->tapmap[name];
+    const size_t n = (size_t)(b * rows * ch);
+    if (tp.cap < n) {
+        if (tp.d) HIP_TRY(hipFree(tp.d));
+        HIP_TRY(hipMalloc(&tp.d, n * 4));
+        tp.cap = n;
+    }
+    HIP_TRY(hipMemcpy2DAsync(tp.d, (size_t)(rows * ch) * 4, src, (size_t)bstride * 4, (size_t)(rows * ch) * 4, (size_t)b,
+                             hipMemcpyDeviceToDevice, s));
+    tp.dims[0] = b;
+    tp.dims[1] = rows;
+    tp.dims[2] = ch;
+    return MIMI_OK;
+}
+
+// the launches of one step (the workspace w sized for it, the step's RoPE rows already enqueued)
+static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int n, const StreamWs& w, float* dev_audio,
+                       hipStream_t s) {
+    mimi_engine* e = st->e;
+    const mimi_config& c = e->cfg;
+    const int B = st->B, K = st->K, Hd = c.hidden_size, Dq = c.vq_hidden_dim, H = c.num_attention_heads, Dh = c.head_dim;
+    const int R = 2 * n, H0 = c.kernel_size - 1, HL = c.last_kernel_size - 1;
+    const int64_t P = 2 * st->pos;  // the absolute 25 Hz row of the step's first
+    int rc;
+    HIP_TRY(hipMemsetAsync(e->dec_flag, 0, sizeof(unsigned), s));
+    Recorder rec{e, s};
+    rec.begin();
+    const char* kname = "?";
+    char nm[64];
+    // where each carry's rows sit in the workspace, in the order of stream_carry_plan: in front of the item's chunk
+    std::vector<float*> where = {w.emb, w.xin};
+    std::vector<int64_t> rows = {n, R};  // the chunk's rows behind each carry
+    {
+        int64_t len = R;
+        for (int si = 0; si < c.num_ratios; ++si) {
+            where.push_back(w.xe[si]);
+            rows.push_back(len);
+            len *= c.upsampling_ratios[si];
+            where.push_back(w.raw[si]);
+            rows.push_back(len);
+        }
+        where.push_back(w.xe[c.num_ratios]);
+        rows.push_back(len);
+    }
+    CarryTable in{}, outc{};
+    for (size_t i = 0; i < where.size(); ++i) {
+        const int64_t hc = (int64_t)st->carry_h[i] * st->carry_c[i], bs = (st->carry_h[i] + rows[i]) * st->carry_c[i];
+        in.c[i] = {st->state + st->carry_off[i], where[i], hc, bs, (int)hc};
+        outc.c[i] = {where[i] + rows[i] * st->carry_c[i], st->state + st->carry_off[i], bs, hc, (int)hc};
+    }
+    in.n = outc.n = (int)where.size();
+    LAUNCH_TRY(launch_stream_carry(in, B, s), "stream carry (in)");
+    rec.mark("dec_carry", 0, 0, "mimi::stream_carry_kernel");
+
+    // ---- quantizer.decode + upsample ----
+    LAUNCH_TRY(launch_rvq_decode(dev_codes, (long long)B * n, n, K, c.num_semantic_quantizers, c.codebook_size,
+                                 c.codebook_dim, e->cb_rows, w.sums, e->dec_flag, s, nullptr, nullptr, 0),
+               "rvq_decode");
+    rec.mark("dec_rvq", (double)B * n * K * Dq, (double)B * n * (K * Dq + 2 * Dq) * 4, "mimi::rvq_decode_kernel");
+    const int64_t emb_bs = (int64_t)(1 + n) * Hd;
+    GemmArgs ap = linear_args(w.sums, n, 2 * Dq, e->outproj, Hd, w.emb + Hd);
+    ap.batch = B;
+    ap.a_bstride = (int64_t)n * 2 * Dq;
+    ap.c_bstride = emb_bs;
+    LAUNCH_TRY(launch_gemm(ROLE_INPROJ, ap, s, &kname, PREC_F32), "output_proj");
+    rec.mark("dec_output_proj", 2.0 * B * n * 2 * Dq * Hd, (double)B * n * (2 * Dq + Hd) * 4, kname);
+    if ((rc = save_tap_strided(e, "quantized", w.emb + Hd, B, n, Hd, emb_bs, s))) return rc;
+    LAUNCH_TRY(launch_upsample_dw_hist(w.emb + Hd, e->upsample_w, w.t0, B, n, Hd, emb_bs, s), "upsample");
+    rec.mark("dec_upsample", 4.0 * B * R * Hd, 3.0 * B * n * Hd * 4, "mimi::upsample_dw_hist_kernel");
+    if ((rc = save_tap(e, "upsample", w.t0, B, R, Hd, s))) return rc;
+
+    // ---- decoder transformer: run_transformer_f32's launches with the stream's RoPE rows and ring attention ----
+    {
+        const int64_t frows = (int64_t)B * R;
+        auto fl = [](const GemmArgs& a) { return 2.0 * a.batch * (double)a.M * a.N * a.K; };
+        auto by = [](const GemmArgs& a, bool res) {
+            return ((double)a.batch * a.M * (a.K + a.N * (res ? 2 : 1)) + (double)a.N * a.K) * 4;
+        };
+        double att_flops = 0;
+        for (int i = 0; i < R; ++i) att_flops += 4.0 * Dh * std::min<int64_t>(P + i + 1, c.sliding_window);
+        att_flops *= (double)H * B;
+        for (size_t l = 0; l < e->dxf.size(); ++l) {
+            const DevXfmr& x = e->dxf[l];
+            LAUNCH_TRY(launch_layernorm(w.t0, x.ln1_w, x.ln1_b, w.t1, frows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f,
+                                        nullptr, nullptr, 0, e->ln_rpw),
+                       "ln1");
+            rec.mark("dec_layernorm", 0, 2.0 * frows * Hd * 4, ln_kname(e->ln_rpw));
+            GemmArgs aq = linear_args(w.t1, R, Hd, x.wqkv, 3 * H * Dh, w.qkv);
+            aq.batch = B;
+            aq.a_bstride = (int64_t)R * Hd;
+            aq.c_bstride = (int64_t)R * 3 * H * Dh;
+            aq.rope_cos = st->rope_cos;  // row m of an item is absolute row P + m: the tables hold rows P ..
+            aq.rope_sin = st->rope_sin;
+            aq.rope_cols = 2 * H * Dh;
+            LAUNCH_TRY(launch_gemm(ROLE_QKV, aq, s, &kname, PREC_F32), "qkv");
+            rec.mark("dec_qkv", fl(aq), by(aq, false), kname);
+            float* kr = st->kring + l * st->ring_layer;
+            float* vr = st->vring + l * st->ring_layer;
+            LAUNCH_TRY(launch_attention_stream(w.qkv, kr, vr, w.att, B, R, H, Dh, c.sliding_window, st->cap, P,
+                                               1.0f / std::sqrt((float)Dh), s),
+                       "attention (stream)");
+            rec.mark("dec_attention", att_flops, (double)frows * 4 * Hd * 4, "mimi::attention_stream_kernel");
+            LAUNCH_TRY(launch_attention_stream_append(w.qkv, kr, vr, B, R, H, Dh, st->cap, P, s), "kv append");
+            rec.mark("dec_kv_append", 0, (double)frows * 4 * H * Dh * 4, "mimi::attention_stream_append_kernel");
+            GemmArgs ao = linear_args(w.att, frows, H * Dh, x.wo, Hd, w.t0);
+            ao.R = w.t0;
+            ao.scale = x.ls1;
+            LAUNCH_TRY(launch_gemm(ROLE_OPROJ, ao, s, &kname, PREC_F32), "o_proj");
+            rec.mark("dec_o_proj", fl(ao), by(ao, true), kname);
+            LAUNCH_TRY(launch_layernorm(w.t0, x.ln2_w, x.ln2_b, w.t1, frows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f,
+                                        nullptr, nullptr, 0, e->ln_rpw),
+                       "ln2");
+            rec.mark("dec_layernorm", 0, 2.0 * frows * Hd * 4, ln_kname(e->ln_rpw));
+            GemmArgs a1 = linear_args(w.t1, frows, Hd, x.w1, c.intermediate_size, w.ff);
+            LAUNCH_TRY(launch_gemm(ROLE_FC1, a1, s, &kname, PREC_F32), "fc1");
+            rec.mark("dec_fc1", fl(a1), by(a1, false), kname);
+            GemmArgs a2 = linear_args(w.ff, frows, c.intermediate_size, x.w2, Hd, w.t0);
+            a2.R = w.t0;
+            a2.scale = x.ls2;
+            LAUNCH_TRY(launch_gemm(ROLE_FC2, a2, s, &kname, PREC_F32), "fc2");
+            rec.mark("dec_fc2", fl(a2), by(a2, true), kname);
+        }
+    }
+    snprintf(nm, sizeof nm, "xfmr%d", c.num_hidden_layers - 1);
+    if ((rc = save_tap(e, nm, w.t0, B, R, Hd, s))) return rc;
+    {  // the transformer's flat rows behind decoder.layers.0's carry
+        CarryTable mv{};
+        mv.c[0] = {w.t0, w.xin + (int64_t)H0 * Hd, (int64_t)R * Hd, (int64_t)(H0 + R) * Hd, R * Hd};
+        mv.n = 1;
+        LAUNCH_TRY(launch_stream_carry(mv, B, s), "stream carry (transformer rows)");
+        rec.mark("dec_carry", 0, 2.0 * B * R * Hd * 4, "mimi::stream_carry_kernel");
+    }
+
+    // ---- SEANet decoder ----
+    // a conv over `len` rows per item whose input has hh carry rows in front: the carry is read where conv_args pads
+    auto conv = [&](const DevConv& cv, const float* in, int hh, int64_t len, float* out, int64_t out_bs) {
+        GemmArgs a = conv_args(cv, in, hh + len, out, len, B);
+        a.a_off += (int64_t)hh * cv.cin;
+        a.c_bstride = out_bs;
+        return a;
+    };
+    auto fl = [&](const GemmArgs& a) { return 2.0 * B * (double)a.M * a.N * a.K; };
+    auto by = [&](const GemmArgs& a) { return ((double)B * a.M * (a.a_rs + a.N) + (double)a.N * a.K) * 4; };
+    int C = c.num_filters << c.num_ratios;
+    if (e->taps) {  // the raw layer-0 output (the pass itself only needs its ELU)
+        GemmArgs at = conv(e->dec_first, w.xin, H0, R, w.tap, (int64_t)R * C);
+        LAUNCH_TRY(launch_gemm(ROLE_DOWN, at, s, &kname, PREC_F32), "decoder conv 0 (tap)");
+        rec.mark("dec_conv0_tap", fl(at), by(at), kname);
+        if ((rc = save_tap(e, "dconv0", w.tap, B, R, C, s))) return rc;
+    }
+    int64_t len = R;
+    GemmArgs a0 = conv(e->dec_first, w.xin, H0, R, w.xe[0] + C, (1 + len) * C);
+    LAUNCH_TRY(launch_gemm(ROLE_DOWN_ELU, a0, s, &kname, PREC_F32), "decoder conv 0");
+    rec.mark("dec_conv0", fl(a0), by(a0), kname);
+    if ((rc = save_tap_strided(e, "dconv0_elu", w.xe[0] + C, B, len, C, (1 + len) * C, s))) return rc;
+    for (int si = 0; si < c.num_ratios; ++si) {
+        const int r = c.upsampling_ratios[si], Co = C / 2;
+        const int64_t olen = len * r;
+        // [len][C] -> [len][r * C/2] = [len * r][C/2], behind the residual block's 2 carry rows
+        GemmArgs au = conv(e->dec_up[si], w.xe[si], 1, len, w.raw[si] + 2 * Co, (2 + olen) * Co);
+        LAUNCH_TRY(launch_gemm(ROLE_UPCONV, au, s, &kname, PREC_F32), "up conv");
+        snprintf(nm, sizeof nm, "dec_up_s%d", si);
+        rec.mark(nm, fl(au), by(au), kname);
+        snprintf(nm, sizeof nm, "up%d", si);
+        if ((rc = save_tap_strided(e, nm, w.raw[si] + 2 * Co, B, olen, Co, (2 + olen) * Co, s))) return rc;
+        const int hn = si + 1 < c.num_ratios ? 1 : HL;  // the carry rows of the stage that reads this block's output
+        ResArgs ra{};
+        ra.x = w.raw[si] + 2 * Co;
+        ra.T = olen;
+        ra.batch = B;
+        ra.w3 = e->dec_res3[si].w;
+        ra.b3 = e->dec_res3[si].b;
+        ra.w1 = e->dec_res1[si].w;
+        ra.b1 = e->dec_res1[si].b;
+        ra.y = w.xe[si + 1] + (int64_t)hn * Co;
+        ra.hist = 2;
+        ra.x_bstride = (2 + olen) * Co;
+        ra.y_bstride = (hn + olen) * Co;
+        LAUNCH_TRY(launch_resblock(Co, ra, s, &kname), "decoder resblock");
+        snprintf(nm, sizeof nm, "dec_res_s%d", si);
+        const double Hh = Co / c.compress;
+        rec.mark(nm, 2.0 * B * olen * (3.0 * Co * Hh + Hh * Co), (double)B * olen * 2 * Co * 4, kname);
+        snprintf(nm, sizeof nm, "dres%d_elu", si);
+        if ((rc = save_tap_strided(e, nm, ra.y, B, olen, Co, ra.y_bstride, s))) return rc;
+        C = Co;
+        len = olen;
+    }
+    LAUNCH_TRY(launch_final_conv_hist(w.xe[c.num_ratios] + (int64_t)HL * C, e->dec_last.w, e->dec_last.b, dev_audio, B,
+                                      len, C, c.last_kernel_size, (HL + len) * C, s),
+               "final conv");
+    rec.mark("dec_final", 2.0 * B * len * C * c.last_kernel_size, (double)B * len * (C + 1) * 4,
+             "mimi::final_conv_hist_kernel");
+    LAUNCH_TRY(launch_stream_carry(outc, B, s), "stream carry (out)");
+    rec.mark("dec_carry", 0, 0, "mimi::stream_carry_kernel");
+    return MIMI_OK;
+}
+
+extern "C" int mimi_decode_stream_step(mimi_decode_stream* st, const int32_t* dev_codes, int32_t n, float* dev_audio,
+                                       void* stream) {
+    if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
+    mimi_engine* e = st->e;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (st->failed) return set_err(MIMI_ERR_STATE, "decode stream: a step failed; mimi_decode_stream_reset first");
+    if (n < 1 || n > st->max_n || !dev_codes || !dev_audio)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream step of %d frames outside [1, %d]", n, st->max_n);
+    const mimi_config& c = e->cfg;
+    const int R = 2 * n, half = c.head_dim / 2;
+    const int64_t P = 2 * st->pos;
+    // RoPE multiplies inv_freq by (float)row: exact only while the row fits float32's 24-bit significand
+    if (P + R > (1LL << 24))
+        return set_err(MIMI_ERR_UNSUPPORTED, "decode stream: row %lld no longer fits a float32 exactly", (long long)(P + R));
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int rc;
+    if ((rc = ensure_dws(e, stream_ws_layout(e, st->B, n, e->taps).bytes))) return rc;  // (state untouched so far)
+    const StreamWs w = stream_ws_layout(e, st->B, n, e->taps);
+    // rows P .. P + R - 1 of the RoPE tables, by ensure_rope's expressions (the previous step synchronised s before it
+    // returned: nothing reads the pinned image any more)
+    float* cs = st->rope_host;
+    float* sn = cs + (size_t)R * half;
+    for (int d = 0; d < half; ++d) {
+        const float expo = (float)(2 * d) / (float)c.head_dim;
+        const float pw = (float)std::pow((double)c.rope_theta, (double)expo);
+        const float inv = 1.0f / pw;
+        for (int i = 0; i < R; ++i) {
+            volatile float fr = inv * (float)(P + i);
+            cs[(size_t)i * half + d] = (float)std::cos((double)fr);
+            sn[(size_t)i * half + d] = (float)std::sin((double)fr);
+        }
+    }
+    st->failed = true;  // from here on a failure leaves the state half-advanced
+    HIP_TRY(hipMemcpyAsync(st->rope_cos, cs, (size_t)R * half * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(st->rope_sin, sn, (size_t)R * half * 4, hipMemcpyHostToDevice, s));
+    if ((rc = stream_pass(st, dev_codes, n, w, dev_audio, s))) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    if ((rc = save_tap(e, "audio", dev_audio, st->B, decode_upsampling(c) * n, 1, s))) return rc;
+    if ((rc = read_decode_flag(e, s))) return rc;
+    st->failed = false;
+    st->pos += n;
+    return MIMI_OK;
 }
 
 extern "C" void mimi_destroy(mimi_engine* e) {

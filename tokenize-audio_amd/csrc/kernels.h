@@ -334,6 +334,10 @@ struct ResArgs {
     // ragged decode (fp32 resblock_ragged_kernel, C = 64 .. 512, no conv0 fusion): item b's ilen[b] rows start at row
     // ioff[b] of the packed x / y; T = the longest item's rows (the grid).  null = the forms above
     const int* ioff;
+    // streamed decode (fp32 resblock_hist_kernel, C = 64 .. 512): hist = 2 -- item b's T rows start at x + b x_bstride
+    // with its 2 rows of history (real data, not zeros) right in front of them, and its output rows at y + b y_bstride
+    int hist;
+    long long x_bstride, y_bstride;
 };
 hipError_t launch_resblock(int C, const ResArgs& a, hipStream_t s, const char** kname);
 // stage 0 + down conv 0 in one kernel (PREC_F16X3)
@@ -480,6 +484,38 @@ hipError_t launch_upsample_dw(const float* x, const float* w, float* y, int batc
 hipError_t launch_final_conv(const float* x, const float* w, const float* bias, float* y, int batch, long long L, int C,
                              int ksize, hipStream_t s, const int* llen = nullptr, const int* loff = nullptr,
                              long long max_llen = 0);
+
+// History forms (the streamed decode, uniform batches only): item b's rows start at x + b * x_bstride and the rows
+// [-H, 0) in front of them are the stream's carry (H = 1 for the upsample, 2 for the last conv), read instead of zeros;
+// y is dense ([B][2T][C] / [B][L]).  Per row the arithmetic is that of the forms above.
+hipError_t launch_upsample_dw_hist(const float* x, const float* w, float* y, int batch, long long T, int C,
+                                   long long x_bstride, hipStream_t s);
+hipError_t launch_final_conv_hist(const float* x, const float* w, const float* bias, float* y, int batch, long long L,
+                                  int C, int ksize, long long x_bstride, hipStream_t s);
+
+// Streamed decode (attn_stream.hip).
+// attention_stream_kernel: the step's R query rows per (item, head) at absolute rows pos0 .. pos0 + R - 1 against the
+// keys / values of rows (row - window, row]: rows >= pos0 from the step's own fused qkv [B][R][3 H 64] (q, k rotated),
+// older ones from the ring ([B][H][cap][64] each for k and v, row r in slot r % cap).  fp32; out [B][R][H 64].
+hipError_t launch_attention_stream(const float* qkv, const float* kring, const float* vring, float* out, int batch,
+                                   int R, int H, int D, int window, int cap, long long pos0, float scale, hipStream_t s);
+// the step's k / v rows into their ring slots (after the attention that may still read the rows they replace)
+hipError_t launch_attention_stream_append(const float* qkv, float* kring, float* vring, int batch, int R, int H, int D,
+                                          int cap, long long pos0, hipStream_t s);
+// stream_carry_kernel: n strided copies in one launch; copy d moves `count` floats (a multiple of 4) per item from
+// src + b * src_bstride to dst + b * dst_bstride.  Source and destination never overlap.
+struct CarryCopy {
+    const float* src;
+    float* dst;
+    long long src_bstride, dst_bstride;
+    int count;
+};
+constexpr int CARRY_MAX = 16;
+struct CarryTable {
+    CarryCopy c[CARRY_MAX];
+    int n;
+};
+hipError_t launch_stream_carry(const CarryTable& t, int batch, hipStream_t s);
 
 // polyphase resampler (resample.hip): clips packed at in_off / out_off (device int64 arrays), one launch
 hipError_t launch_resample_poly(const float* x, const long long* in_off, const long long* in_len, int nclips,

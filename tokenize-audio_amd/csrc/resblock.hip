@@ -84,9 +84,14 @@ __device__ __forceinline__ void store_y_block(const ResArgs& p, float* stg, cons
 
 // RG (the ragged decode pass, never with the conv0 fusion): item b has p.ilen[b] rows starting at row p.ioff[b] of the
 // packed x / y; the BM tiling starts at the item's first row, as alone, and a tile past its rows exits before any load
-template <int C, int BM, bool WINDOW, bool FIRST, int W1M, int W1N, int W2M, int W2N, int NP, bool RG>
+// HS (a step of a decode stream, never with RG or the conv0 fusion): item b's T rows start at p.x + b p.x_bstride and
+// rows -2, -1 in front of them are the stream's carry -- real data, read where the other forms pad with zeros; its
+// output rows start at p.y + b p.y_bstride (the next stage's buffer, behind that stage's own carry rows)
+template <int C, int BM, bool WINDOW, bool FIRST, int W1M, int W1N, int W2M, int W2N, int NP, bool RG, bool HS = false>
 __device__ __forceinline__ void resblock_body(const ResArgs& p) {
     static_assert(!(RG && FIRST), "ragged blocks read x");
+    static_assert(!(HS && (RG || FIRST)), "history blocks are uniform and read x");
+    constexpr long long PAD0 = HS ? -2 : 0;  // the first row that exists
     constexpr int H = C / 2;
     constexpr int K1 = 3 * C;
     constexpr int LDK = 36;
@@ -119,7 +124,8 @@ __device__ __forceinline__ void resblock_body(const ResArgs& p) {
     const int b = blockIdx.y;
     const long long T = RG ? (long long)p.ilen[b] : p.T;
     if (RG && m0 >= T) return;
-    const long long xoff = RG ? (long long)p.ioff[b] * C : (long long)b * T * C;  // the item's first element of x / y
+    const long long xoff = HS ? (long long)b * p.x_bstride
+                              : RG ? (long long)p.ioff[b] * C : (long long)b * T * C;  // the item's first element of x / y
     const float* __restrict__ xb = p.x + xoff;
 
     // ---------------- GEMM1: h = ELU(x) (*) W3 ----------------
@@ -157,7 +163,7 @@ __device__ __forceinline__ void resblock_body(const ResArgs& p) {
             const int r = idx / (C / 4), c = (idx % (C / 4)) * 4;
             const long long pos = m0 - 2 + r;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (idx < TOT && pos >= 0 && pos < T) v = *reinterpret_cast<const f32x4*>(xb + pos * C + c);
+            if (idx < TOT && pos >= PAD0 && pos < T) v = *reinterpret_cast<const f32x4*>(xb + pos * C + c);
             pre[i] = v;
         }
 #pragma unroll
@@ -176,7 +182,7 @@ __device__ __forceinline__ void resblock_body(const ResArgs& p) {
                 const int r = idx >> 3, c = (idx & 7) * 4;
                 const long long e = (m0 + r - 2) * C + k0 + c;  // causal pad 2 rows; rows >= T never read
                 f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (m0 + r < T && e >= 0) v = *reinterpret_cast<const f32x4*>(xb + e);
+                if (m0 + r < T && e >= PAD0 * C) v = *reinterpret_cast<const f32x4*>(xb + e);
                 ra[i] = v;
             }
         }
@@ -287,7 +293,7 @@ __device__ __forceinline__ void resblock_body(const ResArgs& p) {
     }
 
     // ---------------- GEMM2: y = ELU(x + b1 + h . W1^T), NP columns per pass ----------------
-    const long long ybase = xoff;
+    const long long ybase = HS ? (long long)b * p.y_bstride : xoff;
     float ymx = 0.0f;  // max|y| (fp16 planes: the engine's range check)
     for (int n0 = 0; n0 < C; n0 += NP) {
         auto load2 = [&](int k0) {
@@ -369,6 +375,10 @@ __global__ __launch_bounds__(256) void resblock_kernel(ResArgs p) {
 template <int C, int BM, bool WINDOW, int W1M, int W1N, int W2M, int W2N, int NP>
 __global__ __launch_bounds__(256) void resblock_ragged_kernel(ResArgs p) {
     resblock_body<C, BM, WINDOW, false, W1M, W1N, W2M, W2N, NP, true>(p);
+}
+template <int C, int BM, bool WINDOW, int W1M, int W1N, int W2M, int W2N, int NP>
+__global__ __launch_bounds__(256) void resblock_hist_kernel(ResArgs p) {
+    resblock_body<C, BM, WINDOW, false, W1M, W1N, W2M, W2N, NP, false, true>(p);
 }
 
 
@@ -1044,8 +1054,33 @@ static hipError_t run_res_ragged(const ResArgs& a, hipStream_t s, const char** k
     return hipGetLastError();
 }
 
+// a step of a decode stream (a.hist = 2: the rows in front of each item's are its carry): the fp32 block of the same tile
+template <int C, int BM, bool WINDOW, int W1M, int W1N, int W2M, int W2N, int NP>
+static hipError_t run_res_hist(const ResArgs& a, hipStream_t s, const char** kname) {
+    static thread_local char name[160];
+    if (!name[0])
+        snprintf(name, sizeof(name), "mimi::resblock_hist_kernel<%d, %d, %s, %d, %d, %d, %d, %d>", C, BM,
+                 WINDOW ? "true" : "false", W1M, W1N, W2M, W2N, NP);
+    if (kname) *kname = name;
+    dim3 grid((unsigned)((a.T + BM - 1) / BM), a.batch);
+    hipLaunchKernelGGL((resblock_hist_kernel<C, BM, WINDOW, W1M, W1N, W2M, W2N, NP>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_resblock(int C, const ResArgs& a, hipStream_t s, const char** kname) {
     if (a.T <= 0 || a.batch <= 0) return hipErrorInvalidValue;
+    if (a.hist) {
+        if (a.hist != 2 || a.ioff || a.ilen || a.audio || a.wh16 || a.yns != 0 || !a.x || !a.y || a.batch > 65535 ||
+            a.x_bstride < (a.T + 2) * C || a.y_bstride < a.T * C || a.x_bstride % 4 || a.y_bstride % 4)
+            return hipErrorInvalidValue;
+        switch (C) {
+            case 64: return run_res_hist<64, 128, true, 4, 1, 4, 1, 64>(a, s, kname);
+            case 128: return run_res_hist<128, 64, true, 2, 2, 2, 2, 128>(a, s, kname);
+            case 256: return run_res_hist<256, 64, false, 2, 2, 2, 2, 128>(a, s, kname);
+            case 512: return run_res_hist<512, 32, false, 1, 4, 1, 4, 256>(a, s, kname);
+            default: return hipErrorInvalidValue;
+        }
+    }
     if (a.ioff) {
         if (!a.ilen || a.audio || a.wh16 || a.yns != 0 || !a.x || !a.y || a.batch > 65535) return hipErrorInvalidValue;
         switch (C) {

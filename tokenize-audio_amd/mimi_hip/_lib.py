@@ -33,6 +33,8 @@ EXPORTED_SYMBOLS = (
     "mimi_enable_decode", "mimi_create_from_dir_flags", "mimi_decoded_length", "mimi_decoded_length_cfg", "mimi_decode",
     "mimi_rvq_decode", "mimi_decode_workspace_bytes", "mimi_upconv_relayout",
     "mimi_decode_ragged", "mimi_decode_ragged_workspace_bytes",
+    "mimi_decode_stream_create", "mimi_decode_stream_step", "mimi_decode_stream_reset", "mimi_decode_stream_position",
+    "mimi_decode_stream_state_bytes", "mimi_decode_stream_destroy",
     "mimi_bpe_model_create", "mimi_bpe_model_destroy", "mimi_bpe_encode", "mimi_bpe_model_info",
     "mimi_bpe_model_set_alphabet", "mimi_bpe_encode_codes",
     "mimi_bpe_create_opts", "mimi_bpe_info", "mimi_bpe_read_pairs", "mimi_bpe_read_words",
@@ -172,6 +174,12 @@ def _declare(lib):
         "mimi_upconv_relayout": (c.c_int, [vp, c.c_int32, c.c_int32, c.c_int32, vp]),
         "mimi_decode_ragged": (c.c_int, [vp, vp, vp, c.c_int32, c.c_int64, c.c_int32, vp, vp]),
         "mimi_decode_ragged_workspace_bytes": (c.c_int64, [vp, vp, c.c_int32]),
+        "mimi_decode_stream_create": (c.c_int, [vp, c.c_int32, c.c_int32, c.c_int32, c.POINTER(vp)]),
+        "mimi_decode_stream_step": (c.c_int, [vp, vp, c.c_int32, vp, vp]),
+        "mimi_decode_stream_reset": (c.c_int, [vp]),
+        "mimi_decode_stream_position": (c.c_int64, [vp]),
+        "mimi_decode_stream_state_bytes": (c.c_int64, [vp]),
+        "mimi_decode_stream_destroy": (None, [vp]),
         "mimi_resample_poly": (c.c_int, [vp, vp, vp, c.c_int32, vp, vp, vp, c.c_int64, vp, c.c_int32, c.c_int32,
                                          c.c_int32, c.c_int64, vp]),
     }

@@ -11,6 +11,9 @@ Mirrors the model-level API every reference wrapper calls:
 * ``model.decode(audio_codes[B, K, T], padding_mask=None)`` (models built with ``decode=True``) ->
   ``MimiDecoderOutput`` with ``.audio_values`` float32 ``[B, 1, 1920 T]`` on the model's device
   (``TF/modeling_mimi.py:1408-1458``; ``librispeech-mimi/utils.py:72-81`` does ``.audio_values[0]``).
+* ``model.decode_stream(batch, num_quantizers, max_step_frames)`` -> ``DecodeStream``: ``.step(codes[B, K, n])`` returns
+  the ``1920 n`` samples of the next ``n`` frames from a KV cache and per-stage carries (the same bits under any split
+  of a sequence into steps).
 * ``.to(device)``, ``.eval()``, ``get_encoded_length``, ``from_pretrained(local_dir | "kyutai/mimi")``.
 
 The arithmetic runs in ``libmimi_hip.so`` (HIP kernels for gfx950); torch only supplies device memory and
@@ -22,6 +25,7 @@ import ctypes
 import glob
 import os
 import threading
+import weakref
 from dataclasses import dataclass
 from typing import Dict, Optional, Union
 
@@ -127,6 +131,94 @@ class EncodeTicket:
         return self.out
 
 
+class DecodeStream:
+    """Streaming decode (``MimiHipModel.decode_stream``): ``batch`` items advancing in lock-step, ``n`` new frames of
+    codes in and their ``1920 n`` samples out per ``step``, on a KV cache and per-stage carries that the stream owns
+    in device memory (``state_bytes``, constant).  The samples are bitwise the same under any split of a sequence into
+    steps, and within the activation tolerance of ``decode`` of the whole sequence.  A context manager; ``close()``
+    frees the state (closing the model closes its streams)."""
+
+    def __init__(self, model: "MimiHipModel", batch: int, num_quantizers: int, max_step_frames: int):
+        self._model, self.batch, self.num_quantizers = model, int(batch), int(num_quantizers)
+        self.max_step_frames = int(max_step_frames)
+        self._h = None
+        h = ctypes.c_void_p()
+        try:
+            _lib.check(model._lib.mimi_decode_stream_create(model._h, self.batch, self.num_quantizers,
+                                                            self.max_step_frames, ctypes.byref(h)))
+        except _lib.MimiHipError as err:
+            if err.status == 1:
+                raise ValueError(str(err)) from None
+            raise
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError("this DecodeStream is closed")
+        return self._h
+
+    @property
+    def position(self) -> int:
+        """Frames decoded so far."""
+        return int(self._model._lib.mimi_decode_stream_position(self._handle()))
+
+    @property
+    def state_bytes(self) -> int:
+        return int(self._model._lib.mimi_decode_stream_state_bytes(self._handle()))
+
+    def step(self, codes: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The next ``n`` frames: int64 / int32 codes ``[B, K, n]`` on any device -> float32 ``[B, 1, 1920 n]`` on the
+        model's device (``out`` if given).  ``ValueError`` for ``n`` outside ``[1, max_step_frames]`` (the state is
+        untouched) and for a code outside ``[0, codebook_size)`` (the stream then refuses until ``reset``)."""
+        m = self._model
+        h = self._handle()
+        if not torch.is_tensor(codes):
+            codes = torch.as_tensor(np.asarray(codes))
+        if codes.dim() != 3 or codes.shape[0] != self.batch or codes.shape[1] != self.num_quantizers:
+            raise ValueError(f"codes must be [{self.batch}, {self.num_quantizers}, n], got {tuple(codes.shape)}")
+        n = int(codes.shape[2])
+        if n < 1 or n > self.max_step_frames:
+            raise ValueError(f"a step takes 1 .. {self.max_step_frames} frames, got {n}")
+        L = m.get_decoded_length(n)
+        if out is None:
+            out = torch.empty((self.batch, 1, L), dtype=torch.float32, device=m.device)
+        elif (tuple(out.shape) != (self.batch, 1, L) or out.dtype != torch.float32 or out.device != m.device
+              or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 [{self.batch}, 1, {L}] tensor on {m.device}")
+        c = codes.to(device=m.device, dtype=torch.int32).contiguous()
+        try:
+            _lib.check(m._lib.mimi_decode_stream_step(h, ctypes.c_void_p(c.data_ptr()), n,
+                                                      ctypes.c_void_p(out.data_ptr()), m._stream()))
+        except _lib.MimiHipError as err:
+            if err.status == 1:
+                raise ValueError(str(err)) from None
+            raise
+        return out
+
+    def reset(self):
+        """Back to position 0 with zero state: what follows equals a fresh stream."""
+        _lib.check(self._model._lib.mimi_decode_stream_reset(self._handle()))
+
+    def close(self):
+        h, self._h = self._h, None
+        if h is not None and self._model._h is not None:
+            self._model._lib.mimi_decode_stream_destroy(h)
+        self._model._streams.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MimiHipModel:
     """Mimi on MI355X: encode always; decode (codes -> waveform) when built with ``decode=True``, which makes the
     decoder half of the checkpoint (``decoder*``, ``upsample*``, ``decoder_transformer*``, ``output_proj``) required.
@@ -144,6 +236,7 @@ class MimiHipModel:
         _lib.check(self._lib.mimi_create(ctypes.byref(self._cfg_c), self.device.index, ctypes.byref(handle)))
         self._h = handle
         self._lock = threading.Lock()
+        self._streams = weakref.WeakSet()  # open DecodeStreams: closed before the engine
         self._src = (state_dict, config, safetensors_path)  # for clone()
         self.decode_enabled = bool(decode)
         try:
@@ -197,6 +290,8 @@ class MimiHipModel:
     def close(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value:
+            for st in list(getattr(self, "_streams", ())):
+                st.close()
             self._lib.mimi_destroy(h)
         self._h = None
 
@@ -419,6 +514,22 @@ class MimiHipModel:
         if return_dict is False:
             return (audio, None)
         return MimiDecoderOutput(audio)
+
+    def decode_stream(self, batch: int = 1, num_quantizers: Optional[int] = None,
+                      max_step_frames: int = 16) -> DecodeStream:
+        """A streaming decode of ``batch`` items in lock-step (``mimi_decode_stream_*``): ``.step(codes[B, K, n])``
+        returns the ``1920 n`` samples of the next ``n <= max_step_frames`` frames.  Several streams may be open on
+        one model and interleave with ``decode`` / ``decode_ragged`` / ``encode``."""
+        self._require_decode()
+        K = self.config.num_quantizers if num_quantizers is None else int(num_quantizers)
+        if K > self.config.num_quantizers or K < 1:
+            raise ValueError(f"The number of quantizers (i.e codebooks) must be in [1, {self.config.num_quantizers}], "
+                             f"but is currently {K}.")
+        if int(batch) < 1 or int(max_step_frames) < 1:
+            raise ValueError(f"batch and max_step_frames must be >= 1, got {batch} and {max_step_frames}")
+        st = DecodeStream(self, batch, K, max_step_frames)
+        self._streams.add(st)
+        return st
 
     def decode_ragged_workspace_bytes(self, lengths) -> int:
         """Bytes of a ragged decode's workspace at the current taps setting (``mimi_decode_ragged_workspace_bytes``)."""
