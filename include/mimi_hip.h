@@ -256,7 +256,7 @@ int64_t mimi_decode_ragged_workspace_bytes(const mimi_engine* e, const int64_t* 
 
 /*
  * Streaming decode: codes to audio chunk by chunk on a KV cache.  A decode stream holds the decoder's state for `batch`
- * items advancing in lock-step: per item the few rows every causal stage reads from in front of a chunk (1 row of the
+ * items (SLOTS: each with its own position, stepped all together or any subset at a time, see below): per item the few rows every causal stage reads from in front of a chunk (1 row of the
  * embedding for the upsample, 6 of the transformer output for decoder.layers.0, 1 per up conv, 2 per residual block,
  * 2 for the last conv) and, per transformer layer, a ring of the rotated key / value rows of the last
  * sliding_window - 1 + 2 max_step_frames 25 Hz rows.  All of it is device memory owned by the stream
@@ -278,15 +278,45 @@ int64_t mimi_decode_ragged_workspace_bytes(const mimi_engine* e, const int64_t* 
  * encode graphs survive).  Taps and profiling as mimi_decode, holding the step's rows; the history forms record as
  * upsample_dw_hist_kernel, resblock_hist_kernel<...>, final_conv_hist_kernel and attention_stream_kernel.
  * mimi_decode_stream_reset: back to position 0 with zero state (a fresh stream).  Destroy every stream before its
- * engine.  Not provided: per-item positions (a ragged stream), hipGraph capture of a step, f16x3 arithmetic.
+ * engine.
+ *
+ * SLOTS.  Item b of the state is slot b: its own position, carries and rings, so sessions that start and end at
+ * different times share one stream.  mimi_decode_stream_step_slots advances the m slots it lists (`slots`: host, m
+ * distinct values in [0, batch), any order, need not outlive the call), all by the same n frames: item i of dev_codes
+ * [m][num_quantizers][n] and of dev_audio [m][mimi_decoded_length(n)] belongs to slot slots[i], whose position moves
+ * from p to p + n.  Nothing of an unlisted slot is read or written.  CONTRACT: a listed slot's samples are bitwise those
+ * of a batch = 1 stream fed that slot's sequence since its last reset, under any split of that sequence into steps,
+ * whatever the other slots are and where they stand, in any order of `slots`, whatever was called in between.  The
+ * launches are those of a lock-step step (the same count, whatever m, n and the positions); the kernels that touch the
+ * state record as attention_stream_slots_kernel, attention_stream_append_slots_kernel and stream_carry_slots_kernel.
+ * mimi_decode_stream_step means "all slots, in order 0 .. batch - 1" and is allowed at any time: while all slots stand
+ * at one position it is the lock-step pass (the kernels and bits it always had), otherwise a slot step.
+ * Errors of step_slots, with nothing launched and no state touched, MIMI_ERR_INVALID_ARGUMENT: m outside [1, batch], a
+ * slot outside [0, batch), a slot listed twice, n outside [1, max_step_frames], a NULL pointer; MIMI_ERR_UNSUPPORTED: a
+ * listed slot past the 2^24-row limit.  A code outside [0, codebook_size) fails the call as above; the flag is one word,
+ * so every slot LISTED IN THAT CALL (mimi_decode_stream_step: every slot) then returns MIMI_ERR_STATE when listed again,
+ * until mimi_decode_stream_reset_slot on it or mimi_decode_stream_reset; unlisted slots stay usable and their samples
+ * are unaffected.
+ * mimi_decode_stream_reset_slot: the slot back to position 0 with zero carries -- what follows equals a fresh stream;
+ * its neighbours are untouched.  (The slot's rings are not cleared: a query reads only ring rows written since the
+ * reset.)  mimi_decode_stream_position: the largest slot position (the position, on a stream stepped in lock-step);
+ * mimi_decode_stream_slot_position: one slot's, -1 for NULL or a slot out of range.  mimi_decode_stream_state_bytes
+ * counts the state; a slot step's two tables (12 bytes per slot) are a separate allocation.
+ * Not provided: a different n per slot within one call (group the sessions by n), hipGraph capture of a step, f16x3
+ * arithmetic.
  */
 typedef struct mimi_decode_stream mimi_decode_stream;
 int mimi_decode_stream_create(mimi_engine* e, int32_t batch, int32_t num_quantizers, int32_t max_step_frames,
                               mimi_decode_stream** out);
 int mimi_decode_stream_step(mimi_decode_stream* st, const int32_t* dev_codes /* [batch][num_quantizers][n] */, int32_t n,
                             float* dev_audio /* [batch][1920 n] */, void* stream);
+int mimi_decode_stream_step_slots(mimi_decode_stream* st, const int32_t* slots /* host, [m] */, int32_t m,
+                                  const int32_t* dev_codes /* [m][num_quantizers][n] */, int32_t n,
+                                  float* dev_audio /* [m][1920 n] */, void* stream);
 int mimi_decode_stream_reset(mimi_decode_stream* st);
-int64_t mimi_decode_stream_position(const mimi_decode_stream* st);    /* frames decoded so far */
+int mimi_decode_stream_reset_slot(mimi_decode_stream* st, int32_t slot);
+int64_t mimi_decode_stream_position(const mimi_decode_stream* st);    /* frames decoded so far (the largest slot's) */
+int64_t mimi_decode_stream_slot_position(const mimi_decode_stream* st, int32_t slot); /* -1: NULL / out of range */
 int64_t mimi_decode_stream_state_bytes(const mimi_decode_stream* st); /* constant over the stream's life */
 void mimi_decode_stream_destroy(mimi_decode_stream* st);
 

@@ -4,6 +4,9 @@
 //   attention_stream_kernel         a step's R = 2n query rows per (item, head) at absolute rows pos0 .. pos0 + R - 1
 //   attention_stream_append_kernel  the step's k / v rows into their ring slots (row r in slot r % cap)
 //   stream_carry_kernel             n strided copies in one launch, from a by-value table
+// and under the same bodies their slot forms (SL: a step over a subset of the stream's slots, each slot at its own
+// position): item b of the step takes its first row from pos_tab[b] and its rings / carries from slot slot_tab[b];
+// the step's own rows in the workspace stay indexed by b.  The tables are device memory (a step may list 65535 slots).
 //
 // CHUNKING DOES NOT MOVE A BIT.  Query row a (absolute) attends keys jlo = max(0, a - W + 1) .. a.  One WAVE owns the
 // row.  Key jlo + t belongs to lane t % 64; a lane's score is one fmaf chain over d = 0 .. 63; the maximum is exact
@@ -12,7 +15,8 @@
 // Every one of these orders is a function of a alone: not of pos0 (where the chunk starts), not of R (how long it
 // is), not of the ring slot a key sits in, nor of whether a key is read from the ring or from the step's own rows
 // (the ring holds copies of the very words the q/k/v GEMM stored).  So a row's output is the same bits under any
-// split of the sequence into steps.
+// split of the sequence into steps.  For the same reason the slot form moves no bit: giving every item of a step its
+// own pos0 and its own ring changes where a row's keys are read from, never which keys nor in which order.
 //
 // Scores live in the wave's own slice of LDS (W floats): written and read by the same wave, LDS order, no barrier;
 // waves without a row exit before any load.
@@ -22,22 +26,29 @@ namespace mimi {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(256) void attention_stream_kernel(const float* __restrict__ qkv,
-                                                               const float* __restrict__ kring,
-                                                               const float* __restrict__ vring,
-                                                               float* __restrict__ out, int R, int H, int window,
-                                                               int cap, long long pos0, float scale) {
+// SL: pos0 is pos_tab[b] and the ring is slot slot_tab[b]'s; b = blockIdx.z is uniform, so both are scalar loads
+template <bool SL>
+__device__ __forceinline__ void attention_stream_body(float* sc_all, const float* __restrict__ qkv,
+                                                      const float* __restrict__ kring,
+                                                      const float* __restrict__ vring, float* __restrict__ out, int R,
+                                                      int H, int window, int cap, long long pos0,
+                                                      const long long* __restrict__ pos_tab,
+                                                      const int* __restrict__ slot_tab, float scale) {
     constexpr int D = 64;
-    extern __shared__ __attribute__((aligned(16))) float sc_all[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = blockIdx.x * 4 + wave;  // the query's row in the step
     if (i >= R) return;
     const int h = blockIdx.y, b = blockIdx.z;
+    int rb = b;  // the item's place among the rings
+    if constexpr (SL) {
+        pos0 = pos_tab[b];
+        rb = slot_tab[b];
+    }
     float* sc = sc_all + wave * window;
     const long long ld = 3LL * H * D;
     const float* step = qkv + (long long)b * R * ld;               // the item's rows of this step
-    const long long ring = ((long long)b * H + h) * cap * D;      // the (item, head)'s ring
+    const long long ring = ((long long)rb * H + h) * cap * D;     // the (item, head)'s ring
     const long long a = pos0 + i;
     const long long jlo = a - window + 1 > 0 ? a - window + 1 : 0;
     const int cnt = (int)(a - jlo) + 1;  // 1 .. window keys, oldest first
@@ -94,6 +105,25 @@ __global__ __launch_bounds__(256) void attention_stream_kernel(const float* __re
     out[((long long)b * R + i) * (H * D) + h * D + lane] = acc * (1.0f / l);
 }
 
+__global__ __launch_bounds__(256) void attention_stream_kernel(const float* __restrict__ qkv,
+                                                               const float* __restrict__ kring,
+                                                               const float* __restrict__ vring,
+                                                               float* __restrict__ out, int R, int H, int window,
+                                                               int cap, long long pos0, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float sc_all[];
+    attention_stream_body<false>(sc_all, qkv, kring, vring, out, R, H, window, cap, pos0, nullptr, nullptr, scale);
+}
+
+__global__ __launch_bounds__(256) void attention_stream_slots_kernel(const float* __restrict__ qkv,
+                                                                     const float* __restrict__ kring,
+                                                                     const float* __restrict__ vring,
+                                                                     float* __restrict__ out, int R, int H, int window,
+                                                                     int cap, const long long* __restrict__ pos_tab,
+                                                                     const int* __restrict__ slot_tab, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float sc_all[];
+    attention_stream_body<true>(sc_all, qkv, kring, vring, out, R, H, window, cap, 0, pos_tab, slot_tab, scale);
+}
+
 hipError_t launch_attention_stream(const float* qkv, const float* kring, const float* vring, float* out, int batch,
                                    int R, int H, int D, int window, int cap, long long pos0, float scale,
                                    hipStream_t s) {
@@ -107,11 +137,26 @@ hipError_t launch_attention_stream(const float* qkv, const float* kring, const f
     return hipGetLastError();
 }
 
+hipError_t launch_attention_stream_slots(const float* qkv, const float* kring, const float* vring, float* out,
+                                         int batch, int R, int H, int D, int window, int cap, const long long* pos_tab,
+                                         const int* slot_tab, float scale, hipStream_t s) {
+    if (D != 64 || batch <= 0 || batch > 65535 || R <= 0 || H <= 0 || H > 65535 || window < 1 || cap < window - 1 ||
+        cap < 1 || !pos_tab || !slot_tab || !qkv || !kring || !vring || !out)
+        return hipErrorInvalidValue;
+    const size_t lds = (size_t)4 * window * sizeof(float);
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attention_stream_slots_kernel, dim3((unsigned)((R + 3) / 4), (unsigned)H, (unsigned)batch),
+                       dim3(256), lds, s, qkv, kring, vring, out, R, H, window, cap, pos_tab, slot_tab, scale);
+    return hipGetLastError();
+}
+
 // one thread per 16 B of the step's k and v rows: [b][row][k | v][head][16 float4]
-__global__ __launch_bounds__(256) void attention_stream_append_kernel(const float* __restrict__ qkv,
-                                                                      float* __restrict__ kring,
-                                                                      float* __restrict__ vring, int batch, int R, int H,
-                                                                      int cap, long long pos0) {
+// SL: item b's rows go to slot slot_tab[b], ring index (pos_tab[b] + i) % cap
+template <bool SL>
+__device__ __forceinline__ void attention_stream_append_body(const float* __restrict__ qkv, float* __restrict__ kring,
+                                                             float* __restrict__ vring, int batch, int R, int H, int cap,
+                                                             long long pos0, const long long* __restrict__ pos_tab,
+                                                             const int* __restrict__ slot_tab) {
     constexpr int D = 64;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long total = (long long)batch * R * 2 * H * (D / 4);
@@ -124,9 +169,30 @@ __global__ __launch_bounds__(256) void attention_stream_append_kernel(const floa
     r /= 2;
     const int i = (int)(r % R);
     const int b = (int)(r / R);
+    int rb = b;  // b < batch here: idx < total
+    if constexpr (SL) {
+        pos0 = pos_tab[b];
+        rb = slot_tab[b];
+    }
     const float* src = qkv + ((long long)b * R + i) * (3LL * H * D) + (long long)(1 + kv) * H * D + h * D + 4 * c4;
-    float* dst = (kv ? vring : kring) + (((long long)b * H + h) * cap + (pos0 + i) % cap) * D + 4 * c4;
+    float* dst = (kv ? vring : kring) + (((long long)rb * H + h) * cap + (pos0 + i) % cap) * D + 4 * c4;
     *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(src);
+}
+
+__global__ __launch_bounds__(256) void attention_stream_append_kernel(const float* __restrict__ qkv,
+                                                                      float* __restrict__ kring,
+                                                                      float* __restrict__ vring, int batch, int R, int H,
+                                                                      int cap, long long pos0) {
+    attention_stream_append_body<false>(qkv, kring, vring, batch, R, H, cap, pos0, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void attention_stream_append_slots_kernel(const float* __restrict__ qkv,
+                                                                            float* __restrict__ kring,
+                                                                            float* __restrict__ vring, int batch, int R,
+                                                                            int H, int cap,
+                                                                            const long long* __restrict__ pos_tab,
+                                                                            const int* __restrict__ slot_tab) {
+    attention_stream_append_body<true>(qkv, kring, vring, batch, R, H, cap, 0, pos_tab, slot_tab);
 }
 
 hipError_t launch_attention_stream_append(const float* qkv, float* kring, float* vring, int batch, int R, int H, int D,
@@ -142,17 +208,44 @@ hipError_t launch_attention_stream_append(const float* qkv, float* kring, float*
     return hipGetLastError();
 }
 
+hipError_t launch_attention_stream_append_slots(const float* qkv, float* kring, float* vring, int batch, int R, int H,
+                                                int D, int cap, const long long* pos_tab, const int* slot_tab,
+                                                hipStream_t s) {
+    if (D != 64 || batch <= 0 || R <= 0 || R > cap || H <= 0 || !pos_tab || !slot_tab || !qkv || !kring || !vring)
+        return hipErrorInvalidValue;
+    const long long total = (long long)batch * R * 2 * H * (D / 4);
+    const long long blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attention_stream_append_slots_kernel, dim3((unsigned)blocks), dim3(256), 0, s, qkv, kring, vring,
+                       batch, R, H, cap, pos_tab, slot_tab);
+    return hipGetLastError();
+}
+
 // copy blockIdx.z of the table, item blockIdx.y; 16 B per thread, grid-stride along x
-__global__ __launch_bounds__(256) void stream_carry_kernel(CarryTable t) {
+// SL: the stream's side of the copy (c.state) is slot slot_tab[item]'s, the workspace side the item's
+template <bool SL>
+__device__ __forceinline__ void stream_carry_body(const CarryTable& t, const int* __restrict__ slot_tab) {
     const CarryCopy& c = t.c[blockIdx.z];
-    const float* __restrict__ src = c.src + (long long)blockIdx.y * c.src_bstride;
-    float* __restrict__ dst = c.dst + (long long)blockIdx.y * c.dst_bstride;
+    long long sb = blockIdx.y, db = blockIdx.y;
+    if constexpr (SL) {
+        const int slot = slot_tab[blockIdx.y];
+        if (c.state == CARRY_STATE_SRC) sb = slot;
+        if (c.state == CARRY_STATE_DST) db = slot;
+    }
+    const float* __restrict__ src = c.src + sb * c.src_bstride;
+    float* __restrict__ dst = c.dst + db * c.dst_bstride;
     const int n4 = c.count / 4;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256)
         *reinterpret_cast<f32x4*>(dst + 4LL * i) = *reinterpret_cast<const f32x4*>(src + 4LL * i);
 }
 
-hipError_t launch_stream_carry(const CarryTable& t, int batch, hipStream_t s) {
+__global__ __launch_bounds__(256) void stream_carry_kernel(CarryTable t) { stream_carry_body<false>(t, nullptr); }
+
+__global__ __launch_bounds__(256) void stream_carry_slots_kernel(CarryTable t, const int* __restrict__ slot_tab) {
+    stream_carry_body<true>(t, slot_tab);
+}
+
+static hipError_t carry_grid(const CarryTable& t, int batch, dim3* grid) {
     if (t.n < 1 || t.n > CARRY_MAX || batch <= 0 || batch > 65535) return hipErrorInvalidValue;
     int most = 0;
     for (int d = 0; d < t.n; ++d) {
@@ -163,8 +256,24 @@ hipError_t launch_stream_carry(const CarryTable& t, int batch, hipStream_t s) {
         most = c.count > most ? c.count : most;
     }
     const int blocks = (most / 4 + 255) / 256;
-    hipLaunchKernelGGL(stream_carry_kernel, dim3((unsigned)(blocks < 64 ? blocks : 64), (unsigned)batch, (unsigned)t.n),
-                       dim3(256), 0, s, t);
+    *grid = dim3((unsigned)(blocks < 64 ? blocks : 64), (unsigned)batch, (unsigned)t.n);
+    return hipSuccess;
+}
+
+hipError_t launch_stream_carry(const CarryTable& t, int batch, hipStream_t s) {
+    dim3 grid;
+    const hipError_t err = carry_grid(t, batch, &grid);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(stream_carry_kernel, grid, dim3(256), 0, s, t);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_carry_slots(const CarryTable& t, int batch, const int* slot_tab, hipStream_t s) {
+    dim3 grid;
+    const hipError_t err = carry_grid(t, batch, &grid);
+    if (err != hipSuccess) return err;
+    if (!slot_tab) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stream_carry_slots_kernel, grid, dim3(256), 0, s, t, slot_tab);
     return hipGetLastError();
 }
 

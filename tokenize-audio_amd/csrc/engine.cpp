@@ -3388,19 +3388,32 @@ extern "C" int mimi_decode_ragged(mimi_engine* e, const int32_t* dev_codes, cons
 // Per row every kernel computes what it computes in mimi_decode and attention_stream_kernel reduces in an order
 // that is a function of the row's absolute position alone (attn_stream.hip): the samples are the same bits under any
 // split of the sequence into steps.
+//
+// SLOTS.  The state is laid out per item, so item b of it is a slot: its own position, carries and rings.
+// mimi_decode_stream_step_slots advances the m slots it lists, each from its own position: item i of the step's
+// workspace is slot slots[i] of the state.  What is indirected through the step's device tables (slot_tab, pos_tab:
+// uploaded with the step from pinned memory, like the RoPE rows) is exactly what touches the state -- the state side of
+// carry-in and carry-out, the rings' base and the position in the attention and the append -- and every other kernel
+// works on the workspace, indexed by the item's place in the step.  The q/k/v GEMM runs over the flat m * 2n rows with a
+// table of m * 2n RoPE rows in step order (a row's bits do not depend on the tile family, tests/test_decode_kernels.py).
+// mimi_decode_stream_step on slots that all stand at one position is the lock-step pass it always was (same launches,
+// same names); once the positions differ it is a slot step over 0 .. B - 1.
 // ================================================================================================
 struct mimi_decode_stream {
     mimi_engine* e = nullptr;
     int B = 0, K = 0, max_n = 0, cap = 0;
-    int64_t pos = 0;      // frames decoded so far
-    bool failed = false;  // a step failed after it had touched the state: refuse until reset
+    std::vector<int64_t> pos;  // per slot: frames decoded since its last reset
+    std::vector<char> failed;  // per slot: a step that listed it failed after it had touched the state: refuse until reset
     float* state = nullptr;  // one allocation: carries | k rings | v rings | RoPE cos | RoPE sin
     size_t state_bytes = 0, zero_bytes = 0;  // zero_bytes: the carries and rings, what reset clears
     std::vector<size_t> carry_off;           // floats: per carry, in the order of the table above
     std::vector<int> carry_h, carry_c;       // rows and channels of each
     float *kring = nullptr, *vring = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
     size_t ring_layer = 0;       // floats of one layer's ring
-    float* rope_host = nullptr;  // pinned: [cos | sin] of the step's rows
+    float* rope_host = nullptr;  // pinned: [cos | sin] of the step's rows (a slot step: of every item's, in step order)
+    // a slot step's tables, [B] first rows (int64) then [B] slots (int32): the pinned image and its device copy
+    char *tab_host = nullptr, *tab_dev = nullptr;
+    int64_t max_pos() const { return *std::max_element(pos.begin(), pos.end()); }
 };
 
 // the carries in stage order: upsample, decoder.layers.0, then per ratio (up conv, residual block), the last conv
@@ -3478,6 +3491,8 @@ extern "C" int mimi_decode_stream_create(mimi_engine* e, int32_t batch, int32_t 
     st->K = K;
     st->max_n = max_step_frames;
     st->cap = c.sliding_window - 1 + 2 * max_step_frames;
+    st->pos.assign(batch, 0);
+    st->failed.assign(batch, 0);
     stream_carry_plan(c, &st->carry_h, &st->carry_c);
     size_t off = 0;  // floats; every section a multiple of 64 floats
     auto take = [&](size_t floats) {
@@ -3490,7 +3505,9 @@ extern "C" int mimi_decode_stream_create(mimi_engine* e, int32_t batch, int32_t 
     st->ring_layer = (size_t)batch * c.num_attention_heads * st->cap * c.head_dim;
     const size_t kr = take(st->ring_layer * c.num_hidden_layers), vr = take(st->ring_layer * c.num_hidden_layers);
     st->zero_bytes = off * sizeof(float);
-    const size_t rope_floats = (size_t)2 * max_step_frames * (c.head_dim / 2);
+    // the RoPE rows of every item of a slot step (at B = 1 the rows of the step, as before)
+    const size_t rope_floats = (size_t)batch * 2 * max_step_frames * (c.head_dim / 2);
+    const size_t tab_bytes = (size_t)batch * (sizeof(int64_t) + sizeof(int32_t));
     const size_t rc_ = take(rope_floats), rs_ = take(rope_floats);
     st->state_bytes = off * sizeof(float);
     hipError_t err = hipMalloc(reinterpret_cast<void**>(&st->state), st->state_bytes);
@@ -3505,9 +3522,13 @@ extern "C" int mimi_decode_stream_create(mimi_engine* e, int32_t batch, int32_t 
     st->rope_sin = st->state + rs_;
     if ((err = hipMemset(st->state, 0, st->state_bytes)) != hipSuccess ||
         (err = hipHostMalloc(reinterpret_cast<void**>(&st->rope_host), 2 * rope_floats * sizeof(float),
-                             hipHostMallocDefault)) != hipSuccess) {
+                             hipHostMallocDefault)) != hipSuccess ||
+        (err = hipHostMalloc(reinterpret_cast<void**>(&st->tab_host), tab_bytes, hipHostMallocDefault)) != hipSuccess ||
+        (err = hipMalloc(reinterpret_cast<void**>(&st->tab_dev), tab_bytes)) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipFree(st->state);
+        if (st->rope_host) (void)hipHostFree(st->rope_host);
+        if (st->tab_host) (void)hipHostFree(st->tab_host);
         return set_err(MIMI_ERR_HIP, "decode stream state: %s", hipGetErrorString(err));
     }
     *out = st.release();
@@ -3521,6 +3542,8 @@ extern "C" void mimi_decode_stream_destroy(mimi_decode_stream* st) {
         (void)hipSetDevice(st->e->device);
         if (st->state) (void)hipFree(st->state);
         if (st->rope_host) (void)hipHostFree(st->rope_host);
+        if (st->tab_host) (void)hipHostFree(st->tab_host);
+        if (st->tab_dev) (void)hipFree(st->tab_dev);
     }
     delete st;
 }
@@ -3530,12 +3553,35 @@ extern "C" int mimi_decode_stream_reset(mimi_decode_stream* st) {
     std::lock_guard<std::mutex> lk(st->e->mu);
     HIP_TRY(hipSetDevice(st->e->device));
     HIP_TRY(hipMemset(st->state, 0, st->zero_bytes));
-    st->pos = 0;
-    st->failed = false;
+    st->pos.assign(st->B, 0);
+    st->failed.assign(st->B, 0);
     return MIMI_OK;
 }
 
-extern "C" int64_t mimi_decode_stream_position(const mimi_decode_stream* st) { return st ? st->pos : -1; }
+// One slot back to a fresh stream's: position 0 and zero carries.  Its rings keep their words: a query at row a reads
+// ring rows [max(0, a - W + 1), pos0) only, and all of those are written again before they are read.
+extern "C" int mimi_decode_stream_reset_slot(mimi_decode_stream* st, int32_t slot) {
+    if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
+    std::lock_guard<std::mutex> lk(st->e->mu);
+    if (slot < 0 || slot >= st->B)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream: slot %d outside [0, %d)", slot, st->B);
+    HIP_TRY(hipSetDevice(st->e->device));
+    for (size_t i = 0; i < st->carry_h.size(); ++i) {
+        const size_t hc = (size_t)st->carry_h[i] * st->carry_c[i];
+        HIP_TRY(hipMemset(st->state + st->carry_off[i] + (size_t)slot * hc, 0, hc * sizeof(float)));
+    }
+    st->pos[slot] = 0;
+    st->failed[slot] = 0;
+    return MIMI_OK;
+}
+
+// (the positions are only written under the engine mutex; a caller that reads them while another thread steps the
+// stream sees one side or the other of that step, as before)
+extern "C" int64_t mimi_decode_stream_position(const mimi_decode_stream* st) { return st ? st->max_pos() : -1; }
+
+extern "C" int64_t mimi_decode_stream_slot_position(const mimi_decode_stream* st, int32_t slot) {
+    return st && slot >= 0 && slot < st->B ? st->pos[slot] : -1;
+}
 
 extern "C" int64_t mimi_decode_stream_state_bytes(const mimi_decode_stream* st) {
     return st ? (int64_t)st->state_bytes : -1;
@@ -3561,14 +3607,22 @@ static int save_tap_strided(mimi_engine* e, const char* name, const float* src, 
     return MIMI_OK;
 }
 
-// the launches of one step (the workspace w sized for it, the step's RoPE rows already enqueued)
-static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int n, const StreamWs& w, float* dev_audio,
-                       hipStream_t s) {
+// the launches of one step over B items (the workspace w sized for it, the step's RoPE rows already enqueued).
+// slots == nullptr: the lock-step pass, B = st->B items that all stand at frame pos0[0].  Otherwise item i is slot
+// slots[i] at frame pos0[i] (host copies of the tables already enqueued to st->tab_dev).
+static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, int n, const int32_t* slots,
+                       const int64_t* pos0, const StreamWs& w, float* dev_audio, hipStream_t s) {
     mimi_engine* e = st->e;
     const mimi_config& c = e->cfg;
-    const int B = st->B, K = st->K, Hd = c.hidden_size, Dq = c.vq_hidden_dim, H = c.num_attention_heads, Dh = c.head_dim;
+    const int K = st->K, Hd = c.hidden_size, Dq = c.vq_hidden_dim, H = c.num_attention_heads, Dh = c.head_dim;
     const int R = 2 * n, H0 = c.kernel_size - 1, HL = c.last_kernel_size - 1;
-    const int64_t P = 2 * st->pos;  // the absolute 25 Hz row of the step's first
+    const int64_t P = 2 * pos0[0];  // lock-step: the absolute 25 Hz row of the step's first
+    const long long* pos_tab = reinterpret_cast<const long long*>(st->tab_dev);
+    const int* slot_tab = reinterpret_cast<const int*>(st->tab_dev + (size_t)st->B * sizeof(int64_t));
+    const char* carry_kn = slots ? "mimi::stream_carry_slots_kernel" : "mimi::stream_carry_kernel";
+    auto carry = [&](const CarryTable& t) {
+        return slots ? launch_stream_carry_slots(t, B, slot_tab, s) : launch_stream_carry(t, B, s);
+    };
     int rc;
     HIP_TRY(hipMemsetAsync(e->dec_flag, 0, sizeof(unsigned), s));
     Recorder rec{e, s};
@@ -3593,12 +3647,12 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int n, 
     CarryTable in{}, outc{};
     for (size_t i = 0; i < where.size(); ++i) {
         const int64_t hc = (int64_t)st->carry_h[i] * st->carry_c[i], bs = (st->carry_h[i] + rows[i]) * st->carry_c[i];
-        in.c[i] = {st->state + st->carry_off[i], where[i], hc, bs, (int)hc};
-        outc.c[i] = {where[i] + rows[i] * st->carry_c[i], st->state + st->carry_off[i], bs, hc, (int)hc};
+        in.c[i] = {st->state + st->carry_off[i], where[i], hc, bs, (int)hc, CARRY_STATE_SRC};
+        outc.c[i] = {where[i] + rows[i] * st->carry_c[i], st->state + st->carry_off[i], bs, hc, (int)hc, CARRY_STATE_DST};
     }
     in.n = outc.n = (int)where.size();
-    LAUNCH_TRY(launch_stream_carry(in, B, s), "stream carry (in)");
-    rec.mark("dec_carry", 0, 0, "mimi::stream_carry_kernel");
+    LAUNCH_TRY(carry(in), "stream carry (in)");
+    rec.mark("dec_carry", 0, 0, carry_kn);
 
     // ---- quantizer.decode + upsample ----
     LAUNCH_TRY(launch_rvq_decode(dev_codes, (long long)B * n, n, K, c.num_semantic_quantizers, c.codebook_size,
@@ -3625,31 +3679,45 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int n, 
             return ((double)a.batch * a.M * (a.K + a.N * (res ? 2 : 1)) + (double)a.N * a.K) * 4;
         };
         double att_flops = 0;
-        for (int i = 0; i < R; ++i) att_flops += 4.0 * Dh * std::min<int64_t>(P + i + 1, c.sliding_window);
-        att_flops *= (double)H * B;
+        for (int b = 0; b < (slots ? B : 1); ++b)
+            for (int i = 0; i < R; ++i)
+                att_flops += 4.0 * Dh * std::min<int64_t>(2 * pos0[b] + i + 1, c.sliding_window);
+        att_flops *= (double)H * (slots ? 1 : B);
         for (size_t l = 0; l < e->dxf.size(); ++l) {
             const DevXfmr& x = e->dxf[l];
             LAUNCH_TRY(launch_layernorm(w.t0, x.ln1_w, x.ln1_b, w.t1, frows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f,
                                         nullptr, nullptr, 0, e->ln_rpw),
                        "ln1");
             rec.mark("dec_layernorm", 0, 2.0 * frows * Hd * 4, ln_kname(e->ln_rpw));
-            GemmArgs aq = linear_args(w.t1, R, Hd, x.wqkv, 3 * H * Dh, w.qkv);
-            aq.batch = B;
-            aq.a_bstride = (int64_t)R * Hd;
-            aq.c_bstride = (int64_t)R * 3 * H * Dh;
-            aq.rope_cos = st->rope_cos;  // row m of an item is absolute row P + m: the tables hold rows P ..
+            // lock-step: batched, row m of an item is absolute row P + m and the tables hold rows P ..; slots: the flat
+            // rows, the tables hold every item's rows in step order
+            GemmArgs aq = linear_args(w.t1, slots ? frows : R, Hd, x.wqkv, 3 * H * Dh, w.qkv);
+            if (!slots) {
+                aq.batch = B;
+                aq.a_bstride = (int64_t)R * Hd;
+                aq.c_bstride = (int64_t)R * 3 * H * Dh;
+            }
+            aq.rope_cos = st->rope_cos;
             aq.rope_sin = st->rope_sin;
             aq.rope_cols = 2 * H * Dh;
             LAUNCH_TRY(launch_gemm(ROLE_QKV, aq, s, &kname, PREC_F32), "qkv");
             rec.mark("dec_qkv", fl(aq), by(aq, false), kname);
             float* kr = st->kring + l * st->ring_layer;
             float* vr = st->vring + l * st->ring_layer;
-            LAUNCH_TRY(launch_attention_stream(w.qkv, kr, vr, w.att, B, R, H, Dh, c.sliding_window, st->cap, P,
-                                               1.0f / std::sqrt((float)Dh), s),
+            const float qscale = 1.0f / std::sqrt((float)Dh);
+            LAUNCH_TRY(slots ? launch_attention_stream_slots(w.qkv, kr, vr, w.att, B, R, H, Dh, c.sliding_window, st->cap,
+                                                             pos_tab, slot_tab, qscale, s)
+                             : launch_attention_stream(w.qkv, kr, vr, w.att, B, R, H, Dh, c.sliding_window, st->cap, P,
+                                                       qscale, s),
                        "attention (stream)");
-            rec.mark("dec_attention", att_flops, (double)frows * 4 * Hd * 4, "mimi::attention_stream_kernel");
-            LAUNCH_TRY(launch_attention_stream_append(w.qkv, kr, vr, B, R, H, Dh, st->cap, P, s), "kv append");
-            rec.mark("dec_kv_append", 0, (double)frows * 4 * H * Dh * 4, "mimi::attention_stream_append_kernel");
+            rec.mark("dec_attention", att_flops, (double)frows * 4 * Hd * 4,
+                     slots ? "mimi::attention_stream_slots_kernel" : "mimi::attention_stream_kernel");
+            LAUNCH_TRY(slots ? launch_attention_stream_append_slots(w.qkv, kr, vr, B, R, H, Dh, st->cap, pos_tab,
+                                                                    slot_tab, s)
+                             : launch_attention_stream_append(w.qkv, kr, vr, B, R, H, Dh, st->cap, P, s),
+                       "kv append");
+            rec.mark("dec_kv_append", 0, (double)frows * 4 * H * Dh * 4,
+                     slots ? "mimi::attention_stream_append_slots_kernel" : "mimi::attention_stream_append_kernel");
             GemmArgs ao = linear_args(w.att, frows, H * Dh, x.wo, Hd, w.t0);
             ao.R = w.t0;
             ao.scale = x.ls1;
@@ -3675,8 +3743,8 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int n, 
         CarryTable mv{};
         mv.c[0] = {w.t0, w.xin + (int64_t)H0 * Hd, (int64_t)R * Hd, (int64_t)(H0 + R) * Hd, R * Hd};
         mv.n = 1;
-        LAUNCH_TRY(launch_stream_carry(mv, B, s), "stream carry (transformer rows)");
-        rec.mark("dec_carry", 0, 2.0 * B * R * Hd * 4, "mimi::stream_carry_kernel");
+        LAUNCH_TRY(carry(mv), "stream carry (transformer rows)");  // (no state side: by the item's place either way)
+        rec.mark("dec_carry", 0, 2.0 * B * R * Hd * 4, carry_kn);
     }
 
     // ---- SEANet decoder ----
@@ -3738,8 +3806,83 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int n, 
                "final conv");
     rec.mark("dec_final", 2.0 * B * len * C * c.last_kernel_size, (double)B * len * (C + 1) * 4,
              "mimi::final_conv_hist_kernel");
-    LAUNCH_TRY(launch_stream_carry(outc, B, s), "stream carry (out)");
-    rec.mark("dec_carry", 0, 0, "mimi::stream_carry_kernel");
+    LAUNCH_TRY(carry(outc), "stream carry (out)");
+    rec.mark("dec_carry", 0, 0, carry_kn);
+    return MIMI_OK;
+}
+
+// One step over the m listed slots (slots == nullptr: all st->B in order, at one position: the lock-step pass).
+// Called with the engine mutex held and every argument checked but the slots' state.
+static int stream_step_locked(mimi_decode_stream* st, const int32_t* slots, int m, const int32_t* dev_codes, int n,
+                              float* dev_audio, hipStream_t s) {
+    mimi_engine* e = st->e;
+    const mimi_config& c = e->cfg;
+    const int R = 2 * n, half = c.head_dim / 2;
+    auto slot_of = [&](int i) { return slots ? slots[i] : i; };
+    for (int i = 0; i < m; ++i)
+        if (st->failed[slot_of(i)])
+            return set_err(MIMI_ERR_STATE, "decode stream: a step of slot %d failed; mimi_decode_stream_reset(_slot) first",
+                           slot_of(i));
+    // RoPE multiplies inv_freq by (float)row: exact only while the row fits float32's 24-bit significand
+    for (int i = 0; i < m; ++i)
+        if (2 * st->pos[slot_of(i)] + R > (1LL << 24))
+            return set_err(MIMI_ERR_UNSUPPORTED, "decode stream: row %lld no longer fits a float32 exactly",
+                           (long long)(2 * st->pos[slot_of(i)] + R));
+    if (slots && (int64_t)m * R > 0x7fffffffLL)
+        return set_err(MIMI_ERR_UNSUPPORTED, "decode stream: %d slots x %d rows exceed the 32-bit row range", m, R);
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = ensure_dws(e, stream_ws_layout(e, m, n, e->taps).bytes))) return rc;  // (state untouched so far)
+    const StreamWs w = stream_ws_layout(e, m, n, e->taps);
+    // The pinned images (the previous step synchronised s before it returned: nothing reads them any more).  The
+    // tables: item i's first frame and its slot.  The RoPE rows by ensure_rope's expressions: lock-step rows P .. P + R - 1,
+    // a slot step item i's rows 2 pos_i .. 2 pos_i + R - 1 at table rows i R ..
+    std::vector<int64_t> pos0(m);  // frames
+    int64_t* row_img = reinterpret_cast<int64_t*>(st->tab_host);  // the kernels read positions in 25 Hz rows
+    int32_t* slot_img = reinterpret_cast<int32_t*>(st->tab_host + (size_t)st->B * sizeof(int64_t));
+    for (int i = 0; i < m; ++i) {
+        pos0[i] = st->pos[slot_of(i)];
+        if (slots) {
+            row_img[i] = 2 * pos0[i];
+            slot_img[i] = slots[i];
+        }
+    }
+    const int items = slots ? m : 1;
+    const size_t rope_rows = (size_t)items * R;
+    float* cs = st->rope_host;
+    float* sn = cs + rope_rows * half;
+    for (int d = 0; d < half; ++d) {
+        const float expo = (float)(2 * d) / (float)c.head_dim;
+        const float pw = (float)std::pow((double)c.rope_theta, (double)expo);
+        const float inv = 1.0f / pw;
+        for (int b = 0; b < items; ++b) {
+            const int64_t P = 2 * pos0[b];
+            for (int i = 0; i < R; ++i) {
+                volatile float fr = inv * (float)(P + i);
+                cs[((size_t)b * R + i) * half + d] = (float)std::cos((double)fr);
+                sn[((size_t)b * R + i) * half + d] = (float)std::sin((double)fr);
+            }
+        }
+    }
+    for (int i = 0; i < m; ++i) st->failed[slot_of(i)] = 1;  // from here on a failure leaves these slots half-advanced
+    HIP_TRY(hipMemcpyAsync(st->rope_cos, cs, rope_rows * half * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(st->rope_sin, sn, rope_rows * half * 4, hipMemcpyHostToDevice, s));
+    if (slots) {
+        // the device image holds [B] rows then [B] slots, the first m of each
+        HIP_TRY(hipMemcpyAsync(st->tab_dev, row_img, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(st->tab_dev + (size_t)st->B * sizeof(int64_t), slot_img, (size_t)m * sizeof(int32_t),
+                               hipMemcpyHostToDevice, s));
+    }
+    if ((rc = stream_pass(st, dev_codes, m, n, slots, pos0.data(), w, dev_audio, s))) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    if ((rc = save_tap(e, "audio", dev_audio, m, decode_upsampling(c) * n, 1, s))) return rc;
+    if ((rc = read_decode_flag(e, s))) return rc;
+    for (int i = 0; i < m; ++i) {
+        st->failed[slot_of(i)] = 0;
+        st->pos[slot_of(i)] += n;
+    }
     return MIMI_OK;
 }
 
@@ -3748,46 +3891,39 @@ extern "C" int mimi_decode_stream_step(mimi_decode_stream* st, const int32_t* de
     if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
     mimi_engine* e = st->e;
     std::lock_guard<std::mutex> lk(e->mu);
-    if (st->failed) return set_err(MIMI_ERR_STATE, "decode stream: a step failed; mimi_decode_stream_reset first");
+    for (int b = 0; b < st->B; ++b)
+        if (st->failed[b])
+            return set_err(MIMI_ERR_STATE, "decode stream: a step of slot %d failed; mimi_decode_stream_reset(_slot) first", b);
     if (n < 1 || n > st->max_n || !dev_codes || !dev_audio)
         return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream step of %d frames outside [1, %d]", n, st->max_n);
-    const mimi_config& c = e->cfg;
-    const int R = 2 * n, half = c.head_dim / 2;
-    const int64_t P = 2 * st->pos;
-    // RoPE multiplies inv_freq by (float)row: exact only while the row fits float32's 24-bit significand
-    if (P + R > (1LL << 24))
-        return set_err(MIMI_ERR_UNSUPPORTED, "decode stream: row %lld no longer fits a float32 exactly", (long long)(P + R));
-    HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int rc;
-    if ((rc = ensure_dws(e, stream_ws_layout(e, st->B, n, e->taps).bytes))) return rc;  // (state untouched so far)
-    const StreamWs w = stream_ws_layout(e, st->B, n, e->taps);
-    // rows P .. P + R - 1 of the RoPE tables, by ensure_rope's expressions (the previous step synchronised s before it
-    // returned: nothing reads the pinned image any more)
-    float* cs = st->rope_host;
-    float* sn = cs + (size_t)R * half;
-    for (int d = 0; d < half; ++d) {
-        const float expo = (float)(2 * d) / (float)c.head_dim;
-        const float pw = (float)std::pow((double)c.rope_theta, (double)expo);
-        const float inv = 1.0f / pw;
-        for (int i = 0; i < R; ++i) {
-            volatile float fr = inv * (float)(P + i);
-            cs[(size_t)i * half + d] = (float)std::cos((double)fr);
-            sn[(size_t)i * half + d] = (float)std::sin((double)fr);
-        }
+    // all slots at one position: the lock-step pass; otherwise a slot step over 0 .. B - 1
+    if (std::all_of(st->pos.begin(), st->pos.end(), [&](int64_t p) { return p == st->pos[0]; }))
+        return stream_step_locked(st, nullptr, st->B, dev_codes, n, dev_audio, s);
+    std::vector<int32_t> all(st->B);
+    for (int b = 0; b < st->B; ++b) all[b] = b;
+    return stream_step_locked(st, all.data(), st->B, dev_codes, n, dev_audio, s);
+}
+
+extern "C" int mimi_decode_stream_step_slots(mimi_decode_stream* st, const int32_t* slots, int32_t m,
+                                             const int32_t* dev_codes, int32_t n, float* dev_audio, void* stream) {
+    if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
+    mimi_engine* e = st->e;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!slots || !dev_codes || !dev_audio) return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream step: null argument");
+    if (m < 1 || m > st->B)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream step over %d slots outside [1, %d]", m, st->B);
+    if (n < 1 || n > st->max_n)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream step of %d frames outside [1, %d]", n, st->max_n);
+    // every table index is checked here: the kernels index the rings and carries by slots[i] and read m entries
+    std::vector<char> seen(st->B, 0);
+    for (int i = 0; i < m; ++i) {
+        if (slots[i] < 0 || slots[i] >= st->B)
+            return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream: slot %d outside [0, %d)", slots[i], st->B);
+        if (seen[slots[i]]) return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream: slot %d listed twice", slots[i]);
+        seen[slots[i]] = 1;
     }
-    st->failed = true;  // from here on a failure leaves the state half-advanced
-    HIP_TRY(hipMemcpyAsync(st->rope_cos, cs, (size_t)R * half * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(st->rope_sin, sn, (size_t)R * half * 4, hipMemcpyHostToDevice, s));
-    if ((rc = stream_pass(st, dev_codes, n, w, dev_audio, s))) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    if ((rc = save_tap(e, "audio", dev_audio, st->B, decode_upsampling(c) * n, 1, s))) return rc;
-    if ((rc = read_decode_flag(e, s))) return rc;
-    st->failed = false;
-    st->pos += n;
-    return MIMI_OK;
+    return stream_step_locked(st, slots, m, dev_codes, n, dev_audio, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" void mimi_destroy(mimi_engine* e) {

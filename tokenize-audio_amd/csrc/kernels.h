@@ -502,13 +502,27 @@ hipError_t launch_attention_stream(const float* qkv, const float* kring, const f
 // the step's k / v rows into their ring slots (after the attention that may still read the rows they replace)
 hipError_t launch_attention_stream_append(const float* qkv, float* kring, float* vring, int batch, int R, int H, int D,
                                           int cap, long long pos0, hipStream_t s);
+// Slot forms (a step over a subset of a stream's slots, each at its own position): item b of the step, b < batch, is
+// slot slot_tab[b] of the rings and its first row is absolute row pos_tab[b] (device tables of `batch` entries; the
+// caller has checked every slot against the rings' item count and every position >= 0).  The step's own rows and
+// `out` stay indexed by b.  Same body, same orders: a row's bits are those of the forms above at pos0 = pos_tab[b].
+hipError_t launch_attention_stream_slots(const float* qkv, const float* kring, const float* vring, float* out,
+                                         int batch, int R, int H, int D, int window, int cap, const long long* pos_tab,
+                                         const int* slot_tab, float scale, hipStream_t s);
+hipError_t launch_attention_stream_append_slots(const float* qkv, float* kring, float* vring, int batch, int R, int H,
+                                                int D, int cap, const long long* pos_tab, const int* slot_tab,
+                                                hipStream_t s);
 // stream_carry_kernel: n strided copies in one launch; copy d moves `count` floats (a multiple of 4) per item from
 // src + b * src_bstride to dst + b * dst_bstride.  Source and destination never overlap.
+// stream_carry_slots_kernel: the same with the stream's side of a copy (`state`: CARRY_STATE_SRC for carry-in,
+// CARRY_STATE_DST for carry-out, 0 for neither) indexed by slot_tab[b] instead of b.
+enum { CARRY_STATE_SRC = 1, CARRY_STATE_DST = 2 };
 struct CarryCopy {
     const float* src;
     float* dst;
     long long src_bstride, dst_bstride;
     int count;
+    int state;  // slot form only
 };
 constexpr int CARRY_MAX = 16;
 struct CarryTable {
@@ -516,6 +530,7 @@ struct CarryTable {
     int n;
 };
 hipError_t launch_stream_carry(const CarryTable& t, int batch, hipStream_t s);
+hipError_t launch_stream_carry_slots(const CarryTable& t, int batch, const int* slot_tab, hipStream_t s);
 
 // polyphase resampler (resample.hip): clips packed at in_off / out_off (device int64 arrays), one launch
 hipError_t launch_resample_poly(const float* x, const long long* in_off, const long long* in_len, int nclips,

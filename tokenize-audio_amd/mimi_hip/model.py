@@ -13,7 +13,8 @@ Mirrors the model-level API every reference wrapper calls:
   (``TF/modeling_mimi.py:1408-1458``; ``librispeech-mimi/utils.py:72-81`` does ``.audio_values[0]``).
 * ``model.decode_stream(batch, num_quantizers, max_step_frames)`` -> ``DecodeStream``: ``.step(codes[B, K, n])`` returns
   the ``1920 n`` samples of the next ``n`` frames from a KV cache and per-stage carries (the same bits under any split
-  of a sequence into steps).
+  of a sequence into steps); ``.step(codes[m, K, n], slots=[...])`` advances only the listed slots, each at its own
+  position, and ``.reset(slot)`` frees one.
 * ``.to(device)``, ``.eval()``, ``get_encoded_length``, ``from_pretrained(local_dir | "kyutai/mimi")``.
 
 The arithmetic runs in ``libmimi_hip.so`` (HIP kernels for gfx950); torch only supplies device memory and
@@ -27,7 +28,7 @@ import os
 import threading
 import weakref
 from dataclasses import dataclass
-from typing import Dict, Optional, Union
+from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -132,11 +133,15 @@ class EncodeTicket:
 
 
 class DecodeStream:
-    """Streaming decode (``MimiHipModel.decode_stream``): ``batch`` items advancing in lock-step, ``n`` new frames of
-    codes in and their ``1920 n`` samples out per ``step``, on a KV cache and per-stage carries that the stream owns
-    in device memory (``state_bytes``, constant).  The samples are bitwise the same under any split of a sequence into
-    steps, and within the activation tolerance of ``decode`` of the whole sequence.  A context manager; ``close()``
-    frees the state (closing the model closes its streams)."""
+    """Streaming decode (``MimiHipModel.decode_stream``): ``batch`` items, ``n`` new frames of codes in and their
+    ``1920 n`` samples out per ``step``, on a KV cache and per-stage carries that the stream owns in device memory
+    (``state_bytes``, constant).  The samples are bitwise the same under any split of a sequence into steps, and within
+    the activation tolerance of ``decode`` of the whole sequence.
+
+    Every item is a SLOT with its own position: ``step(codes)`` advances all of them, ``step(codes, slots=[...])`` only
+    the listed ones (sessions that start and end at different times: a new session takes a free slot, ``reset(slot)``
+    frees it).  A slot's samples are bitwise those of a ``batch=1`` stream fed the same sequence, whatever its
+    neighbours do.  A context manager; ``close()`` frees the state (closing the model closes its streams)."""
 
     def __init__(self, model: "MimiHipModel", batch: int, num_quantizers: int, max_step_frames: int):
         self._model, self.batch, self.num_quantizers = model, int(batch), int(num_quantizers)
@@ -159,45 +164,75 @@ class DecodeStream:
 
     @property
     def position(self) -> int:
-        """Frames decoded so far."""
+        """Frames decoded so far (the furthest slot's)."""
         return int(self._model._lib.mimi_decode_stream_position(self._handle()))
+
+    @property
+    def positions(self) -> List[int]:
+        """Frames decoded by each slot since its last reset."""
+        h = self._handle()
+        return [int(self._model._lib.mimi_decode_stream_slot_position(h, b)) for b in range(self.batch)]
 
     @property
     def state_bytes(self) -> int:
         return int(self._model._lib.mimi_decode_stream_state_bytes(self._handle()))
 
-    def step(self, codes: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def step(self, codes: torch.Tensor, out: Optional[torch.Tensor] = None,
+             slots: Optional[Sequence[int]] = None) -> torch.Tensor:
         """The next ``n`` frames: int64 / int32 codes ``[B, K, n]`` on any device -> float32 ``[B, 1, 1920 n]`` on the
-        model's device (``out`` if given).  ``ValueError`` for ``n`` outside ``[1, max_step_frames]`` (the state is
-        untouched) and for a code outside ``[0, codebook_size)`` (the stream then refuses until ``reset``)."""
+        model's device (``out`` if given).  With ``slots`` (``m`` distinct ints in ``[0, batch)``, any order) only those
+        slots advance: ``codes`` is ``[m, K, n]``, item ``i`` the next frames of slot ``slots[i]``, the result
+        ``[m, 1, 1920 n]``.  ``ValueError`` for ``n`` outside ``[1, max_step_frames]`` and a bad slot list (the state is
+        untouched) and for a code outside ``[0, codebook_size)`` (the slots of that call then refuse until ``reset``)."""
         m = self._model
         h = self._handle()
         if not torch.is_tensor(codes):
             codes = torch.as_tensor(np.asarray(codes))
-        if codes.dim() != 3 or codes.shape[0] != self.batch or codes.shape[1] != self.num_quantizers:
-            raise ValueError(f"codes must be [{self.batch}, {self.num_quantizers}, n], got {tuple(codes.shape)}")
+        if slots is not None:
+            slots = [int(x) for x in slots]
+            if not 1 <= len(slots) <= self.batch:
+                raise ValueError(f"a step lists 1 .. {self.batch} slots, got {len(slots)}")
+            if min(slots) < 0 or max(slots) >= self.batch or len(set(slots)) != len(slots):
+                raise ValueError(f"slots must be distinct and in [0, {self.batch}), got {slots}")
+        items = self.batch if slots is None else len(slots)
+        if codes.dim() != 3 or codes.shape[0] != items or codes.shape[1] != self.num_quantizers:
+            raise ValueError(f"codes must be [{items}, {self.num_quantizers}, n], got {tuple(codes.shape)}")
         n = int(codes.shape[2])
         if n < 1 or n > self.max_step_frames:
             raise ValueError(f"a step takes 1 .. {self.max_step_frames} frames, got {n}")
         L = m.get_decoded_length(n)
         if out is None:
-            out = torch.empty((self.batch, 1, L), dtype=torch.float32, device=m.device)
-        elif (tuple(out.shape) != (self.batch, 1, L) or out.dtype != torch.float32 or out.device != m.device
+            out = torch.empty((items, 1, L), dtype=torch.float32, device=m.device)
+        elif (tuple(out.shape) != (items, 1, L) or out.dtype != torch.float32 or out.device != m.device
               or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous float32 [{self.batch}, 1, {L}] tensor on {m.device}")
+            raise ValueError(f"out must be a contiguous float32 [{items}, 1, {L}] tensor on {m.device}")
         c = codes.to(device=m.device, dtype=torch.int32).contiguous()
         try:
-            _lib.check(m._lib.mimi_decode_stream_step(h, ctypes.c_void_p(c.data_ptr()), n,
-                                                      ctypes.c_void_p(out.data_ptr()), m._stream()))
+            if slots is None:
+                _lib.check(m._lib.mimi_decode_stream_step(h, ctypes.c_void_p(c.data_ptr()), n,
+                                                          ctypes.c_void_p(out.data_ptr()), m._stream()))
+            else:
+                tab = (ctypes.c_int32 * items)(*slots)
+                _lib.check(m._lib.mimi_decode_stream_step_slots(h, tab, items, ctypes.c_void_p(c.data_ptr()), n,
+                                                                ctypes.c_void_p(out.data_ptr()), m._stream()))
         except _lib.MimiHipError as err:
             if err.status == 1:
                 raise ValueError(str(err)) from None
             raise
         return out
 
-    def reset(self):
-        """Back to position 0 with zero state: what follows equals a fresh stream."""
-        _lib.check(self._model._lib.mimi_decode_stream_reset(self._handle()))
+    def reset(self, slot: Optional[int] = None):
+        """Back to position 0 with zero state: what follows equals a fresh stream.  With ``slot`` only that slot, its
+        neighbours untouched (``ValueError`` for a slot outside ``[0, batch)``)."""
+        if slot is None:
+            _lib.check(self._model._lib.mimi_decode_stream_reset(self._handle()))
+            return
+        try:
+            _lib.check(self._model._lib.mimi_decode_stream_reset_slot(self._handle(), int(slot)))
+        except _lib.MimiHipError as err:
+            if err.status == 1:
+                raise ValueError(str(err)) from None
+            raise
 
     def close(self):
         h, self._h = self._h, None
@@ -517,9 +552,10 @@ class MimiHipModel:
 
     def decode_stream(self, batch: int = 1, num_quantizers: Optional[int] = None,
                       max_step_frames: int = 16) -> DecodeStream:
-        """A streaming decode of ``batch`` items in lock-step (``mimi_decode_stream_*``): ``.step(codes[B, K, n])``
-        returns the ``1920 n`` samples of the next ``n <= max_step_frames`` frames.  Several streams may be open on
-        one model and interleave with ``decode`` / ``decode_ragged`` / ``encode``."""
+        """A streaming decode of ``batch`` items (``mimi_decode_stream_*``): ``.step(codes[B, K, n])`` returns the
+        ``1920 n`` samples of the next ``n <= max_step_frames`` frames of all of them, ``.step(codes[m, K, n],
+        slots=[...])`` of the listed slots only, each slot at its own position.  Several streams may be open on one
+        model and interleave with ``decode`` / ``decode_ragged`` / ``encode``."""
         self._require_decode()
         K = self.config.num_quantizers if num_quantizers is None else int(num_quantizers)
         if K > self.config.num_quantizers or K < 1:
