@@ -32,8 +32,9 @@ the error in units of one fp32 rounding of the element's own condition sum.  Two
   (tests/test_decode_stage_ref.py injects the faults and asserts the margins).
 
 All tensors are channel-first ``[B, C, T]`` as in ``decode_ref`` (an engine tap ``[B][T][C]`` is transposed by the
-caller).  The decoder transformer is checked as a whole with the project metric against ``mimi_ref.transformer`` in
-float64 (no condition sum: LayerNorm, softmax and GELU are not sums of products).
+caller).  Here the decoder transformer is checked as a whole with the project metric against ``mimi_ref.transformer``
+in float64; its 8 x 5 stages, with condition sums derived for LayerNorm, softmax and GELU, are in
+tests/decode_xfmr_ref.py (on the table of tests/encode_stage_ref.py).
 """
 from __future__ import annotations
 

@@ -176,14 +176,14 @@ def speech_batch(B, L, seed):
 
 
 # ---- measures ---------------------------------------------------------------------------------------------------------
-def attention_regime(qkv_tap) -> dict:
-    """Of a qkv tap [B, T, 3 H D], over every (item, head, row), in float64: the largest score range of a row (over
+def attention_regime(qkv_tap, window=None) -> dict:
+    """Of a qkv tap [B, T, 3 H D] at sliding window ``window`` (None: the reference's), over every (item, head, row), in float64: the largest score range of a row (over
     its unmasked keys), the median and the smallest largest-softmax-weight, the largest |score|, and how often the
     running maximum of a row changes in a chunk after its first (the kernels walk the keys in 32-key chunks from key 0
     of the item; every such change is a corr = exp(m - mnew) < 1)."""
     q, k, v = esr.heads(torch.as_tensor(qkv_tap).double())
     T = q.shape[2]
-    mask = esr.att_mask(T)
+    mask = esr.att_mask(T, window)
     s = (q @ k.transpose(-1, -2)) / math.sqrt(q.shape[-1])
     lo = s.masked_fill(~mask, float("inf")).amin(-1)
     hi = s.masked_fill(~mask, float("-inf")).amax(-1)

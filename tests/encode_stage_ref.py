@@ -84,6 +84,7 @@ prologues and the residual blocks are not emulated: q_ref alone.
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from dataclasses import dataclass
 from typing import Callable, Dict, Optional, Tuple
@@ -405,10 +406,15 @@ def heads(x):
     return t[0], t[1], t[2]
 
 
-def att_value(xs, sd, dtype):
+def _window_cfg(window=None):
+    return CFG if window is None else dataclasses.replace(CFG, sliding_window=int(window))
+
+
+def att_value(xs, sd, dtype, window=None):
+    """``window``: the sliding window (None: the module's ``CFG``, what the encode stages use)."""
     q, k, v = heads(xs[0].to(dtype))
     B, H, T, D = q.shape
-    return mimi_ref.attention(q, k, v, CFG).transpose(1, 2).contiguous().reshape(B, T, H * D)
+    return mimi_ref.attention(q, k, v, _window_cfg(window)).transpose(1, 2).contiguous().reshape(B, T, H * D)
 
 
 def att_mask(T, window=None):
@@ -417,11 +423,11 @@ def att_mask(T, window=None):
     return (j <= i) & (j > i - window)
 
 
-def att_cond(xs, sd, ar):
+def att_cond(xs, sd, ar, window=None):
     q, k, v = heads(xs[0].double())
     B, H, T, D = q.shape
     scale = 1.0 / math.sqrt(D)
-    mask = att_mask(T)
+    mask = att_mask(T, window)
     aq, ak, av = q.abs(), k.abs(), v.abs()
     pfloor = 0.0
     if ar.h16:  # the kernels' own plane scales: the maximum at [2^13, 2^14) -> floors 2^-17 of each head's maximum
@@ -434,6 +440,28 @@ def att_cond(xs, sd, ar):
     pf = p.clamp(min=pfloor).masked_fill(~mask, 0.0)
     m = (pf * (1.0 + S + sbar)) @ av
     return m.transpose(1, 2).contiguous().reshape(B, T, H * D)
+
+
+def att_n(window=None) -> int:
+    """The attention stage's hard bound: the score's 64 + 2, two sums of at most ``window`` terms, 6 operations."""
+    return (CFG.head_dim + 2) + 2 * _window_cfg(window).sliding_window + 6
+
+
+def att_stage(window=None):
+    """(value, cond, n) of the attention stage at a sliding window of its own (None: ``CFG``'s)."""
+    if window is None:
+        return att_value, att_cond, lambda sd: att_n()
+    return (lambda xs, sd, dtype: att_value(xs, sd, dtype, window), lambda xs, sd, ar: att_cond(xs, sd, ar, window),
+            lambda sd: att_n(window))
+
+
+DECODER_PREFIX, ENCODER_PREFIX = "decoder_transformer.", "encoder_transformer."
+
+
+def decoder_view(sd):
+    """The decoder transformer's weights under the encoder transformer's names, which every transformer stage here
+    reads: the renaming view of ``decode_ref.decoder_transformer`` (the tensors are shared, not copied)."""
+    return {ENCODER_PREFIX + k[len(DECODER_PREFIX):]: v for k, v in sd.items() if k.startswith(DECODER_PREFIX)}
 
 
 def linear_res_stage(l, wkey, lskey, slot):
@@ -536,6 +564,28 @@ class Stage:
         return ar.c_term * self.gemms + (ar.c_out if self.planes_out else 0)
 
 
+XFMR_STAGES = ("qkv", "att", "oproj", "ff", "xfmr")   # the five stages of a transformer layer, in order
+
+
+def transformer_stages(first: str, window=None) -> Dict[str, Stage]:
+    """The 5 stages of each of the 8 layers; layer 0 reads the tap ``first``, attention has the sliding window
+    ``window`` (None: ``CFG``'s).  The weights are read under the encoder transformer's names (``decoder_view``)."""
+    st: Dict[str, Stage] = {}
+    av, ac, an = att_stage(window)
+    for l in range(CFG.num_hidden_layers):
+        x = first if l == 0 else f"xfmr{l - 1}"
+        C = CFG.hidden_size
+        st[f"qkv{l}"] = Stage(f"qkv{l}", (x,), qkv_value(l), qkv_cond(l), lambda sd, C=C: (C + 4) + (C + 2) + N_ROPE)
+        st[f"att{l}"] = Stage(f"att{l}", (f"qkv{l}",), av, ac, an, planes_out=True)
+        v, c, n, e = linear_res_stage(l, "self_attn.o_proj.weight", "self_attn_layer_scale.scale", f"xf{l}.att")
+        st[f"oproj{l}"] = Stage(f"oproj{l}", (f"att{l}", x), v, c, n, emul=e)
+        st[f"ff{l}"] = Stage(f"ff{l}", (f"oproj{l}",), ff_value(l), ff_cond(l),
+                             lambda sd, C=C: (C + 4) + (C + 2) + N_GELU, planes_out=True)
+        v, c, n, e = linear_res_stage(l, "mlp.fc2.weight", "mlp_layer_scale.scale", f"xf{l}.ff")
+        st[f"xfmr{l}"] = Stage(f"xfmr{l}", (f"ff{l}", f"oproj{l}"), v, c, n, emul=e)
+    return st
+
+
 def _stages() -> Dict[str, Stage]:
     st: Dict[str, Stage] = {}
     st["conv0"] = Stage("conv0", ("audio",), conv0_value, conv0_cond, lambda sd: CFG.kernel_size + 2, gemms=0)
@@ -553,18 +603,7 @@ def _stages() -> Dict[str, Stage]:
         st[name] = Stage(name, (f"res{s}_elu",), v, c, n, planes_out=last, emul=e)
     v, c, n, e = conv_stage(PF, "x_last")
     st["encoder"] = Stage("encoder", (f"down{len(RATIOS) - 1}_elu",), v, c, n, emul=e)
-    for l in range(CFG.num_hidden_layers):
-        x = "encoder" if l == 0 else f"xfmr{l - 1}"
-        C = CFG.hidden_size
-        st[f"qkv{l}"] = Stage(f"qkv{l}", (x,), qkv_value(l), qkv_cond(l), lambda sd, C=C: (C + 4) + (C + 2) + N_ROPE)
-        st[f"att{l}"] = Stage(f"att{l}", (f"qkv{l}",), att_value, att_cond,
-                              lambda sd: (CFG.head_dim + 2) + 2 * CFG.sliding_window + 6, planes_out=True)
-        v, c, n, e = linear_res_stage(l, "self_attn.o_proj.weight", "self_attn_layer_scale.scale", f"xf{l}.att")
-        st[f"oproj{l}"] = Stage(f"oproj{l}", (f"att{l}", x), v, c, n, emul=e)
-        st[f"ff{l}"] = Stage(f"ff{l}", (f"oproj{l}",), ff_value(l), ff_cond(l),
-                             lambda sd, C=C: (C + 4) + (C + 2) + N_GELU, planes_out=True)
-        v, c, n, e = linear_res_stage(l, "mlp.fc2.weight", "mlp_layer_scale.scale", f"xf{l}.ff")
-        st[f"xfmr{l}"] = Stage(f"xfmr{l}", (f"ff{l}", f"oproj{l}"), v, c, n, emul=e)
+    st.update(transformer_stages("encoder"))
     last = f"xfmr{CFG.num_hidden_layers - 1}"
     v, c, n, e = conv_stage("downsample.conv.", "ds.in", stride=2, bias=False)
     st["ds_gemm"] = Stage("ds_gemm", (last,), v, c, n, emul=e, interior=True)
@@ -589,10 +628,10 @@ def chain_f32(audio, sd, names=None) -> Dict[str, torch.Tensor]:
     return taps
 
 
-def measure(name: str, xs, sd, ar: Arith, got=None, f32=None) -> dict:
+def measure(name: str, xs, sd, ar: Arith, got=None, f32=None, stages=None) -> dict:
     """One stage on inputs xs: n, c, q_ref (torch-CPU fp32, or the given ``f32`` evaluation), q_emul (f16x3 mode, the
-    emulated stages), and q_engine / worst when ``got`` is given."""
-    st = STAGES[name]
+    emulated stages), and q_engine / worst when ``got`` is given.  ``stages``: another table than ``STAGES``."""
+    st = (STAGES if stages is None else stages)[name]
     xs = [torch.as_tensor(x) for x in xs]
     ref64, mag64 = st.ref(xs, sd, ar)
     rows = slice(None)

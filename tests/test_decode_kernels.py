@@ -322,6 +322,25 @@ def test_taps_profiling_and_stream_do_not_move_decode(dec, base):
         y = dec.decode(codes).audio_values
     side.synchronize()
     assert torch.equal(y, want)
+    # a stream step and a slot step (the transformer's 40 per-layer taps are saved between their launches): taps on
+    # moves no bit of the samples, and the per-layer taps are there
+    sc = rand_codes(8, 2, 8, 5)
+    outs = []
+    for taps in (False, True):
+        dec.set_taps(taps)
+        try:
+            with dec.decode_stream(batch=2, num_quantizers=8, max_step_frames=3) as st:
+                ys = [st.step(sc[:, :, :2]).cpu()]
+                if taps:
+                    assert dec.get_tap("qkv3").shape == (2, 4, 1536) and dec.get_tap("ff7").shape == (2, 4, 2048)
+                ys.append(st.step(sc[1:, :, 2:5], slots=[1]).cpu())
+                if taps:
+                    assert dec.get_tap("att0").shape == (1, 6, 512) and dec.get_tap("xfmr7").shape == (1, 6, 512)
+                ys.append(st.step(sc[:1, :, 2:3], slots=[0]).cpu())
+        finally:
+            dec.set_taps(False)
+        outs.append(ys)
+    assert len(outs[0]) == len(outs[1]) == 3 and all(torch.equal(a, b) for a, b in zip(*outs))
 
 
 def test_workspace_regrow_does_not_move_decode(full_np, base):

@@ -1276,6 +1276,16 @@ static int save_tap_planes(mimi_engine* e, const char* name, const void* planes,
     return MIMI_OK;
 }
 
+// layer l's tap of a decoder transformer stage, under the encode pass's name ("qkv3"); nothing is formatted when taps
+// are off
+static int save_tap_layer(mimi_engine* e, const char* stage, size_t l, const float* src, int64_t b, int64_t t,
+                          int64_t ch, hipStream_t s) {
+    if (!e->taps) return MIMI_OK;
+    char nm[48];
+    snprintf(nm, sizeof nm, "%s%d", stage, (int)l);
+    return save_tap(e, nm, src, b, t, ch, s);
+}
+
 // A operand of a GEMM read from plane-format activations (plane stride = the activation's element count)
 static void planes_in(GemmArgs& a, const void* planes, long long n) {
     a.Ap = planes;
@@ -3089,6 +3099,11 @@ static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, c
     const int64_t T = L.len(1), rows = L.rows(1);
     const std::string sp = stage_prefix;
     const char* kname = "?";
+    int rc;
+    // the per-layer taps, under the encode pass's names (a ragged pass's are packed, like its other taps)
+    auto tap = [&](const char* stage, size_t l, const float* src, int C) {
+        return L.ragged ? save_tap_layer(e, stage, l, src, 1, rows, C, s) : save_tap_layer(e, stage, l, src, B, T, C, s);
+    };
     double att_flops = 0;
     for (int64_t i = 0; i < T; ++i) att_flops += 4.0 * Dh * std::min<int64_t>(i + 1, c.sliding_window);
     att_flops *= (double)H * B;
@@ -3114,6 +3129,7 @@ static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, c
         aq.a_boff = aq.c_boff = L.toff(1);
         LAUNCH_TRY(launch_gemm(ROLE_QKV, aq, s, &kname, PREC_F32), "qkv");
         rec.mark(sp + "qkv", fl(aq), by(aq, false), kname);
+        if ((rc = tap("qkv", l, qkv, 3 * H * Dh))) return rc;
         const char* akn = T <= 256 ? "mimi::attention_t256_kernel" : "mimi::attention_kernel";
         if (L.ragged) {
             // each item the kernel it would run alone: one launch per regime present (and one record each), each
@@ -3139,11 +3155,13 @@ static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, c
                        "attention");
             rec.mark(sp + "attention", att_flops, (double)rows * 4 * Hd * 4, akn);
         }
+        if ((rc = tap("att", l, att, H * Dh))) return rc;
         GemmArgs ao = linear_args(att, rows, H * Dh, x.wo, Hd, t0);
         ao.R = t0;
         ao.scale = x.ls1;
         LAUNCH_TRY(launch_gemm(ROLE_OPROJ, ao, s, &kname, PREC_F32), "o_proj");
         rec.mark(sp + "o_proj", fl(ao), by(ao, true), kname);
+        if ((rc = tap("oproj", l, t0, Hd))) return rc;
         LAUNCH_TRY(launch_layernorm(t0, x.ln2_w, x.ln2_b, t1, rows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f, nullptr,
                                     nullptr, 0, e->ln_rpw),
                    "ln2");
@@ -3151,11 +3169,13 @@ static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, c
         GemmArgs a1 = linear_args(t1, rows, Hd, x.w1, c.intermediate_size, ff);
         LAUNCH_TRY(launch_gemm(ROLE_FC1, a1, s, &kname, PREC_F32), "fc1");
         rec.mark(sp + "fc1", fl(a1), by(a1, false), kname);
+        if ((rc = tap("ff", l, ff, c.intermediate_size))) return rc;
         GemmArgs a2 = linear_args(ff, rows, c.intermediate_size, x.w2, Hd, t0);
         a2.R = t0;
         a2.scale = x.ls2;
         LAUNCH_TRY(launch_gemm(ROLE_FC2, a2, s, &kname, PREC_F32), "fc2");
         rec.mark(sp + "fc2", fl(a2), by(a2, true), kname);
+        if ((rc = tap("xfmr", l, t0, Hd))) return rc;
     }
     return MIMI_OK;
 }
@@ -3204,10 +3224,8 @@ static int decode_pass(mimi_engine* e, const int32_t* dev_codes, const DecLayout
     if ((rc = tap("upsample", t0, 1, Hd))) return rc;
 
     // ---- decoder transformer ----
-    if ((rc = run_transformer_f32(e, e->dxf, L, t0, t1, qkv, att, ff, s, rec, "dec_"))) return rc;
+    if ((rc = run_transformer_f32(e, e->dxf, L, t0, t1, qkv, att, ff, s, rec, "dec_"))) return rc;  // (taps inside)
     char nm[64];
-    snprintf(nm, sizeof nm, "xfmr%d", c.num_hidden_layers - 1);
-    if ((rc = tap(nm, t0, 1, Hd))) return rc;
 
     // ---- SEANet decoder ----
     int C = c.num_filters << c.num_ratios;
@@ -3702,6 +3720,7 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
             aq.rope_cols = 2 * H * Dh;
             LAUNCH_TRY(launch_gemm(ROLE_QKV, aq, s, &kname, PREC_F32), "qkv");
             rec.mark("dec_qkv", fl(aq), by(aq, false), kname);
+            if ((rc = save_tap_layer(e, "qkv", l, w.qkv, B, R, 3 * H * Dh, s))) return rc;
             float* kr = st->kring + l * st->ring_layer;
             float* vr = st->vring + l * st->ring_layer;
             const float qscale = 1.0f / std::sqrt((float)Dh);
@@ -3712,6 +3731,7 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
                        "attention (stream)");
             rec.mark("dec_attention", att_flops, (double)frows * 4 * Hd * 4,
                      slots ? "mimi::attention_stream_slots_kernel" : "mimi::attention_stream_kernel");
+            if ((rc = save_tap_layer(e, "att", l, w.att, B, R, H * Dh, s))) return rc;
             LAUNCH_TRY(slots ? launch_attention_stream_append_slots(w.qkv, kr, vr, B, R, H, Dh, st->cap, pos_tab,
                                                                     slot_tab, s)
                              : launch_attention_stream_append(w.qkv, kr, vr, B, R, H, Dh, st->cap, P, s),
@@ -3723,6 +3743,7 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
             ao.scale = x.ls1;
             LAUNCH_TRY(launch_gemm(ROLE_OPROJ, ao, s, &kname, PREC_F32), "o_proj");
             rec.mark("dec_o_proj", fl(ao), by(ao, true), kname);
+            if ((rc = save_tap_layer(e, "oproj", l, w.t0, B, R, Hd, s))) return rc;
             LAUNCH_TRY(launch_layernorm(w.t0, x.ln2_w, x.ln2_b, w.t1, frows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f,
                                         nullptr, nullptr, 0, e->ln_rpw),
                        "ln2");
@@ -3730,15 +3751,15 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
             GemmArgs a1 = linear_args(w.t1, frows, Hd, x.w1, c.intermediate_size, w.ff);
             LAUNCH_TRY(launch_gemm(ROLE_FC1, a1, s, &kname, PREC_F32), "fc1");
             rec.mark("dec_fc1", fl(a1), by(a1, false), kname);
+            if ((rc = save_tap_layer(e, "ff", l, w.ff, B, R, c.intermediate_size, s))) return rc;
             GemmArgs a2 = linear_args(w.ff, frows, c.intermediate_size, x.w2, Hd, w.t0);
             a2.R = w.t0;
             a2.scale = x.ls2;
             LAUNCH_TRY(launch_gemm(ROLE_FC2, a2, s, &kname, PREC_F32), "fc2");
             rec.mark("dec_fc2", fl(a2), by(a2, true), kname);
+            if ((rc = save_tap_layer(e, "xfmr", l, w.t0, B, R, Hd, s))) return rc;
         }
     }
-    snprintf(nm, sizeof nm, "xfmr%d", c.num_hidden_layers - 1);
-    if ((rc = save_tap(e, nm, w.t0, B, R, Hd, s))) return rc;
     {  // the transformer's flat rows behind decoder.layers.0's carry
         CarryTable mv{};
         mv.c[0] = {w.t0, w.xin + (int64_t)H0 * Hd, (int64_t)R * Hd, (int64_t)(H0 + R) * Hd, R * Hd};
