@@ -15,8 +15,9 @@ namespace mimi {
 // K order: tap j, then j + 4, per 32-channel half; products lo.hi, hi.lo, hi.hi).
 //
 // One workgroup of 12 waves per CU (3 per SIMD, <= 168 VGPRs each), two roles meeting at one barrier per round:
-//   4 block waves (one per SIMD) -- each walks its own contiguous range of 32-step blocks, one per round: the
-//      block (conv0 -> slab -> GEMM1 -> h -> GEMM2 -> y) with y, zeroed past the item's end, written to section
+//   4 block waves (one per SIMD) -- each walks its own contiguous range of 32-step blocks, one per round (rounds
+//      and buffers here as without S0F_DEFER; with it, below): the block (conv0 -> slab -> GEMM1 -> h -> GEMM2 ->
+//      y) with y, zeroed past the item's end, written to section
 //      w of y buffer n % 2 (rows 4..35; rows 0..3 = the 4 causal halo steps: the same section's rows 32..35 of
 //      buffer (n-1) % 2, zeros at t = 0) + a descriptor (item, first 6 kHz step, rows to store)
 //   8 conv waves -- the down conv of round n-1's 4 sections (32 output steps, 8 per section) for 16 output
@@ -29,11 +30,28 @@ namespace mimi {
 // y buffer [plane][section 4][36 rows][72 halves] + 32 B between sections, 16-B chunk c of row r at c ^ 2 (r & 1):
 // the block waves' row writes (ds_write_b64) and the conv waves' fragment reads (ds_read_b128) are conflict-free.
 // LDS: block weights 36 KB + biases + 4 x 9.75 KB slabs + 2 x 40.75 KB y buffers = 157.3 KB.
+//
+// S0F_DEFER (default): the y epilogue of a block runs one round late.  After GEMM2 the block wave keeps only z = x0 +
+// (acc2 u2 + b1) (2 x 16 registers) with the block's item, first step, length and rows to store; during GEMM1 of the
+// next round -- a 36-MFMA accumulator chain in which the wave had nothing else to issue -- it runs the kept block's
+// ELU, plane split, zeroing and LDS stores, one channel pair behind each of the first 32 MFMAs.  So in round n a block
+// wave writes y, halo (S0F_HELP: the odd helper conv wave) and descriptor of block n - 1 into buffer (n - 1) % 2, the
+// conv waves read block n - 2 from buffer n % 2, and both roles run R + 2 rounds from the one shared R: every wave
+// passes the same barriers.  A wave past its last block retires its kept epilogue alone.  The arithmetic and its order
+// are the undeferred form's, bit for bit.  Measured: round 10.4k -> 9.2k cycles (GEMM2 + y 3.5k ->
+// GEMM2 + z 0.8k, GEMM1 + h 3.4k -> 4.3k with the epilogue in its gaps), stage 0 1.24 -> 1.18 ms; the conv waves
+// (7.0-8.2k) are now co-critical with the block chain (8.3k).  An LDS-only round barrier and the helper's audio split
+// in front of the x1 stores were measured equal and are not here.
 // ------------------------------------------------------------------------------------------------
 #ifndef S0F_HELP
 #define S0F_HELP 1  // the conv waves (idle ~2.9k of the 10.7k-cycle round) split the next round's audio window into
 #endif              // planes and copy each section's y halo, off the block waves' chain (0: the block waves do both;
                     // same bits, stage 0 1.29 / 1.29 / 1.30 -> 1.28 / 1.27 / 1.29 ms alternated, gpurun_out/r6o/ab.log)
+#ifndef S0F_DEFER
+#define S0F_DEFER 1  // a block wave keeps z = x0 + (acc2 u2 + b1) of its round-n block in registers and runs that block's
+#endif               // y epilogue (ELU, plane split, LDS stores) in the MFMA gaps of round n + 1's GEMM1; the conv waves
+                     // follow one round later and every wave runs one more round (0: the epilogue after GEMM2, the
+                     // parent's order; same bits)
 #ifndef S0F_DIAG
 #define S0F_DIAG 0  // tuning diagnostics (results are garbage): 1 = conv waves skip their MFMAs, 2 = block waves skip
 #endif              // their blocks, 3 = block waves without the explicit LDS drains (s_waitcnt lgkmcnt(0))
@@ -44,6 +62,7 @@ namespace mimi {
 #endif
 namespace s0f {
 constexpr int NA = 4, NC = 8, NW = NA + NC;  // block waves, conv waves
+constexpr int DS = S0F_DEFER ? 1 : 0;        // rounds between a block's GEMMs and its y in LDS (both roles: R + 1 + DS rounds)
 constexpr int YLD = 72, YSR = 36, YSS = YSR * YLD + 16, YPS = 4 * YSS, YBS = 2 * YPS;  // halves
 constexpr int OFF_SLAB = r0h::NFRAG * 1024 + r0h::BIAS * 4;
 constexpr int OFF_Y = OFF_SLAB + NA * r0h::WAVE_BYTES;
@@ -74,7 +93,7 @@ static_assert(NC * 16 == 128, "conv waves x 16 channels = down conv 0's output c
 #endif
 __global__ __launch_bounds__(768) void stage0_fused_h16_kernel(ResArgs p) {
     using namespace r0h;
-    constexpr int YLD = s0f::YLD, YSS = s0f::YSS, YPS = s0f::YPS, YBS = s0f::YBS, NA = s0f::NA;
+    constexpr int YLD = s0f::YLD, YSS = s0f::YSS, YPS = s0f::YPS, YBS = s0f::YBS, NA = s0f::NA, DS = s0f::DS;
     __shared__ __attribute__((aligned(16))) char lds[s0f::LDS_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -183,18 +202,20 @@ __global__ __launch_bounds__(768) void stage0_fused_h16_kernel(ResArgs p) {
         __syncthreads();  // round 0's audio images
 #endif
         S0F_T0();
-        for (int n = 0; n <= R; ++n) {
+        // round n: the block waves write block n - DS's y into buffer (n - DS) % 2; the down conv reads block
+        // n - DS - 1's from the other buffer
+        for (int n = 0; n <= R + DS; ++n) {
 #if S0F_HELP
-            if (hrole == 1 && n < hRw) {  // y halo of this round's section hw (the block wave writes rows 4..35)
+            if (hrole == 1 && n >= DS && n - DS < hRw) {  // y halo of section hw's block n - DS (the block wave writes rows 4..35)
                 uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                if (htw.t0 > 0) v = *reinterpret_cast<const uint4*>(ybase + ((n + 1) & 1) * YBS + hoff_ + 32 * YLD);
-                *reinterpret_cast<uint4*>(ybase + (n & 1) * YBS + hoff_) = v;
+                if (htw.t0 > 0) v = *reinterpret_cast<const uint4*>(ybase + ((n + DS + 1) & 1) * YBS + hoff_ + 32 * YLD);
+                *reinterpret_cast<uint4*>(ybase + ((n + DS) & 1) * YBS + hoff_) = v;
                 htw.next();
             }
 #endif
-            if (n > 0) {
-                const _Float16* yb = ybase + ((n + 1) & 1) * YBS;
-                const int4* dsc = desc + ((n + 1) & 1) * NA;
+            if (n > DS) {
+                const _Float16* yb = ybase + ((n + DS + 1) & 1) * YBS;
+                const int4* dsc = desc + ((n + DS + 1) & 1) * NA;
                 f32x4 acc[2];
 #pragma unroll
                 for (int i = 0; i < 2; ++i) acc[i] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
@@ -345,26 +366,101 @@ __global__ __launch_bounds__(768) void stage0_fused_h16_kernel(ResArgs p) {
     float anext = Rw > 0 ? aload(tw.b, tw.t0) : 0.0f;
 #endif
     S0F_T0();
-    for (int n = 0; n <= R; ++n) {
-        _Float16* ycur = ybase + (n & 1) * YBS;
-        const _Float16* yprev = ybase + ((n + 1) & 1) * YBS;
-        int4* dcur = desc + (n & 1) * NA;
+    // (S0F_DEFER) the kept block: z (2 x 16 registers), its item, first step, item length and rows to store (0 for
+    // the recompute round), retired -- y, halo, descriptor -- one round after its GEMMs
+    [[maybe_unused]] f32x16 kz[2];
+    [[maybe_unused]] unsigned kb = 0;
+    [[maybe_unused]] long long kt0 = 0, kTb = 0;
+    [[maybe_unused]] int krows = 0;
+    [[maybe_unused]] bool kept = false;
+    if (S0F_DEFER) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) kz[0][r] = kz[1][r] = 0.0f;
+    }
+    // y of a block = ELU(z) -> planes of y * yscale, section row 4 + j (zeros past the item's end), 32 pieces of one
+    // channel pair each: even pieces the two ELUs, odd pieces max |t|, the plane split, the zeroing and -- per 4
+    // channels -- the two LDS stores.  (The ops of elu_s4 / split4_t, so the bits of the S0F_DEFER = 0 epilogue.)
+    [[maybe_unused]] float tmy = 0.0f, et[2] = {0.0f, 0.0f};
+    [[maybe_unused]] unsigned eh[2] = {0u, 0u}, el[2] = {0u, 0u};
+    [[maybe_unused]] bool kyin = false;
+    [[maybe_unused]] _Float16* kys = nullptr;
+    [[maybe_unused]] auto epi_piece = [&](int g) {
+        const int pr = g >> 1, mt = pr >> 3, gq = (pr >> 1) & 3, q2 = pr & 1;
+        if (!(g & 1)) {
+            const f32x2 r = elu_s2<true>((f32x2){kz[mt][4 * gq + 2 * q2], kz[mt][4 * gq + 2 * q2 + 1]}, sy);
+            et[0] = r[0];
+            et[1] = r[1];
+        } else {
+            asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(tmy) : "v"(tmy), "v"(et[0]), "v"(et[1]));
+            const f16x2 h = __builtin_convertvector((f32x2){et[0], et[1]}, f16x2);
+            eh[q2] = __builtin_bit_cast(unsigned, h);
+            asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
+                "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
+                : "=&v"(el[q2])
+                : "v"(eh[q2]), "v"(et[0]), "v"(et[1]));
+            if (!kyin) eh[q2] = el[q2] = 0u;
+            if (q2) {
+                const int o = 8 * ((4 * mt + gq) ^ ysw);
+                *reinterpret_cast<uint2*>(kys + o) = make_uint2(eh[0], eh[1]);
+                *reinterpret_cast<uint2*>(kys + YPS + o) = make_uint2(el[0], el[1]);
+            }
+        }
+    };
+    // after the 32 pieces: the range maximum, and (taps only) the y planes in resblock0_h16_kernel's HBM layout,
+    // read back from the rows this lane has just written -- a branch kept out of the GEMM1 schedule
+    [[maybe_unused]] auto epi_done = [&]() {
+        asm volatile("" ::: "memory");  // (the read-back below is of LDS, not of the stores' registers)
+        if (kyin) mxy = fmaxf(mxy, tmy);
+        if (p.yp && kyin) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const int o = 8 * (c ^ ysw);
+                const uint2 hi = *reinterpret_cast<const uint2*>(kys + o);
+                const uint2 lo = *reinterpret_cast<const uint2*>(kys + YPS + o);
+                _Float16* g = reinterpret_cast<_Float16*>(p.yp) + ((long long)kb * T + kt0 + j) * 64 + 8 * c + 4 * hh;
+                *reinterpret_cast<uint2*>(g) = hi;
+                *reinterpret_cast<uint2*>(g + p.y_pstride) = lo;
+            }
+        }
+        kept = false;
+    };
+    for (int n = 0; n <= R + DS; ++n) {
+        // the buffer and descriptors written this round: block n - DS's
+        _Float16* ycur = ybase + ((n + DS) & 1) * YBS;
+        const _Float16* yprev = ybase + ((n + DS + 1) & 1) * YBS;
+        int4* dcur = desc + ((n + DS) & 1) * NA;
+        if (S0F_DEFER) {  // the kept block's descriptor (an empty one without a kept block: round 0 too) and halo
+            if (!S0F_HELP && kept) {
+                uint4 v = make_uint4(0u, 0u, 0u, 0u);
+                if (kt0 > 0) v = *reinterpret_cast<const uint4*>(yprev + hoff + 32 * YLD);
+                *reinterpret_cast<uint4*>(ycur + hoff) = v;
+            }
+            if (lane == 0) dcur[wave] = kept ? make_int4((int)kb, (int)(kt0 >> 2), krows, 0) : make_int4(0, 0, 0, 0);
+            kyin = kept && kt0 + j < kTb;
+            kys = ycur + wave * YSS + yrow * YLD + 4 * hh;
+            tmy = 0.0f;
+        }
         if (n < Rw && S0F_DIAG == 2) {
-            if (lane == 0) dcur[wave] = make_int4((int)tw.b, (int)(tw.t0 >> 2), n < hstart ? 0 : 1, 0);
+            if (S0F_DEFER) {
+                kb = tw.b, kt0 = tw.t0, kTb = tw.Tb, krows = n < hstart ? 0 : 1, kept = true;
+            } else if (lane == 0) {
+                dcur[wave] = make_int4((int)tw.b, (int)(tw.t0 >> 2), n < hstart ? 0 : 1, 0);
+            }
             tw.next();
         } else if (n < Rw) {
             const unsigned b = tw.b;
             const long long t0 = tw.t0;
             const long long Tb = tw.Tb;
-            if (!S0F_HELP) {
-                uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                if (t0 > 0) v = *reinterpret_cast<const uint4*>(yprev + hoff + 32 * YLD);
-                *reinterpret_cast<uint4*>(ycur + hoff) = v;
-            }
-            if (lane == 0) {
-                const long long T1b = (Tb + 3) >> 2;  // ceil(T0 / 4): down conv 0's output steps
-                const long long t10 = t0 >> 2;
-                dcur[wave] = make_int4((int)b, (int)t10, n < hstart ? 0 : (int)min(8LL, T1b - t10), 0);
+            const long long T1b = (Tb + 3) >> 2;  // ceil(T0 / 4): down conv 0's output steps
+            const long long t10 = t0 >> 2;
+            const int rows = n < hstart ? 0 : (int)min(8LL, T1b - t10);
+            if (!S0F_DEFER) {
+                if (!S0F_HELP) {
+                    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+                    if (t0 > 0) v = *reinterpret_cast<const uint4*>(yprev + hoff + 32 * YLD);
+                    *reinterpret_cast<uint4*>(ycur + hoff) = v;
+                }
+                if (lane == 0) dcur[wave] = make_int4((int)b, (int)t10, rows, 0);
             }
             if (t0 == 0) {
                 *reinterpret_cast<uint2*>(slab + cpl * SPL + crow * SLD + cc) = make_uint2(0u, 0u);
@@ -402,13 +498,36 @@ __global__ __launch_bounds__(768) void stage0_fused_h16_kernel(ResArgs p) {
                 f[3] = wf[(FR_W3 + 2 * ks + 1) * 64 + lane];
             };
             g1load(0, fr[0]);
+            if (S0F_DEFER) {
+                // the kept block's epilogue, one piece in the gap behind each of the first 32 MFMAs of the one
+                // accumulator chain: the wave issues the piece's VALU while the MFMA runs.  The scheduling barriers
+                // pin each piece to its gap.  (Round 0 has no kept block: kyin is false, the pieces store zeros
+                // into the section of buffer 1 that round 2 writes next and nothing reads before -- one GEMM1
+                // form, not two, in the registers and the instruction cache.)
 #pragma unroll
-            for (int ks = 0; ks < 12; ++ks) {
-                if (ks + 1 < 12) g1load(ks + 1, fr[(ks + 1) & 1]);
-                const f16x8(&f)[4] = fr[ks & 1];
-                acc1 = mfma_h(f[3], f[0], acc1);
-                acc1 = mfma_h(f[2], f[1], acc1);
-                acc1 = mfma_h(f[2], f[0], acc1);
+                for (int ks = 0; ks < 12; ++ks) {
+                    if (ks + 1 < 12) g1load(ks + 1, fr[(ks + 1) & 1]);
+                    const f16x8(&f)[4] = fr[ks & 1];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        acc1 = mfma_h(i == 0 ? f[3] : f[2], i == 1 ? f[1] : f[0], acc1);
+                        if (3 * ks + i < 32) {
+                            __builtin_amdgcn_sched_barrier(0);
+                            epi_piece(3 * ks + i);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+                }
+                epi_done();
+            } else {
+#pragma unroll
+                for (int ks = 0; ks < 12; ++ks) {
+                    if (ks + 1 < 12) g1load(ks + 1, fr[(ks + 1) & 1]);
+                    const f16x8(&f)[4] = fr[ks & 1];
+                    acc1 = mfma_h(f[3], f[0], acc1);
+                    acc1 = mfma_h(f[2], f[1], acc1);
+                    acc1 = mfma_h(f[2], f[0], acc1);
+                }
             }
             {
                 _Float16* sp = slab + cpl * SPL;
@@ -441,6 +560,32 @@ __global__ __launch_bounds__(768) void stage0_fused_h16_kernel(ResArgs p) {
                 bh[ks][1] = *reinterpret_cast<const f16x8*>(hb + SPL + o);
             }
             // y = ELU(x0 + (acc + b1)) -> planes of y * yscale, section row 4 + j (zeros past the item's end)
+#if S0F_DEFER
+            // ... in the next round's GEMM1 (epi_piece): here only z, kept in x0's place
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                f32x16 acc2;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc2[r] = 0.0f;
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    const f16x8 aw0 = wf[(FR_W1 + (mt * 2 + ks) * 2) * 64 + lane];
+                    const f16x8 aw1 = wf[(FR_W1 + (mt * 2 + ks) * 2 + 1) * 64 + lane];
+                    acc2 = mfma_h(aw1, bh[ks][0], acc2);
+                    acc2 = mfma_h(aw0, bh[ks][1], acc2);
+                    acc2 = mfma_h(aw0, bh[ks][0], acc2);
+                }
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    const f32x4 bb = *reinterpret_cast<const f32x4*>(bl + 96 + 32 * mt + 8 * gq + 4 * hh);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        kz[mt][4 * gq + q] = x0[mt][4 * gq + q] + __builtin_fmaf(acc2[4 * gq + q], u2, bb[q]);
+                }
+            }
+            kb = b, kt0 = t0, kTb = Tb, krows = rows, kept = true;
+            S0F_T(4);  // (slots: 0 descriptor, 1 conv0, 2 slab, 3 GEMM1 + the kept block's y + h, 4 GEMM2 + z, 5 barrier)
+#else
             float tmy = 0.0f;
             const bool yin = t0 + j < Tb;
             _Float16* ys = ycur + wave * YSS + yrow * YLD + 4 * hh;
@@ -480,6 +625,14 @@ __global__ __launch_bounds__(768) void stage0_fused_h16_kernel(ResArgs p) {
             }
             if (yin) mxy = fmaxf(mxy, tmy);
             S0F_T(4);  // (slots: 0 halo + descriptor, 1 conv0, 2 slab, 3 GEMM1 + h, 4 GEMM2 + y, 5 barrier)
+#endif
+        } else if (S0F_DEFER) {
+            if (kept) {  // a round without a block: the kept epilogue alone (slot 3)
+#pragma unroll
+                for (int g = 0; g < 32; ++g) epi_piece(g);
+                epi_done();
+                S0F_T(3);
+            }
         } else if (lane == 0) {
             dcur[wave] = make_int4(0, 0, 0, 0);
         }
