@@ -321,6 +321,74 @@ int64_t mimi_decode_stream_state_bytes(const mimi_decode_stream* st); /* constan
 void mimi_decode_stream_destroy(mimi_decode_stream* st);
 
 /*
+ * Streaming encode: audio to codes chunk by chunk on a KV cache -- the decode stream's other direction.  An encode
+ * stream holds the encoder's state for `batch` items (SLOTS, as in the decode stream): per item the rows every causal
+ * stage reads from in front of a chunk (6 samples of audio for conv 0, kept as the last 8; per stage s 2 rows [C_s] of
+ * the residual block's raw input and r_s rows [C_s] of its ELU'd output for the k = 2 r_s, stride r_s down conv, with
+ * C_s = 64, 128, 256, 512 and r_s = 4, 5, 6, 8; 2 rows [1024] for the final conv; 2 rows [512] of the transformer output
+ * for the downsample) and, per transformer layer, a ring of the rotated key / value rows of the last
+ * sliding_window - 1 + 2 max_step_frames 25 Hz rows.  One device allocation owned by the stream
+ * (mimi_encode_stream_state_bytes: constant over its life).  A fresh or reset slot is all zeros at position 0, with one
+ * exception: the reference pads the downsample with copies of the sequence's FIRST ROW (mode = "replicate"), so on a
+ * step that finds a slot at position 0 that slot's downsample carry is filled from row 0 of that step's transformer
+ * output -- never from what a previous session left.
+ *
+ * mimi_frame_samples_cfg: F = 2 x prod(upsampling_ratios) = 1920 samples, one 12.5 Hz frame (cfg NULL: the defaults).
+ * mimi_encode_stream_step: dev_audio device f32 [batch][F n], 1 <= n <= max_step_frames, the next n WHOLE frames of
+ * every item; dev_codes device int32 [batch][num_quantizers][n].  Fed whole frames every strided length divides
+ * exactly, so no conv pads on the right, which is what MimiModel.encode(use_streaming=True) computes with its
+ * MimiConv1dPaddingCache: the codes of frames [p, p + n) are those of mimi_encode of any sequence that contains those
+ * frames whole (the pre-quantizer embedding within the project's activation tolerance; codes differ only at near-ties).
+ * BIT CONTRACT: (1) a slot's codes for frames [p, p + n) are bitwise the same under ANY split of its sequence into steps;
+ * (2) they are bitwise those of a batch = 1 stream fed that sequence since its last reset; (3) whatever the other slots
+ * do, in any order of `slots`, whatever was called in between.  (Per output row every kernel runs the same instruction
+ * sequence whatever the chunk -- conv 0's history form keeps one fmaf chain per output in tap order -- and the stream
+ * attention's reduction order is a function of the query's absolute row alone.)
+ * Arithmetic: fp32 MFMA always, whatever mimi_set_precision says: no activation scales, no calibration, no overflow
+ * read-back, no lanes, no graphs.  A step runs under the engine mutex on the caller's stream, in mimi_decode's
+ * workspace (grown on demand; MIMI_ERR_OUT_OF_MEMORY leaves the state untouched), with RoPE rows built on the host per
+ * step in pinned memory the stream owns: the engine's shared RoPE table never grows and captured encode graphs survive.
+ * It synchronises `stream` before it returns.  The RVQ runs the per-level kernels.  Works on an encode-only engine.
+ * The number of launches depends on num_quantizers only: not on m, n or the positions.
+ * Taps under mimi_encode's names, holding the step's rows: conv0, res{s}_elu, down{s} / down3_elu, encoder, the per-layer
+ * qkv / att / oproj / ff / xfmr, downsample, proj.  Profiling stages are prefixed encs_; the history and stream forms
+ * record as conv0_hist_kernel<64, 7>, resblock_hist_kernel<...>, attention_stream_kernel,
+ * attention_stream_append_kernel, stream_carry_kernel and stream_ds_rows_kernel (a slot step: the *_slots_kernel forms).
+ *
+ * mimi_encode_stream_step_slots: the m listed slots (`slots`: host, m distinct values in [0, batch), any order), all by
+ * the same n frames: item i of dev_audio [m][F n] and dev_codes [m][num_quantizers][n] belongs to slot slots[i]; nothing
+ * of an unlisted slot is read or written.  mimi_encode_stream_step means "all slots, in order 0 .. batch - 1": while
+ * all slots share a position it is the lock-step pass under the lock-step kernel names, otherwise a slot step.
+ * Errors, with nothing launched and no state touched: MIMI_ERR_INVALID_ARGUMENT for m outside [1, batch], a slot out
+ * of range or listed twice, n outside [1, max_step_frames], a NULL pointer; MIMI_ERR_UNSUPPORTED for a listed slot past
+ * 2^24 25 Hz rows.  There is no bounds flag: audio has no invalid values to index with.  Non-finite samples make that
+ * slot's codes unspecified -- but inside [0, codebook_size) -- from that step until mimi_encode_stream_reset_slot (the
+ * carries and the ring hold them); other slots are bitwise unaffected; the engine does not look for them.  A step that
+ * fails after it touched the state (a HIP error) makes its listed slots return MIMI_ERR_STATE until reset.
+ * mimi_encode_stream_reset / _reset_slot: back to position 0 and a fresh state (all slots / one, its neighbours
+ * untouched).  mimi_encode_stream_position: the largest slot position; _slot_position: one slot's, -1 for NULL or a slot
+ * out of range.  Destroy every stream before its engine.
+ * Not provided: a tail shorter than a frame (the caller keeps it for the next step; mimi_encode's last, right-padded
+ * frame of a length that is not a multiple of F has no streamed equivalent here), a different n per slot within one
+ * call, f16x3 arithmetic, hipGraph capture of a step, the reference's encoder_past_key_values / padding_cache objects.
+ */
+typedef struct mimi_encode_stream mimi_encode_stream;
+int mimi_encode_stream_create(mimi_engine* e, int32_t batch, int32_t num_quantizers, int32_t max_step_frames,
+                              mimi_encode_stream** out);
+int mimi_encode_stream_step(mimi_encode_stream* st, const float* dev_audio /* [batch][F n] */, int32_t n,
+                            int32_t* dev_codes /* [batch][num_quantizers][n] */, void* stream);
+int mimi_encode_stream_step_slots(mimi_encode_stream* st, const int32_t* slots /* host, [m] */, int32_t m,
+                                  const float* dev_audio /* [m][F n] */, int32_t n,
+                                  int32_t* dev_codes /* [m][num_quantizers][n] */, void* stream);
+int mimi_encode_stream_reset(mimi_encode_stream* st);
+int mimi_encode_stream_reset_slot(mimi_encode_stream* st, int32_t slot);
+int64_t mimi_encode_stream_position(const mimi_encode_stream* st);    /* frames encoded so far (the largest slot's) */
+int64_t mimi_encode_stream_slot_position(const mimi_encode_stream* st, int32_t slot); /* -1: NULL / out of range */
+int64_t mimi_encode_stream_state_bytes(const mimi_encode_stream* st); /* constant over the stream's life */
+void mimi_encode_stream_destroy(mimi_encode_stream* st);
+int64_t mimi_frame_samples_cfg(const mimi_config* cfg);               /* F: samples of one frame */
+
+/*
  * Host-only: the weight re-layout that turns a causal MimiConvTranspose1d (kernel 2 ratio, stride ratio, weight
  * [cin][cout][2 ratio]; TF/modeling_mimi.py:349-405) into a causal k = 2 convolution with ratio x cout phase-major
  * output channels: out [ratio * cout][2 * cin], out[p cout + co][ci] = w[ci][co][p + ratio] (the x[t - 1] tap),

@@ -4,6 +4,8 @@
 //   attention_stream_kernel         a step's R = 2n query rows per (item, head) at absolute rows pos0 .. pos0 + R - 1
 //   attention_stream_append_kernel  the step's k / v rows into their ring slots (row r in slot r % cap)
 //   stream_carry_kernel             n strided copies in one launch, from a by-value table
+//   stream_ds_rows_kernel           (encode stream) the transformer's rows behind the downsample's carry, which on an
+//                                   item at row 0 is two copies of its first row (replicate padding)
 // and under the same bodies their slot forms (SL: a step over a subset of the stream's slots, each slot at its own
 // position): item b of the step takes its first row from pos_tab[b] and its rings / carries from slot slot_tab[b];
 // the step's own rows in the workspace stay indexed by b.  The tables are device memory (a step may list 65535 slots).
@@ -274,6 +276,69 @@ hipError_t launch_stream_carry_slots(const CarryTable& t, int batch, const int* 
     if (err != hipSuccess) return err;
     if (!slot_tab) return hipErrorInvalidValue;
     hipLaunchKernelGGL(stream_carry_slots_kernel, grid, dim3(256), 0, s, t, slot_tab);
+    return hipGetLastError();
+}
+
+// Encode stream: item b's R transformer rows (flat [batch][R][C]) go behind the downsample's 2 carry rows in
+// dst [batch][2 + R][C].  An item whose first row is absolute row 0 -- a fresh or reset slot -- has no past: its two
+// carry rows are copies of its row 0 (the reference pads the downsample with mode = "replicate"), written here over
+// whatever carry-in put there.  16 B per thread; the row of dst is uniform per 16 B, the position per workgroup.
+// SL: the item's position is pos_tab[b] (b = blockIdx.y is uniform: a scalar load); both sides stay indexed by b.
+template <bool SL>
+__device__ __forceinline__ void stream_ds_rows_body(const float* __restrict__ src, float* __restrict__ dst, int R, int C,
+                                                    long long pos0, const long long* __restrict__ pos_tab) {
+    const int b = blockIdx.y;
+    if constexpr (SL) pos0 = pos_tab[b];
+    const bool fresh = pos0 == 0;
+    const int c4 = C / 4;
+    const long long n4 = (long long)(2 + R) * c4;
+    const float* __restrict__ sb = src + (long long)b * R * C;
+    float* __restrict__ db = dst + (long long)b * (2 + R) * C;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const long long r = i / c4;  // the row of dst: 0, 1 the carry, 2 + j row j of the step
+        const int c = (int)(i % c4) * 4;
+        if (r < 2 && !fresh) continue;
+        const long long sr = r < 2 ? 0 : r - 2;
+        *reinterpret_cast<f32x4*>(db + r * C + c) = *reinterpret_cast<const f32x4*>(sb + sr * C + c);
+    }
+}
+
+__global__ __launch_bounds__(256) void stream_ds_rows_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                             int R, int C, long long pos0) {
+    stream_ds_rows_body<false>(src, dst, R, C, pos0, nullptr);
+}
+
+__global__ __launch_bounds__(256) void stream_ds_rows_slots_kernel(const float* __restrict__ src,
+                                                                   float* __restrict__ dst, int R, int C,
+                                                                   const long long* __restrict__ pos_tab) {
+    stream_ds_rows_body<true>(src, dst, R, C, 0, pos_tab);
+}
+
+static hipError_t ds_rows_grid(const float* src, float* dst, int batch, int R, int C, dim3* grid) {
+    if (!src || !dst || batch <= 0 || batch > 65535 || R <= 0 || C <= 0 || C % 4 ||
+        (reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 16)
+        return hipErrorInvalidValue;
+    const long long blocks = ((long long)(2 + R) * (C / 4) + 255) / 256;
+    *grid = dim3((unsigned)(blocks < 64 ? blocks : 64), (unsigned)batch);
+    return hipSuccess;
+}
+
+hipError_t launch_stream_ds_rows(const float* src, float* dst, int batch, int R, int C, long long pos0, hipStream_t s) {
+    dim3 grid;
+    const hipError_t err = ds_rows_grid(src, dst, batch, R, C, &grid);
+    if (err != hipSuccess) return err;
+    if (pos0 < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stream_ds_rows_kernel, grid, dim3(256), 0, s, src, dst, R, C, pos0);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_ds_rows_slots(const float* src, float* dst, int batch, int R, int C, const long long* pos_tab,
+                                       hipStream_t s) {
+    dim3 grid;
+    const hipError_t err = ds_rows_grid(src, dst, batch, R, C, &grid);
+    if (err != hipSuccess) return err;
+    if (!pos_tab) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stream_ds_rows_slots_kernel, grid, dim3(256), 0, s, src, dst, R, C, pos_tab);
     return hipGetLastError();
 }
 

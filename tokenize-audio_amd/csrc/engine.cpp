@@ -2732,8 +2732,8 @@ extern "C" int mimi_rvq_encode(mimi_engine* e, const float* emb, int64_t frames,
 // whatever mimi_set_precision says: no activation scales, so no calibration, no overflow read-back, no fallback.
 // A mixed-length batch (mimi_decode_ragged) runs the same pass (decode_pass) over packed rows: DecLayout below.
 // Chunk by chunk on a KV cache: "decode stream" below (mimi_decode_stream_*).
-// Not built here: f16x3 decode, hipGraph capture of decode or of a stream's step, per-item stream positions,
-// streaming encode.
+// The other direction chunk by chunk: "encode stream" further below (mimi_encode_stream_*).
+// Not built here: f16x3 decode, hipGraph capture of decode or of a stream's step.
 
 static int64_t decode_upsampling(const mimi_config& c) {
     int64_t f = 2;  // upsample: 12.5 -> 25 Hz
@@ -3417,10 +3417,14 @@ extern "C" int mimi_decode_ragged(mimi_engine* e, const int32_t* dev_codes, cons
 // mimi_decode_stream_step on slots that all stand at one position is the lock-step pass it always was (same launches,
 // same names); once the positions differ it is a slot step over 0 .. B - 1.
 // ================================================================================================
-struct mimi_decode_stream {
+// What a decode stream and an encode stream have in common: the slots' bookkeeping, the one state allocation (carries |
+// k rings | v rings | RoPE cos | RoPE sin), the pinned images of a step's RoPE rows and slot tables.  The stream_*
+// helpers below are the parts of create / reset / step that do not depend on the direction (`what`: "decode" /
+// "encode", for the messages).
+struct StreamBase {
     mimi_engine* e = nullptr;
     int B = 0, K = 0, max_n = 0, cap = 0;
-    std::vector<int64_t> pos;  // per slot: frames decoded since its last reset
+    std::vector<int64_t> pos;  // per slot: frames decoded / encoded since its last reset
     std::vector<char> failed;  // per slot: a step that listed it failed after it had touched the state: refuse until reset
     float* state = nullptr;  // one allocation: carries | k rings | v rings | RoPE cos | RoPE sin
     size_t state_bytes = 0, zero_bytes = 0;  // zero_bytes: the carries and rings, what reset clears
@@ -3433,6 +3437,197 @@ struct mimi_decode_stream {
     char *tab_host = nullptr, *tab_dev = nullptr;
     int64_t max_pos() const { return *std::max_element(pos.begin(), pos.end()); }
 };
+struct mimi_decode_stream : StreamBase {};
+
+// The RoPE rows of a stream step by ensure_rope's expressions, into a pinned image: item b's rows 2 pos0[b] ..
+// 2 pos0[b] + R - 1 at table rows b R .. (cs, sn: [items * R][head_dim / 2]).  Shared by the decode and the encode stream.
+static void stream_rope_rows(const mimi_config& c, const int64_t* pos0, int items, int R, float* cs, float* sn) {
+    const int half = c.head_dim / 2;
+    for (int d = 0; d < half; ++d) {
+        const float expo = (float)(2 * d) / (float)c.head_dim;
+        const float pw = (float)std::pow((double)c.rope_theta, (double)expo);
+        const float inv = 1.0f / pw;
+        for (int b = 0; b < items; ++b) {
+            const int64_t P = 2 * pos0[b];
+            for (int i = 0; i < R; ++i) {
+                volatile float fr = inv * (float)(P + i);
+                cs[((size_t)b * R + i) * half + d] = (float)std::cos((double)fr);
+                sn[((size_t)b * R + i) * half + d] = (float)std::sin((double)fr);
+            }
+        }
+    }
+}
+
+// lays the state out for st->carry_h / carry_c (already planned) and allocates it, zeroed, with the pinned images
+static int stream_alloc(StreamBase* st, mimi_engine* e, const char* what, int batch, int K, int max_step_frames) {
+    const mimi_config& c = e->cfg;
+    st->e = e;
+    st->B = batch;
+    st->K = K;
+    st->max_n = max_step_frames;
+    st->cap = c.sliding_window - 1 + 2 * max_step_frames;
+    st->pos.assign(batch, 0);
+    st->failed.assign(batch, 0);
+    size_t off = 0;  // floats; every section a multiple of 64 floats
+    auto take = [&](size_t floats) {
+        const size_t at = off;
+        off += (floats + 63) / 64 * 64;
+        return at;
+    };
+    for (size_t i = 0; i < st->carry_h.size(); ++i)
+        st->carry_off.push_back(take((size_t)batch * st->carry_h[i] * st->carry_c[i]));
+    st->ring_layer = (size_t)batch * c.num_attention_heads * st->cap * c.head_dim;
+    const size_t kr = take(st->ring_layer * c.num_hidden_layers), vr = take(st->ring_layer * c.num_hidden_layers);
+    st->zero_bytes = off * sizeof(float);
+    // the RoPE rows of every item of a slot step (at B = 1 the rows of the step, as before)
+    const size_t rope_floats = (size_t)batch * 2 * max_step_frames * (c.head_dim / 2);
+    const size_t tab_bytes = (size_t)batch * (sizeof(int64_t) + sizeof(int32_t));
+    const size_t rc_ = take(rope_floats), rs_ = take(rope_floats);
+    st->state_bytes = off * sizeof(float);
+    hipError_t err = hipMalloc(reinterpret_cast<void**>(&st->state), st->state_bytes);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        st->state = nullptr;
+        return set_err(err == hipErrorOutOfMemory ? MIMI_ERR_OUT_OF_MEMORY : MIMI_ERR_HIP,
+                       "%s stream state hipMalloc(%zu bytes): %s", what, st->state_bytes, hipGetErrorString(err));
+    }
+    st->kring = st->state + kr;
+    st->vring = st->state + vr;
+    st->rope_cos = st->state + rc_;
+    st->rope_sin = st->state + rs_;
+    if ((err = hipMemset(st->state, 0, st->state_bytes)) != hipSuccess ||
+        (err = hipHostMalloc(reinterpret_cast<void**>(&st->rope_host), 2 * rope_floats * sizeof(float),
+                             hipHostMallocDefault)) != hipSuccess ||
+        (err = hipHostMalloc(reinterpret_cast<void**>(&st->tab_host), tab_bytes, hipHostMallocDefault)) != hipSuccess ||
+        (err = hipMalloc(reinterpret_cast<void**>(&st->tab_dev), tab_bytes)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(st->state);
+        if (st->rope_host) (void)hipHostFree(st->rope_host);
+        if (st->tab_host) (void)hipHostFree(st->tab_host);
+        return set_err(MIMI_ERR_HIP, "%s stream state: %s", what, hipGetErrorString(err));
+    }
+    return MIMI_OK;
+}
+
+static void stream_free(StreamBase* st) {
+    std::lock_guard<std::mutex> lk(st->e->mu);  // (every step has synchronised its stream before it returned)
+    (void)hipSetDevice(st->e->device);
+    if (st->state) (void)hipFree(st->state);
+    if (st->rope_host) (void)hipHostFree(st->rope_host);
+    if (st->tab_host) (void)hipHostFree(st->tab_host);
+    if (st->tab_dev) (void)hipFree(st->tab_dev);
+}
+
+static int stream_reset_all(StreamBase* st) {
+    if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
+    std::lock_guard<std::mutex> lk(st->e->mu);
+    HIP_TRY(hipSetDevice(st->e->device));
+    HIP_TRY(hipMemset(st->state, 0, st->zero_bytes));
+    st->pos.assign(st->B, 0);
+    st->failed.assign(st->B, 0);
+    return MIMI_OK;
+}
+
+// One slot back to a fresh stream's: position 0 and zero carries.  Its rings keep their words: a query at row a reads
+// ring rows [max(0, a - W + 1), pos0) only, and all of those are written again before they are read.
+static int stream_reset_one(StreamBase* st, const char* what, int32_t slot) {
+    if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
+    std::lock_guard<std::mutex> lk(st->e->mu);
+    if (slot < 0 || slot >= st->B)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "%s stream: slot %d outside [0, %d)", what, slot, st->B);
+    HIP_TRY(hipSetDevice(st->e->device));
+    for (size_t i = 0; i < st->carry_h.size(); ++i) {
+        const size_t hc = (size_t)st->carry_h[i] * st->carry_c[i];
+        HIP_TRY(hipMemset(st->state + st->carry_off[i] + (size_t)slot * hc, 0, hc * sizeof(float)));
+    }
+    st->pos[slot] = 0;
+    st->failed[slot] = 0;
+    return MIMI_OK;
+}
+
+static bool stream_in_lock_step(const StreamBase* st) {
+    return std::all_of(st->pos.begin(), st->pos.end(), [&](int64_t p) { return p == st->pos[0]; });
+}
+
+// the arguments of a slot step (the pointers apart): every table index is checked here -- the kernels index the rings
+// and carries by slots[i] and read m entries
+static int stream_check_slots(const StreamBase* st, const char* what, const int32_t* slots, int32_t m, int32_t n) {
+    if (m < 1 || m > st->B)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "%s stream step over %d slots outside [1, %d]", what, m, st->B);
+    if (n < 1 || n > st->max_n)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "%s stream step of %d frames outside [1, %d]", what, n, st->max_n);
+    std::vector<char> seen(st->B, 0);
+    for (int i = 0; i < m; ++i) {
+        if (slots[i] < 0 || slots[i] >= st->B)
+            return set_err(MIMI_ERR_INVALID_ARGUMENT, "%s stream: slot %d outside [0, %d)", what, slots[i], st->B);
+        if (seen[slots[i]]) return set_err(MIMI_ERR_INVALID_ARGUMENT, "%s stream: slot %d listed twice", what, slots[i]);
+        seen[slots[i]] = 1;
+    }
+    return MIMI_OK;
+}
+
+// the listed slots' state before a step touches anything (slots == nullptr: all st->B in order)
+static int stream_step_check(const StreamBase* st, const char* what, const int32_t* slots, int m, int n) {
+    const int R = 2 * n;
+    auto slot_of = [&](int i) { return slots ? slots[i] : i; };
+    for (int i = 0; i < m; ++i)
+        if (st->failed[slot_of(i)])
+            return set_err(MIMI_ERR_STATE, "%s stream: a step of slot %d failed; mimi_%s_stream_reset(_slot) first", what,
+                           slot_of(i), what);
+    // RoPE multiplies inv_freq by (float)row: exact only while the row fits float32's 24-bit significand
+    for (int i = 0; i < m; ++i)
+        if (2 * st->pos[slot_of(i)] + R > (1LL << 24))
+            return set_err(MIMI_ERR_UNSUPPORTED, "%s stream: row %lld no longer fits a float32 exactly", what,
+                           (long long)(2 * st->pos[slot_of(i)] + R));
+    if (slots && (int64_t)m * R > 0x7fffffffLL)
+        return set_err(MIMI_ERR_UNSUPPORTED, "%s stream: %d slots x %d rows exceed the 32-bit row range", what, m, R);
+    return MIMI_OK;
+}
+
+// The pinned images of a step and their uploads on s (the previous step synchronised s before it returned: nothing
+// reads them any more).  The tables: item i's first frame and its slot.  The RoPE rows: lock-step rows P .. P + R - 1, a
+// slot step item i's rows 2 pos_i .. 2 pos_i + R - 1 at table rows i R ..  pos0: the items' first frames.  From here on
+// a failure leaves the listed slots half-advanced: they are marked failed until stream_step_done.
+static int stream_step_upload(StreamBase* st, const int32_t* slots, int m, int n, std::vector<int64_t>* pos0,
+                              hipStream_t s) {
+    const mimi_config& c = st->e->cfg;
+    const int R = 2 * n, half = c.head_dim / 2;
+    auto slot_of = [&](int i) { return slots ? slots[i] : i; };
+    pos0->assign(m, 0);
+    int64_t* row_img = reinterpret_cast<int64_t*>(st->tab_host);  // the kernels read positions in 25 Hz rows
+    int32_t* slot_img = reinterpret_cast<int32_t*>(st->tab_host + (size_t)st->B * sizeof(int64_t));
+    for (int i = 0; i < m; ++i) {
+        (*pos0)[i] = st->pos[slot_of(i)];
+        if (slots) {
+            row_img[i] = 2 * (*pos0)[i];
+            slot_img[i] = slots[i];
+        }
+    }
+    const int items = slots ? m : 1;
+    const size_t rope_rows = (size_t)items * R;
+    float* cs = st->rope_host;
+    float* sn = cs + rope_rows * half;
+    stream_rope_rows(c, pos0->data(), items, R, cs, sn);
+    for (int i = 0; i < m; ++i) st->failed[slot_of(i)] = 1;
+    HIP_TRY(hipMemcpyAsync(st->rope_cos, cs, rope_rows * half * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(st->rope_sin, sn, rope_rows * half * 4, hipMemcpyHostToDevice, s));
+    if (slots) {
+        // the device image holds [B] rows then [B] slots, the first m of each
+        HIP_TRY(hipMemcpyAsync(st->tab_dev, row_img, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(st->tab_dev + (size_t)st->B * sizeof(int64_t), slot_img, (size_t)m * sizeof(int32_t),
+                               hipMemcpyHostToDevice, s));
+    }
+    return MIMI_OK;
+}
+
+static void stream_step_done(StreamBase* st, const int32_t* slots, int m, int n) {
+    for (int i = 0; i < m; ++i) {
+        const int b = slots ? slots[i] : i;
+        st->failed[b] = 0;
+        st->pos[b] += n;
+    }
+}
+
 
 // the carries in stage order: upsample, decoder.layers.0, then per ratio (up conv, residual block), the last conv
 static void stream_carry_plan(const mimi_config& c, std::vector<int>* h, std::vector<int>* ch) {
@@ -3504,93 +3699,22 @@ extern "C" int mimi_decode_stream_create(mimi_engine* e, int32_t batch, int32_t 
         return set_err(MIMI_ERR_UNSUPPORTED, "decode stream: sliding_window %d", c.sliding_window);
     HIP_TRY(hipSetDevice(e->device));
     std::unique_ptr<mimi_decode_stream> st(new mimi_decode_stream);
-    st->e = e;
-    st->B = batch;
-    st->K = K;
-    st->max_n = max_step_frames;
-    st->cap = c.sliding_window - 1 + 2 * max_step_frames;
-    st->pos.assign(batch, 0);
-    st->failed.assign(batch, 0);
     stream_carry_plan(c, &st->carry_h, &st->carry_c);
-    size_t off = 0;  // floats; every section a multiple of 64 floats
-    auto take = [&](size_t floats) {
-        const size_t at = off;
-        off += (floats + 63) / 64 * 64;
-        return at;
-    };
-    for (size_t i = 0; i < st->carry_h.size(); ++i)
-        st->carry_off.push_back(take((size_t)batch * st->carry_h[i] * st->carry_c[i]));
-    st->ring_layer = (size_t)batch * c.num_attention_heads * st->cap * c.head_dim;
-    const size_t kr = take(st->ring_layer * c.num_hidden_layers), vr = take(st->ring_layer * c.num_hidden_layers);
-    st->zero_bytes = off * sizeof(float);
-    // the RoPE rows of every item of a slot step (at B = 1 the rows of the step, as before)
-    const size_t rope_floats = (size_t)batch * 2 * max_step_frames * (c.head_dim / 2);
-    const size_t tab_bytes = (size_t)batch * (sizeof(int64_t) + sizeof(int32_t));
-    const size_t rc_ = take(rope_floats), rs_ = take(rope_floats);
-    st->state_bytes = off * sizeof(float);
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&st->state), st->state_bytes);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        return set_err(err == hipErrorOutOfMemory ? MIMI_ERR_OUT_OF_MEMORY : MIMI_ERR_HIP,
-                       "decode stream state hipMalloc(%zu bytes): %s", st->state_bytes, hipGetErrorString(err));
-    }
-    st->kring = st->state + kr;
-    st->vring = st->state + vr;
-    st->rope_cos = st->state + rc_;
-    st->rope_sin = st->state + rs_;
-    if ((err = hipMemset(st->state, 0, st->state_bytes)) != hipSuccess ||
-        (err = hipHostMalloc(reinterpret_cast<void**>(&st->rope_host), 2 * rope_floats * sizeof(float),
-                             hipHostMallocDefault)) != hipSuccess ||
-        (err = hipHostMalloc(reinterpret_cast<void**>(&st->tab_host), tab_bytes, hipHostMallocDefault)) != hipSuccess ||
-        (err = hipMalloc(reinterpret_cast<void**>(&st->tab_dev), tab_bytes)) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(st->state);
-        if (st->rope_host) (void)hipHostFree(st->rope_host);
-        if (st->tab_host) (void)hipHostFree(st->tab_host);
-        return set_err(MIMI_ERR_HIP, "decode stream state: %s", hipGetErrorString(err));
-    }
+    if ((rc = stream_alloc(st.get(), e, "decode", batch, K, max_step_frames))) return rc;
     *out = st.release();
     return MIMI_OK;
 }
 
 extern "C" void mimi_decode_stream_destroy(mimi_decode_stream* st) {
     if (!st) return;
-    {
-        std::lock_guard<std::mutex> lk(st->e->mu);  // (every step has synchronised its stream before it returned)
-        (void)hipSetDevice(st->e->device);
-        if (st->state) (void)hipFree(st->state);
-        if (st->rope_host) (void)hipHostFree(st->rope_host);
-        if (st->tab_host) (void)hipHostFree(st->tab_host);
-        if (st->tab_dev) (void)hipFree(st->tab_dev);
-    }
+    stream_free(st);
     delete st;
 }
 
-extern "C" int mimi_decode_stream_reset(mimi_decode_stream* st) {
-    if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
-    std::lock_guard<std::mutex> lk(st->e->mu);
-    HIP_TRY(hipSetDevice(st->e->device));
-    HIP_TRY(hipMemset(st->state, 0, st->zero_bytes));
-    st->pos.assign(st->B, 0);
-    st->failed.assign(st->B, 0);
-    return MIMI_OK;
-}
+extern "C" int mimi_decode_stream_reset(mimi_decode_stream* st) { return stream_reset_all(st); }
 
-// One slot back to a fresh stream's: position 0 and zero carries.  Its rings keep their words: a query at row a reads
-// ring rows [max(0, a - W + 1), pos0) only, and all of those are written again before they are read.
 extern "C" int mimi_decode_stream_reset_slot(mimi_decode_stream* st, int32_t slot) {
-    if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
-    std::lock_guard<std::mutex> lk(st->e->mu);
-    if (slot < 0 || slot >= st->B)
-        return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream: slot %d outside [0, %d)", slot, st->B);
-    HIP_TRY(hipSetDevice(st->e->device));
-    for (size_t i = 0; i < st->carry_h.size(); ++i) {
-        const size_t hc = (size_t)st->carry_h[i] * st->carry_c[i];
-        HIP_TRY(hipMemset(st->state + st->carry_off[i] + (size_t)slot * hc, 0, hc * sizeof(float)));
-    }
-    st->pos[slot] = 0;
-    st->failed[slot] = 0;
-    return MIMI_OK;
+    return stream_reset_one(st, "decode", slot);
 }
 
 // (the positions are only written under the engine mutex; a caller that reads them while another thread steps the
@@ -3625,6 +3749,101 @@ static int save_tap_strided(mimi_engine* e, const char* name, const float* src, 
     return MIMI_OK;
 }
 
+// The transformer section of a stream step, shared by the decode stream (xf = the decoder's layers, stage names
+// "dec_...") and the encode stream (the encoder's, "encs_..."): run_transformer_f32's launches with the stream's RoPE rows
+// and the attention on the stream's rings.  x in w.t0, the result in w.t0.  slots: the slot forms (sx.pos_tab / slot_tab);
+// pos0: per item (lock-step: [0] for all) the frame its first row belongs to.
+struct StreamXf {
+    const float *rope_cos, *rope_sin;
+    float *kring, *vring;
+    size_t ring_layer;
+    int cap;
+    const long long* pos_tab;
+    const int* slot_tab;
+};
+struct StreamXfWs {
+    float *t0, *t1, *qkv, *att, *ff;
+};
+static int stream_transformer(mimi_engine* e, const std::vector<DevXfmr>& xf, const StreamXf& sx, const StreamXfWs& w,
+                              int B, int R, bool slots, const int64_t* pos0, const char* prefix, Recorder& rec,
+                              hipStream_t s) {
+    const mimi_config& c = e->cfg;
+    const int Hd = c.hidden_size, H = c.num_attention_heads, Dh = c.head_dim;
+    const int64_t P = 2 * pos0[0];  // lock-step: the absolute 25 Hz row of the step's first
+    const std::string pre(prefix);
+    const char* kname = "?";
+    int rc;
+    const int64_t frows = (int64_t)B * R;
+    auto fl = [](const GemmArgs& a) { return 2.0 * a.batch * (double)a.M * a.N * a.K; };
+    auto by = [](const GemmArgs& a, bool res) {
+        return ((double)a.batch * a.M * (a.K + a.N * (res ? 2 : 1)) + (double)a.N * a.K) * 4;
+    };
+    double att_flops = 0;
+    for (int b = 0; b < (slots ? B : 1); ++b)
+        for (int i = 0; i < R; ++i)
+            att_flops += 4.0 * Dh * std::min<int64_t>(2 * pos0[b] + i + 1, c.sliding_window);
+    att_flops *= (double)H * (slots ? 1 : B);
+    for (size_t l = 0; l < xf.size(); ++l) {
+        const DevXfmr& x = xf[l];
+        LAUNCH_TRY(launch_layernorm(w.t0, x.ln1_w, x.ln1_b, w.t1, frows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f,
+                                    nullptr, nullptr, 0, e->ln_rpw),
+                   "ln1");
+        rec.mark(pre + "layernorm", 0, 2.0 * frows * Hd * 4, ln_kname(e->ln_rpw));
+        // lock-step: batched, row m of an item is absolute row P + m and the tables hold rows P ..; slots: the flat
+        // rows, the tables hold every item's rows in step order
+        GemmArgs aq = linear_args(w.t1, slots ? frows : R, Hd, x.wqkv, 3 * H * Dh, w.qkv);
+        if (!slots) {
+            aq.batch = B;
+            aq.a_bstride = (int64_t)R * Hd;
+            aq.c_bstride = (int64_t)R * 3 * H * Dh;
+        }
+        aq.rope_cos = sx.rope_cos;
+        aq.rope_sin = sx.rope_sin;
+        aq.rope_cols = 2 * H * Dh;
+        LAUNCH_TRY(launch_gemm(ROLE_QKV, aq, s, &kname, PREC_F32), "qkv");
+        rec.mark(pre + "qkv", fl(aq), by(aq, false), kname);
+        if ((rc = save_tap_layer(e, "qkv", l, w.qkv, B, R, 3 * H * Dh, s))) return rc;
+        float* kr = sx.kring + l * sx.ring_layer;
+        float* vr = sx.vring + l * sx.ring_layer;
+        const float qscale = 1.0f / std::sqrt((float)Dh);
+        LAUNCH_TRY(slots ? launch_attention_stream_slots(w.qkv, kr, vr, w.att, B, R, H, Dh, c.sliding_window, sx.cap,
+                                                         sx.pos_tab, sx.slot_tab, qscale, s)
+                         : launch_attention_stream(w.qkv, kr, vr, w.att, B, R, H, Dh, c.sliding_window, sx.cap, P,
+                                                   qscale, s),
+                   "attention (stream)");
+        rec.mark(pre + "attention", att_flops, (double)frows * 4 * Hd * 4,
+                 slots ? "mimi::attention_stream_slots_kernel" : "mimi::attention_stream_kernel");
+        if ((rc = save_tap_layer(e, "att", l, w.att, B, R, H * Dh, s))) return rc;
+        LAUNCH_TRY(slots ? launch_attention_stream_append_slots(w.qkv, kr, vr, B, R, H, Dh, sx.cap, sx.pos_tab,
+                                                                sx.slot_tab, s)
+                         : launch_attention_stream_append(w.qkv, kr, vr, B, R, H, Dh, sx.cap, P, s),
+                   "kv append");
+        rec.mark(pre + "kv_append", 0, (double)frows * 4 * H * Dh * 4,
+                 slots ? "mimi::attention_stream_append_slots_kernel" : "mimi::attention_stream_append_kernel");
+        GemmArgs ao = linear_args(w.att, frows, H * Dh, x.wo, Hd, w.t0);
+        ao.R = w.t0;
+        ao.scale = x.ls1;
+        LAUNCH_TRY(launch_gemm(ROLE_OPROJ, ao, s, &kname, PREC_F32), "o_proj");
+        rec.mark(pre + "o_proj", fl(ao), by(ao, true), kname);
+        if ((rc = save_tap_layer(e, "oproj", l, w.t0, B, R, Hd, s))) return rc;
+        LAUNCH_TRY(launch_layernorm(w.t0, x.ln2_w, x.ln2_b, w.t1, frows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f,
+                                    nullptr, nullptr, 0, e->ln_rpw),
+                   "ln2");
+        rec.mark(pre + "layernorm", 0, 2.0 * frows * Hd * 4, ln_kname(e->ln_rpw));
+        GemmArgs a1 = linear_args(w.t1, frows, Hd, x.w1, c.intermediate_size, w.ff);
+        LAUNCH_TRY(launch_gemm(ROLE_FC1, a1, s, &kname, PREC_F32), "fc1");
+        rec.mark(pre + "fc1", fl(a1), by(a1, false), kname);
+        if ((rc = save_tap_layer(e, "ff", l, w.ff, B, R, c.intermediate_size, s))) return rc;
+        GemmArgs a2 = linear_args(w.ff, frows, c.intermediate_size, x.w2, Hd, w.t0);
+        a2.R = w.t0;
+        a2.scale = x.ls2;
+        LAUNCH_TRY(launch_gemm(ROLE_FC2, a2, s, &kname, PREC_F32), "fc2");
+        rec.mark(pre + "fc2", fl(a2), by(a2, true), kname);
+        if ((rc = save_tap_layer(e, "xfmr", l, w.t0, B, R, Hd, s))) return rc;
+    }
+    return MIMI_OK;
+}
+
 // the launches of one step over B items (the workspace w sized for it, the step's RoPE rows already enqueued).
 // slots == nullptr: the lock-step pass, B = st->B items that all stand at frame pos0[0].  Otherwise item i is slot
 // slots[i] at frame pos0[i] (host copies of the tables already enqueued to st->tab_dev).
@@ -3632,9 +3851,8 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
                        const int64_t* pos0, const StreamWs& w, float* dev_audio, hipStream_t s) {
     mimi_engine* e = st->e;
     const mimi_config& c = e->cfg;
-    const int K = st->K, Hd = c.hidden_size, Dq = c.vq_hidden_dim, H = c.num_attention_heads, Dh = c.head_dim;
+    const int K = st->K, Hd = c.hidden_size, Dq = c.vq_hidden_dim;
     const int R = 2 * n, H0 = c.kernel_size - 1, HL = c.last_kernel_size - 1;
-    const int64_t P = 2 * pos0[0];  // lock-step: the absolute 25 Hz row of the step's first
     const long long* pos_tab = reinterpret_cast<const long long*>(st->tab_dev);
     const int* slot_tab = reinterpret_cast<const int*>(st->tab_dev + (size_t)st->B * sizeof(int64_t));
     const char* carry_kn = slots ? "mimi::stream_carry_slots_kernel" : "mimi::stream_carry_kernel";
@@ -3691,74 +3909,9 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
 
     // ---- decoder transformer: run_transformer_f32's launches with the stream's RoPE rows and ring attention ----
     {
-        const int64_t frows = (int64_t)B * R;
-        auto fl = [](const GemmArgs& a) { return 2.0 * a.batch * (double)a.M * a.N * a.K; };
-        auto by = [](const GemmArgs& a, bool res) {
-            return ((double)a.batch * a.M * (a.K + a.N * (res ? 2 : 1)) + (double)a.N * a.K) * 4;
-        };
-        double att_flops = 0;
-        for (int b = 0; b < (slots ? B : 1); ++b)
-            for (int i = 0; i < R; ++i)
-                att_flops += 4.0 * Dh * std::min<int64_t>(2 * pos0[b] + i + 1, c.sliding_window);
-        att_flops *= (double)H * (slots ? 1 : B);
-        for (size_t l = 0; l < e->dxf.size(); ++l) {
-            const DevXfmr& x = e->dxf[l];
-            LAUNCH_TRY(launch_layernorm(w.t0, x.ln1_w, x.ln1_b, w.t1, frows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f,
-                                        nullptr, nullptr, 0, e->ln_rpw),
-                       "ln1");
-            rec.mark("dec_layernorm", 0, 2.0 * frows * Hd * 4, ln_kname(e->ln_rpw));
-            // lock-step: batched, row m of an item is absolute row P + m and the tables hold rows P ..; slots: the flat
-            // rows, the tables hold every item's rows in step order
-            GemmArgs aq = linear_args(w.t1, slots ? frows : R, Hd, x.wqkv, 3 * H * Dh, w.qkv);
-            if (!slots) {
-                aq.batch = B;
-                aq.a_bstride = (int64_t)R * Hd;
-                aq.c_bstride = (int64_t)R * 3 * H * Dh;
-            }
-            aq.rope_cos = st->rope_cos;
-            aq.rope_sin = st->rope_sin;
-            aq.rope_cols = 2 * H * Dh;
-            LAUNCH_TRY(launch_gemm(ROLE_QKV, aq, s, &kname, PREC_F32), "qkv");
-            rec.mark("dec_qkv", fl(aq), by(aq, false), kname);
-            if ((rc = save_tap_layer(e, "qkv", l, w.qkv, B, R, 3 * H * Dh, s))) return rc;
-            float* kr = st->kring + l * st->ring_layer;
-            float* vr = st->vring + l * st->ring_layer;
-            const float qscale = 1.0f / std::sqrt((float)Dh);
-            LAUNCH_TRY(slots ? launch_attention_stream_slots(w.qkv, kr, vr, w.att, B, R, H, Dh, c.sliding_window, st->cap,
-                                                             pos_tab, slot_tab, qscale, s)
-                             : launch_attention_stream(w.qkv, kr, vr, w.att, B, R, H, Dh, c.sliding_window, st->cap, P,
-                                                       qscale, s),
-                       "attention (stream)");
-            rec.mark("dec_attention", att_flops, (double)frows * 4 * Hd * 4,
-                     slots ? "mimi::attention_stream_slots_kernel" : "mimi::attention_stream_kernel");
-            if ((rc = save_tap_layer(e, "att", l, w.att, B, R, H * Dh, s))) return rc;
-            LAUNCH_TRY(slots ? launch_attention_stream_append_slots(w.qkv, kr, vr, B, R, H, Dh, st->cap, pos_tab,
-                                                                    slot_tab, s)
-                             : launch_attention_stream_append(w.qkv, kr, vr, B, R, H, Dh, st->cap, P, s),
-                       "kv append");
-            rec.mark("dec_kv_append", 0, (double)frows * 4 * H * Dh * 4,
-                     slots ? "mimi::attention_stream_append_slots_kernel" : "mimi::attention_stream_append_kernel");
-            GemmArgs ao = linear_args(w.att, frows, H * Dh, x.wo, Hd, w.t0);
-            ao.R = w.t0;
-            ao.scale = x.ls1;
-            LAUNCH_TRY(launch_gemm(ROLE_OPROJ, ao, s, &kname, PREC_F32), "o_proj");
-            rec.mark("dec_o_proj", fl(ao), by(ao, true), kname);
-            if ((rc = save_tap_layer(e, "oproj", l, w.t0, B, R, Hd, s))) return rc;
-            LAUNCH_TRY(launch_layernorm(w.t0, x.ln2_w, x.ln2_b, w.t1, frows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f,
-                                        nullptr, nullptr, 0, e->ln_rpw),
-                       "ln2");
-            rec.mark("dec_layernorm", 0, 2.0 * frows * Hd * 4, ln_kname(e->ln_rpw));
-            GemmArgs a1 = linear_args(w.t1, frows, Hd, x.w1, c.intermediate_size, w.ff);
-            LAUNCH_TRY(launch_gemm(ROLE_FC1, a1, s, &kname, PREC_F32), "fc1");
-            rec.mark("dec_fc1", fl(a1), by(a1, false), kname);
-            if ((rc = save_tap_layer(e, "ff", l, w.ff, B, R, c.intermediate_size, s))) return rc;
-            GemmArgs a2 = linear_args(w.ff, frows, c.intermediate_size, x.w2, Hd, w.t0);
-            a2.R = w.t0;
-            a2.scale = x.ls2;
-            LAUNCH_TRY(launch_gemm(ROLE_FC2, a2, s, &kname, PREC_F32), "fc2");
-            rec.mark("dec_fc2", fl(a2), by(a2, true), kname);
-            if ((rc = save_tap_layer(e, "xfmr", l, w.t0, B, R, Hd, s))) return rc;
-        }
+        const StreamXf sx{st->rope_cos, st->rope_sin, st->kring, st->vring, st->ring_layer, st->cap, pos_tab, slot_tab};
+        const StreamXfWs xw{w.t0, w.t1, w.qkv, w.att, w.ff};
+        if ((rc = stream_transformer(e, e->dxf, sx, xw, B, R, slots != nullptr, pos0, "dec_", rec, s))) return rc;
     }
     {  // the transformer's flat rows behind decoder.layers.0's carry
         CarryTable mv{};
@@ -3837,73 +3990,20 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
 static int stream_step_locked(mimi_decode_stream* st, const int32_t* slots, int m, const int32_t* dev_codes, int n,
                               float* dev_audio, hipStream_t s) {
     mimi_engine* e = st->e;
-    const mimi_config& c = e->cfg;
-    const int R = 2 * n, half = c.head_dim / 2;
-    auto slot_of = [&](int i) { return slots ? slots[i] : i; };
-    for (int i = 0; i < m; ++i)
-        if (st->failed[slot_of(i)])
-            return set_err(MIMI_ERR_STATE, "decode stream: a step of slot %d failed; mimi_decode_stream_reset(_slot) first",
-                           slot_of(i));
-    // RoPE multiplies inv_freq by (float)row: exact only while the row fits float32's 24-bit significand
-    for (int i = 0; i < m; ++i)
-        if (2 * st->pos[slot_of(i)] + R > (1LL << 24))
-            return set_err(MIMI_ERR_UNSUPPORTED, "decode stream: row %lld no longer fits a float32 exactly",
-                           (long long)(2 * st->pos[slot_of(i)] + R));
-    if (slots && (int64_t)m * R > 0x7fffffffLL)
-        return set_err(MIMI_ERR_UNSUPPORTED, "decode stream: %d slots x %d rows exceed the 32-bit row range", m, R);
-    HIP_TRY(hipSetDevice(e->device));
     int rc;
+    if ((rc = stream_step_check(st, "decode", slots, m, n))) return rc;
+    HIP_TRY(hipSetDevice(e->device));
     if ((rc = ensure_dws(e, stream_ws_layout(e, m, n, e->taps).bytes))) return rc;  // (state untouched so far)
     const StreamWs w = stream_ws_layout(e, m, n, e->taps);
-    // The pinned images (the previous step synchronised s before it returned: nothing reads them any more).  The
-    // tables: item i's first frame and its slot.  The RoPE rows by ensure_rope's expressions: lock-step rows P .. P + R - 1,
-    // a slot step item i's rows 2 pos_i .. 2 pos_i + R - 1 at table rows i R ..
-    std::vector<int64_t> pos0(m);  // frames
-    int64_t* row_img = reinterpret_cast<int64_t*>(st->tab_host);  // the kernels read positions in 25 Hz rows
-    int32_t* slot_img = reinterpret_cast<int32_t*>(st->tab_host + (size_t)st->B * sizeof(int64_t));
-    for (int i = 0; i < m; ++i) {
-        pos0[i] = st->pos[slot_of(i)];
-        if (slots) {
-            row_img[i] = 2 * pos0[i];
-            slot_img[i] = slots[i];
-        }
-    }
-    const int items = slots ? m : 1;
-    const size_t rope_rows = (size_t)items * R;
-    float* cs = st->rope_host;
-    float* sn = cs + rope_rows * half;
-    for (int d = 0; d < half; ++d) {
-        const float expo = (float)(2 * d) / (float)c.head_dim;
-        const float pw = (float)std::pow((double)c.rope_theta, (double)expo);
-        const float inv = 1.0f / pw;
-        for (int b = 0; b < items; ++b) {
-            const int64_t P = 2 * pos0[b];
-            for (int i = 0; i < R; ++i) {
-                volatile float fr = inv * (float)(P + i);
-                cs[((size_t)b * R + i) * half + d] = (float)std::cos((double)fr);
-                sn[((size_t)b * R + i) * half + d] = (float)std::sin((double)fr);
-            }
-        }
-    }
-    for (int i = 0; i < m; ++i) st->failed[slot_of(i)] = 1;  // from here on a failure leaves these slots half-advanced
-    HIP_TRY(hipMemcpyAsync(st->rope_cos, cs, rope_rows * half * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(st->rope_sin, sn, rope_rows * half * 4, hipMemcpyHostToDevice, s));
-    if (slots) {
-        // the device image holds [B] rows then [B] slots, the first m of each
-        HIP_TRY(hipMemcpyAsync(st->tab_dev, row_img, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(st->tab_dev + (size_t)st->B * sizeof(int64_t), slot_img, (size_t)m * sizeof(int32_t),
-                               hipMemcpyHostToDevice, s));
-    }
+    std::vector<int64_t> pos0;  // frames
+    if ((rc = stream_step_upload(st, slots, m, n, &pos0, s))) return rc;
     if ((rc = stream_pass(st, dev_codes, m, n, slots, pos0.data(), w, dev_audio, s))) {
         (void)hipStreamSynchronize(s);
         return rc;
     }
-    if ((rc = save_tap(e, "audio", dev_audio, m, decode_upsampling(c) * n, 1, s))) return rc;
+    if ((rc = save_tap(e, "audio", dev_audio, m, decode_upsampling(e->cfg) * n, 1, s))) return rc;
     if ((rc = read_decode_flag(e, s))) return rc;
-    for (int i = 0; i < m; ++i) {
-        st->failed[slot_of(i)] = 0;
-        st->pos[slot_of(i)] += n;
-    }
+    stream_step_done(st, slots, m, n);
     return MIMI_OK;
 }
 
@@ -3919,8 +4019,7 @@ extern "C" int mimi_decode_stream_step(mimi_decode_stream* st, const int32_t* de
         return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream step of %d frames outside [1, %d]", n, st->max_n);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // all slots at one position: the lock-step pass; otherwise a slot step over 0 .. B - 1
-    if (std::all_of(st->pos.begin(), st->pos.end(), [&](int64_t p) { return p == st->pos[0]; }))
-        return stream_step_locked(st, nullptr, st->B, dev_codes, n, dev_audio, s);
+    if (stream_in_lock_step(st)) return stream_step_locked(st, nullptr, st->B, dev_codes, n, dev_audio, s);
     std::vector<int32_t> all(st->B);
     for (int b = 0; b < st->B; ++b) all[b] = b;
     return stream_step_locked(st, all.data(), st->B, dev_codes, n, dev_audio, s);
@@ -3932,19 +4031,393 @@ extern "C" int mimi_decode_stream_step_slots(mimi_decode_stream* st, const int32
     mimi_engine* e = st->e;
     std::lock_guard<std::mutex> lk(e->mu);
     if (!slots || !dev_codes || !dev_audio) return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream step: null argument");
-    if (m < 1 || m > st->B)
-        return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream step over %d slots outside [1, %d]", m, st->B);
-    if (n < 1 || n > st->max_n)
-        return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream step of %d frames outside [1, %d]", n, st->max_n);
-    // every table index is checked here: the kernels index the rings and carries by slots[i] and read m entries
-    std::vector<char> seen(st->B, 0);
-    for (int i = 0; i < m; ++i) {
-        if (slots[i] < 0 || slots[i] >= st->B)
-            return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream: slot %d outside [0, %d)", slots[i], st->B);
-        if (seen[slots[i]]) return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream: slot %d listed twice", slots[i]);
-        seen[slots[i]] = 1;
-    }
+    int rc;
+    if ((rc = stream_check_slots(st, "decode", slots, m, n))) return rc;
     return stream_step_locked(st, slots, m, dev_codes, n, dev_audio, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ================================================================================================
+// encode stream (mimi_encode_stream_*): the encode pass n frames at a time on a KV cache.  DESIGN.md 3.7.2.
+//
+// Every stage of the encoder is causal and, fed whole frames (F = 1920 samples), every strided length divides exactly
+// (F n -> 480 n -> 96 n -> 16 n -> 2 n -> 2 n -> n): no conv ever pads on the right.  So the codes of frames [p, p + n)
+// depend on the past only through (per item) the rows each stage reads from in front of the chunk:
+//   conv 0 (k = 7)         6 samples of audio (kept as the last 8: 16-byte copies)
+//   residual block s       2 rows [C_s]    of its raw input (conv 0 / down conv s - 1 output)
+//   down conv s            r_s rows [C_s]  of the block's ELU'd output (k = 2 r_s, stride r_s)
+//   final conv (k = 3)     2 rows [1024]   of the ELU'd down conv 3 output
+//   attention, per layer   the rotated k and v rows (P - W, P): the decode stream's ring, cap = W - 1 + 2 max_step_frames
+//   downsample (k 4, s 2)  2 rows [hidden] of the transformer output
+// All zero on a fresh or reset slot (causal padding is zero, ELU(0) = 0) but the downsample's: the reference pads it
+// with copies of the sequence's FIRST ROW (F.pad(mode = "replicate"); MimiConv1dPaddingCache when streaming), so on a
+// step that finds a slot at position 0 stream_ds_rows_kernel fills that slot's two carry rows from row 0 of the step's
+// transformer output instead of the state -- per item, from the step's position (table), never from what a previous
+// session left.  The downsample GEMM then reads its carry like every other conv and never reaches its replicate pad.
+//
+// The step runs in the engine's decode workspace (as a decode stream's does: used only between taking and leaving the
+// engine mutex, every step synchronises its stream before it returns), on fp32 MFMA whatever mimi_set_precision says:
+// no activation scales, no calibration, no lanes, no graphs.  Layout and carries as in the decode stream: every stage's
+// tensor is per item [H carry rows | the chunk's rows]; one carry launch in front, one at the end.  The transformer
+// section is stream_transformer, shared with the decode stream; the RVQ runs the per-level kernels (the persistent
+// chain needs its give-up flag read back: off here).  Slots as in the decode stream: what touches the state is
+// indirected through slot_tab / pos_tab (the carry kernel, the attention and the append), the downsample fill reads
+// pos_tab by the item's place, everything else works on the workspace by the item's place in the step.
+// Profiling stages: encs_carry, encs_conv0, encs_res_s<s>, encs_down_s<s>, encs_final, encs_layernorm, encs_qkv,
+// encs_attention, encs_kv_append, encs_o_proj, encs_fc1, encs_fc2, encs_ds_rows, encs_downsample, encs_input_proj, encs_rvq.
+// ================================================================================================
+struct mimi_encode_stream : StreamBase {
+    int64_t F = 0;  // samples per frame
+};
+
+static int64_t frame_samples(const mimi_config& c) {
+    int64_t f = c.downsample_stride;
+    for (int i = 0; i < c.num_ratios; ++i) f *= c.upsampling_ratios[i];
+    return f;
+}
+
+extern "C" int64_t mimi_frame_samples_cfg(const mimi_config* cfg) {
+    mimi_config def;
+    if (!cfg) {
+        mimi_config_default(&def);
+        cfg = &def;
+    }
+    if (cfg->num_ratios < 1 || cfg->num_ratios > 8) return -1;
+    return frame_samples(*cfg);
+}
+
+// the encoder's ratio of stage s (the config lists the decoder's order)
+static int enc_ratio(const mimi_config& c, int s) { return c.upsampling_ratios[c.num_ratios - 1 - s]; }
+
+// the carries in stage order: conv 0, then per stage (residual block, down conv), the final conv, the downsample
+static void enc_stream_carry_plan(const mimi_config& c, std::vector<int>* h, std::vector<int>* ch) {
+    h->assign(1, 1);
+    ch->assign(1, 8);
+    int C = c.num_filters;
+    for (int s = 0; s < c.num_ratios; ++s) {
+        h->push_back(c.residual_kernel_size - 1);
+        ch->push_back(C);
+        h->push_back(enc_ratio(c, s));
+        ch->push_back(C);
+        C *= 2;
+    }
+    h->push_back(c.last_kernel_size - 1);
+    ch->push_back(C);
+    h->push_back(c.downsample_kernel - c.downsample_stride);
+    ch->push_back(c.hidden_size);
+}
+
+// a step's workspace: per SEANet stage its [B][H + rows][C], then the flat-row buffers of the transformer and the rest
+struct EncStreamWs {
+    float *a_hist, *a_tail;       // [B][8]: conv 0's carry in, and the chunk's last 8 samples
+    std::vector<float*> x, y;     // x[s]: raw input of block s behind its 2 carry rows; y[s]: its ELU'd output behind r_s
+    float* xl;                    // ELU'd down conv 3 output behind the final conv's carry
+    float *t0, *t1, *qkv, *att, *ff, *dsin, *dsout, *proj;
+    void* rvq;
+    size_t bytes;
+};
+static EncStreamWs enc_stream_ws_layout(const mimi_engine* e, int B, int n) {
+    const mimi_config& c = e->cfg;
+    const size_t h = c.hidden_size, R = 2 * (size_t)n;
+    EncStreamWs w{};
+    // (sized before the workspace exists: without a base only the byte count is formed, no pointer)
+    char* base = reinterpret_cast<char*>(e->dws);
+    size_t off = 0;
+    auto take = [&](size_t floats) {
+        float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
+        off += pad256(floats * sizeof(float));
+        return p;
+    };
+    w.a_hist = take((size_t)B * 8);
+    w.a_tail = take((size_t)B * 8);
+    size_t C = c.num_filters, len = (size_t)frame_samples(c) * n;
+    for (int s = 0; s < c.num_ratios; ++s) {
+        w.x.push_back(take((size_t)B * (c.residual_kernel_size - 1 + len) * C));
+        w.y.push_back(take((size_t)B * (enc_ratio(c, s) + len) * C));
+        len /= enc_ratio(c, s);
+        C *= 2;
+    }
+    w.xl = take((size_t)B * (c.last_kernel_size - 1 + len) * C);
+    w.t0 = take(B * R * h);
+    w.t1 = take(B * R * h);
+    w.qkv = take(B * R * 3 * c.num_attention_heads * c.head_dim);
+    w.att = take(B * R * h);
+    w.ff = take(B * R * c.intermediate_size);
+    w.dsin = take((size_t)B * (c.downsample_kernel - c.downsample_stride + R) * h);
+    w.dsout = take((size_t)B * n * h);
+    w.proj = take((size_t)B * n * 2 * c.vq_hidden_dim);
+    w.rvq = base ? base + off : nullptr;
+    off += pad256(rvq_work_bytes((long long)B * n));
+    w.bytes = off;
+    return w;
+}
+
+extern "C" int mimi_encode_stream_create(mimi_engine* e, int32_t batch, int32_t K, int32_t max_step_frames,
+                                         mimi_encode_stream** out) {
+    if (!e || !out) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null engine / out");
+    *out = nullptr;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!e->finalized) return set_err(MIMI_ERR_STATE, "mimi_finalize has not been called");
+    const mimi_config& c = e->cfg;
+    if (K <= 0) K = c.num_quantizers;
+    if (K > c.num_quantizers || K < c.num_semantic_quantizers)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "num_quantizers %d outside [%d, %d]", K, c.num_semantic_quantizers,
+                       c.num_quantizers);
+    if (K > e->levels_available)
+        return set_err(MIMI_ERR_WEIGHTS, "num_quantizers %d but the checkpoint has %d codebooks", K, e->levels_available);
+    if (batch <= 0 || batch > 65535 || max_step_frames < 1 || max_step_frames > (1 << 15))
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "batch=%d max_step_frames=%d", batch, max_step_frames);
+    if (c.sliding_window < 1 || (size_t)4 * c.sliding_window * sizeof(float) > 64 * 1024)
+        return set_err(MIMI_ERR_UNSUPPORTED, "encode stream: sliding_window %d", c.sliding_window);
+    // the history kernels' shapes: conv 0 as launch_conv0 takes it, k = 3 / k = 1 blocks, a k = 4 / stride 2 downsample
+    if (c.num_filters != 64 || c.kernel_size != 7 || c.residual_kernel_size != 3 || c.compress != 2 ||
+        c.downsample_kernel != 4 || c.downsample_stride != 2 || c.last_kernel_size < 2 || c.num_ratios > 4 ||
+        c.num_attention_heads * c.head_dim != c.hidden_size)
+        return set_err(MIMI_ERR_UNSUPPORTED, "encode stream: a config outside the kyutai/mimi shapes");
+    HIP_TRY(hipSetDevice(e->device));
+    std::unique_ptr<mimi_encode_stream> st(new mimi_encode_stream);
+    st->F = frame_samples(c);
+    enc_stream_carry_plan(c, &st->carry_h, &st->carry_c);
+    int rc;
+    if ((rc = stream_alloc(st.get(), e, "encode", batch, K, max_step_frames))) return rc;
+    *out = st.release();
+    return MIMI_OK;
+}
+
+extern "C" void mimi_encode_stream_destroy(mimi_encode_stream* st) {
+    if (!st) return;
+    stream_free(st);
+    delete st;
+}
+
+extern "C" int mimi_encode_stream_reset(mimi_encode_stream* st) { return stream_reset_all(st); }
+
+// (the downsample's carry is zeroed with the others: the slot's first step fills it from its own first row whatever it
+// holds)
+extern "C" int mimi_encode_stream_reset_slot(mimi_encode_stream* st, int32_t slot) {
+    return stream_reset_one(st, "encode", slot);
+}
+
+extern "C" int64_t mimi_encode_stream_position(const mimi_encode_stream* st) { return st ? st->max_pos() : -1; }
+
+extern "C" int64_t mimi_encode_stream_slot_position(const mimi_encode_stream* st, int32_t slot) {
+    return st && slot >= 0 && slot < st->B ? st->pos[slot] : -1;
+}
+
+extern "C" int64_t mimi_encode_stream_state_bytes(const mimi_encode_stream* st) {
+    return st ? (int64_t)st->state_bytes : -1;
+}
+
+// the launches of one step over B items (the workspace w sized for it, the step's RoPE rows and tables already
+// enqueued).  slots == nullptr: the lock-step pass, B = st->B items that all stand at frame pos0[0].  Otherwise item i
+// is slot slots[i] at frame pos0[i].
+static int encode_stream_pass(mimi_encode_stream* st, const float* dev_audio, int B, int n, const int32_t* slots,
+                              const int64_t* pos0, const EncStreamWs& w, int32_t* dev_codes, hipStream_t s) {
+    mimi_engine* e = st->e;
+    const mimi_config& c = e->cfg;
+    const int K = st->K, Hd = c.hidden_size, Dq = c.vq_hidden_dim;
+    const int R = 2 * n, HR = c.residual_kernel_size - 1, HL = c.last_kernel_size - 1;
+    const int HD = c.downsample_kernel - c.downsample_stride;
+    const int64_t L = st->F * n;
+    const long long* pos_tab = reinterpret_cast<const long long*>(st->tab_dev);
+    const int* slot_tab = reinterpret_cast<const int*>(st->tab_dev + (size_t)st->B * sizeof(int64_t));
+    const char* carry_kn = slots ? "mimi::stream_carry_slots_kernel" : "mimi::stream_carry_kernel";
+    auto carry = [&](const CarryTable& t) {
+        return slots ? launch_stream_carry_slots(t, B, slot_tab, s) : launch_stream_carry(t, B, s);
+    };
+    int rc;
+    Recorder rec{e, s};
+    rec.begin();
+    const char* kname = "?";
+    char nm[64];
+    // where each carry's rows sit in the workspace, in the order of enc_stream_carry_plan: in front of the item's chunk
+    // (conv 0's apart: in from a_hist, out from a_tail, which conv0_hist_kernel fills)
+    std::vector<float*> where = {nullptr};
+    std::vector<int64_t> rows = {0};  // the chunk's rows behind each carry
+    {
+        int64_t len = L;
+        for (int si = 0; si < c.num_ratios; ++si) {
+            where.push_back(w.x[si]);
+            rows.push_back(len);
+            where.push_back(w.y[si]);
+            rows.push_back(len);
+            len /= enc_ratio(c, si);
+        }
+        where.push_back(w.xl);
+        rows.push_back(len);
+        where.push_back(w.dsin);
+        rows.push_back(len);
+    }
+    if (where.size() != st->carry_h.size() || where.size() > (size_t)CARRY_MAX)
+        return set_err(MIMI_ERR_STATE, "encode stream: %zu carries", where.size());
+    CarryTable in{}, outc{};
+    in.c[0] = {st->state + st->carry_off[0], w.a_hist, 8, 8, 8, CARRY_STATE_SRC};
+    outc.c[0] = {w.a_tail, st->state + st->carry_off[0], 8, 8, 8, CARRY_STATE_DST};
+    for (size_t i = 1; i < where.size(); ++i) {
+        const int64_t hc = (int64_t)st->carry_h[i] * st->carry_c[i], bs = (st->carry_h[i] + rows[i]) * st->carry_c[i];
+        in.c[i] = {st->state + st->carry_off[i], where[i], hc, bs, (int)hc, CARRY_STATE_SRC};
+        outc.c[i] = {where[i] + rows[i] * st->carry_c[i], st->state + st->carry_off[i], bs, hc, (int)hc, CARRY_STATE_DST};
+    }
+    in.n = outc.n = (int)where.size();
+    LAUNCH_TRY(carry(in), "encode stream carry (in)");
+    rec.mark("encs_carry", 0, 0, carry_kn);
+
+    // ---- SEANet encoder ----
+    int C = c.num_filters;
+    int64_t len = L;
+    LAUNCH_TRY(launch_conv0_hist(dev_audio, L, B, e->conv0.w, e->conv0.b, w.x[0] + (int64_t)HR * C, C, c.kernel_size,
+                                 (HR + len) * C, w.a_hist, w.a_tail, s),
+               "conv0 (history)");
+    rec.mark("encs_conv0", 2.0 * B * len * C * c.kernel_size, (double)B * len * (1 + C) * 4,
+             "mimi::conv0_hist_kernel<64, 7>");
+    if ((rc = save_tap_strided(e, "conv0", w.x[0] + (int64_t)HR * C, B, len, C, (HR + len) * C, s))) return rc;
+    // a conv over olen output rows per item whose input has hh carry rows in front of its ilen rows: the carry is
+    // read where conv_args pads
+    auto conv = [&](const DevConv& cv, const float* inp, int hh, int64_t ilen, float* out, int64_t olen, int64_t out_bs) {
+        GemmArgs a = conv_args(cv, inp, hh + ilen, out, olen, B);
+        a.a_off += (int64_t)hh * cv.cin;
+        a.c_bstride = out_bs;
+        return a;
+    };
+    auto fl = [&](const GemmArgs& a) { return 2.0 * B * (double)a.M * a.N * a.K; };
+    auto by = [&](const GemmArgs& a) { return ((double)B * a.M * (a.a_rs + a.N) + (double)a.N * a.K) * 4; };
+    for (int si = 0; si < c.num_ratios; ++si) {
+        const int r = enc_ratio(c, si);
+        const bool last = si == c.num_ratios - 1;
+        if (e->down[si].k != 2 * r || e->down[si].stride != r || len % r)
+            return set_err(MIMI_ERR_UNSUPPORTED, "encode stream: down conv %d is not k = 2 r, stride r", si);
+        ResArgs ra{};
+        ra.x = w.x[si] + (int64_t)HR * C;
+        ra.T = len;
+        ra.batch = B;
+        ra.w3 = e->res3[si].w;
+        ra.b3 = e->res3[si].b;
+        ra.w1 = e->res1[si].w;
+        ra.b1 = e->res1[si].b;
+        ra.y = w.y[si] + (int64_t)r * C;
+        ra.hist = 2;
+        ra.x_bstride = (HR + len) * C;
+        ra.y_bstride = (r + len) * C;
+        LAUNCH_TRY(launch_resblock(C, ra, s, &kname), "encoder resblock (history)");
+        snprintf(nm, sizeof nm, "encs_res_s%d", si);
+        const double Hh = C / c.compress;
+        rec.mark(nm, 2.0 * B * len * (3.0 * C * Hh + Hh * C), (double)B * len * 2 * C * 4, kname);
+        snprintf(nm, sizeof nm, "res%d_elu", si);
+        if ((rc = save_tap_strided(e, nm, ra.y, B, len, C, ra.y_bstride, s))) return rc;
+        // [r + len][C] -> [len / r][2 C], behind the next block's (the final conv's) carry rows
+        const int64_t olen = len / r;
+        const int hn = last ? HL : HR;
+        float* out = (last ? w.xl : w.x[si + 1]) + (int64_t)hn * 2 * C;
+        GemmArgs ad = conv(e->down[si], w.y[si], r, len, out, olen, (hn + olen) * 2 * C);
+        LAUNCH_TRY(launch_gemm(last ? ROLE_DOWN_ELU : ROLE_DOWN, ad, s, &kname, PREC_F32), "down conv");
+        snprintf(nm, sizeof nm, "encs_down_s%d", si);
+        rec.mark(nm, fl(ad), by(ad), kname);
+        snprintf(nm, sizeof nm, last ? "down%d_elu" : "down%d", si);
+        if ((rc = save_tap_strided(e, nm, out, B, olen, 2 * C, (hn + olen) * 2 * C, s))) return rc;
+        C *= 2;
+        len = olen;
+    }
+    if (len != R) return set_err(MIMI_ERR_STATE, "encode stream: %lld rows for %d frames", (long long)len, n);
+    GemmArgs af = conv(e->final_conv, w.xl, HL, R, w.t0, R, (int64_t)R * Hd);
+    LAUNCH_TRY(launch_gemm(ROLE_FINAL, af, s, &kname, PREC_F32), "final conv");
+    rec.mark("encs_final", fl(af), by(af), kname);
+    if ((rc = save_tap(e, "encoder", w.t0, B, R, Hd, s))) return rc;
+
+    // ---- encoder transformer on the stream's rings ----
+    {
+        const StreamXf sx{st->rope_cos, st->rope_sin, st->kring, st->vring, st->ring_layer, st->cap, pos_tab, slot_tab};
+        const StreamXfWs xw{w.t0, w.t1, w.qkv, w.att, w.ff};
+        if ((rc = stream_transformer(e, e->xf, sx, xw, B, R, slots != nullptr, pos0, "encs_", rec, s))) return rc;
+    }
+    // ---- downsample behind its carry (a slot at position 0: two copies of its first row) + projections + RVQ ----
+    LAUNCH_TRY(slots ? launch_stream_ds_rows_slots(w.t0, w.dsin, B, R, Hd, pos_tab, s)
+                     : launch_stream_ds_rows(w.t0, w.dsin, B, R, Hd, 2 * pos0[0], s),
+               "downsample rows");
+    rec.mark("encs_ds_rows", 0, 2.0 * B * R * Hd * 4,
+             slots ? "mimi::stream_ds_rows_slots_kernel" : "mimi::stream_ds_rows_kernel");
+    GemmArgs ad = conv(e->ds, w.dsin, HD, R, w.dsout, n, (int64_t)n * Hd);
+    LAUNCH_TRY(launch_gemm(ROLE_DOWNSAMPLE, ad, s, &kname, PREC_F32), "downsample");
+    rec.mark("encs_downsample", fl(ad), by(ad), kname);
+    if ((rc = save_tap(e, "downsample", w.dsout, B, n, Hd, s))) return rc;
+    GemmArgs ap = linear_args(w.dsout, (int64_t)B * n, Hd, e->inproj, 2 * Dq, w.proj);
+    LAUNCH_TRY(launch_gemm(ROLE_INPROJ, ap, s, &kname, PREC_F32), "input_proj");
+    rec.mark("encs_input_proj", 2.0 * B * n * Hd * 2 * Dq, ((double)B * n * (Hd + 2 * Dq) + 2.0 * Dq * Hd) * 4, kname);
+    if ((rc = save_tap(e, "proj", w.proj, B, n, 2 * Dq, s))) return rc;
+    {
+        RvqArgs r{};
+        r.work = w.rvq;
+        r.proj = w.proj;
+        r.frames = (int64_t)B * n;
+        r.D = c.codebook_dim;
+        r.ncodes = c.codebook_size;
+        r.levels = K;
+        r.nsem = c.num_semantic_quantizers;
+        r.cb_frag = e->cb_frag;
+        r.cb_rows = e->cb_rows;
+        r.cb_norm = e->cb_norm;
+        r.cb_h16 = e->cb_h16;
+        r.cb_unscale = e->cb_unscale;
+        r.cb_emax = e->cb_emax;
+        r.codes = dev_codes;
+        r.frames_per_item = n;
+        r.form = e->rvq_form;
+        r.chain = 0;  // the per-level kernels: nobody reads a give-up flag back here
+        r.xcd_group_ok = e->rvq_xcd;
+        LAUNCH_TRY(launch_rvq(r, s, &kname, nullptr, nullptr), "rvq");
+        rec.mark("encs_rvq", 2.0 * B * n * r.D * r.ncodes * K, (double)B * n * (2 * r.D + K) * 4, kname);
+    }
+    LAUNCH_TRY(carry(outc), "encode stream carry (out)");
+    rec.mark("encs_carry", 0, 0, carry_kn);
+    return MIMI_OK;
+}
+
+// One step over the m listed slots (slots == nullptr: all st->B in order, at one position: the lock-step pass).
+// Called with the engine mutex held and every argument checked but the slots' state.
+static int encode_stream_step_locked(mimi_encode_stream* st, const int32_t* slots, int m, const float* dev_audio, int n,
+                                     int32_t* dev_codes, hipStream_t s) {
+    mimi_engine* e = st->e;
+    int rc;
+    if ((rc = stream_step_check(st, "encode", slots, m, n))) return rc;
+    if (st->F * n > 0x7fffffffLL)
+        return set_err(MIMI_ERR_UNSUPPORTED, "encode stream: %d frames exceed the 32-bit row range", n);
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = ensure_dws(e, enc_stream_ws_layout(e, m, n).bytes))) return rc;  // (state untouched so far)
+    const EncStreamWs w = enc_stream_ws_layout(e, m, n);
+    std::vector<int64_t> pos0;  // frames
+    if ((rc = stream_step_upload(st, slots, m, n, &pos0, s))) return rc;
+    rc = encode_stream_pass(st, dev_audio, m, n, slots, pos0.data(), w, dev_codes, s);
+    // the workspace and the pinned images are free for the next call under the mutex, whatever its stream
+    const hipError_t se = hipStreamSynchronize(s);
+    if (rc) return rc;
+    if (se != hipSuccess) return set_err(MIMI_ERR_HIP, "encode stream step: %s", hipGetErrorString(se));
+    stream_step_done(st, slots, m, n);
+    return MIMI_OK;
+}
+
+extern "C" int mimi_encode_stream_step(mimi_encode_stream* st, const float* dev_audio, int32_t n, int32_t* dev_codes,
+                                       void* stream) {
+    if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
+    mimi_engine* e = st->e;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!dev_audio || !dev_codes) return set_err(MIMI_ERR_INVALID_ARGUMENT, "encode stream step: null argument");
+    if (n < 1 || n > st->max_n)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "encode stream step of %d frames outside [1, %d]", n, st->max_n);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // all slots at one position: the lock-step pass; otherwise a slot step over 0 .. B - 1
+    if (stream_in_lock_step(st)) return encode_stream_step_locked(st, nullptr, st->B, dev_audio, n, dev_codes, s);
+    std::vector<int32_t> all(st->B);
+    for (int b = 0; b < st->B; ++b) all[b] = b;
+    return encode_stream_step_locked(st, all.data(), st->B, dev_audio, n, dev_codes, s);
+}
+
+extern "C" int mimi_encode_stream_step_slots(mimi_encode_stream* st, const int32_t* slots, int32_t m,
+                                             const float* dev_audio, int32_t n, int32_t* dev_codes, void* stream) {
+    if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
+    mimi_engine* e = st->e;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!slots || !dev_audio || !dev_codes) return set_err(MIMI_ERR_INVALID_ARGUMENT, "encode stream step: null argument");
+    int rc;
+    if ((rc = stream_check_slots(st, "encode", slots, m, n))) return rc;
+    return encode_stream_step_locked(st, slots, m, dev_audio, n, dev_codes, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" void mimi_destroy(mimi_engine* e) {

@@ -532,6 +532,18 @@ struct CarryTable {
 hipError_t launch_stream_carry(const CarryTable& t, int batch, hipStream_t s);
 hipError_t launch_stream_carry_slots(const CarryTable& t, int batch, const int* slot_tab, hipStream_t s);
 
+// Streamed encode (engine.cpp "encode stream").
+// conv0_hist_kernel: launch_conv0 on a chunk of L >= 8 samples per item whose 6 samples of the past are the last ones
+// of hist [batch][8] (read where the one-shot form pads with zeros); y rows at y + b * y_bstride; the chunk's last 8
+// samples to tail [batch][8].  Per output the arithmetic of conv0_kernel.
+hipError_t launch_conv0_hist(const float* x, long long L, int batch, const float* w, const float* b, float* y, int cout,
+                             int ksize, long long y_bstride, const float* hist, float* tail, hipStream_t s);
+// stream_ds_rows_kernel: src [batch][R][C] -> dst [batch][2 + R][C] rows 2 .., and where the item's first row is
+// absolute row 0 (pos0, or pos_tab[b] in the slot form) dst rows 0, 1 = src row 0: the downsample's replicate padding
+hipError_t launch_stream_ds_rows(const float* src, float* dst, int batch, int R, int C, long long pos0, hipStream_t s);
+hipError_t launch_stream_ds_rows_slots(const float* src, float* dst, int batch, int R, int C, const long long* pos_tab,
+                                       hipStream_t s);
+
 // polyphase resampler (resample.hip): clips packed at in_off / out_off (device int64 arrays), one launch
 hipError_t launch_resample_poly(const float* x, const long long* in_off, const long long* in_len, int nclips,
                                 float* y, const long long* out_off, const long long* out_len, long long max_out,

@@ -14,13 +14,18 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // HBM-bound (7 MACs per 4-byte output): each workgroup stages its 128 + 6 input samples in LDS and
 // writes 128 x 64 outputs as coalesced float4 rows.
 // ------------------------------------------------------------------------------------------------
-template <int COUT, int KS>
-__global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ x, long long L,
-                                                    const float* __restrict__ w, const float* __restrict__ bias,
-                                                    float* __restrict__ y) {
+// HS (a step of an encode stream, engine.cpp "encode stream"): item b's KS - 1 samples in front of the chunk are the
+// last ones of hist[b][8] -- the stream's carry, real data where the one-shot form pads with zeros -- its output rows
+// start at y + b * y_bstride (behind the stage-0 block's own carry rows), and the chunk's last 8 samples go to
+// tail[b][8], the next step's carry.  Per output the same fmaf chain in tap order, then + bias.
+template <int COUT, int KS, bool HS>
+__device__ __forceinline__ void conv0_body(const float* __restrict__ x, long long L, const float* __restrict__ w,
+                                           const float* __restrict__ bias, float* __restrict__ y, long long y_bstride,
+                                           const float* __restrict__ hist, float* __restrict__ tail) {
     constexpr int TT = 128;
     constexpr int CG = COUT / 4;        // channel groups of 4
     constexpr int TG = 256 / CG;        // time lanes
+    static_assert(!HS || KS - 1 <= 8, "the carry holds 8 samples");
     __shared__ float xs[TT + KS - 1];
     __shared__ float ws[COUT * KS];
     __shared__ float bs[COUT];
@@ -29,14 +34,25 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ x,
     const float* xb = x + (long long)b * L;
     for (int i = threadIdx.x; i < TT + KS - 1; i += 256) {
         const long long t = t0 - (KS - 1) + i;
-        xs[i] = (t >= 0 && t < L) ? xb[t] : 0.0f;
+        float v = (t >= 0 && t < L) ? xb[t] : 0.0f;
+        if constexpr (HS) {
+            if (t < 0) v = hist[(long long)b * 8 + 8 + t];  // t in [-(KS - 1), 0)
+        }
+        xs[i] = v;
+    }
+    if constexpr (HS) {
+        // sample L - 8 + i belongs to exactly one workgroup's [t0, t0 + TT)
+        if (threadIdx.x < 8) {
+            const long long t = L - 8 + threadIdx.x;
+            if (t >= t0 && t < t0 + TT && t >= 0) tail[(long long)b * 8 + threadIdx.x] = xb[t];
+        }
     }
     for (int i = threadIdx.x; i < COUT * KS; i += 256) ws[i] = w[i];
     for (int i = threadIdx.x; i < COUT; i += 256) bs[i] = bias[i];
     __syncthreads();
     const int cg = threadIdx.x % CG;
     const int tl = threadIdx.x / CG;
-    float* yb = y + (long long)b * L * COUT;
+    float* yb = y + (HS ? (long long)b * y_bstride : (long long)b * L * COUT);
     for (int tt = tl; tt < TT; tt += TG) {
         const long long t = t0 + tt;
         if (t >= L) break;
@@ -53,11 +69,36 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ x,
     }
 }
 
+template <int COUT, int KS>
+__global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ x, long long L,
+                                                    const float* __restrict__ w, const float* __restrict__ bias,
+                                                    float* __restrict__ y) {
+    conv0_body<COUT, KS, false>(x, L, w, bias, y, 0, nullptr, nullptr);
+}
+
+template <int COUT, int KS>
+__global__ __launch_bounds__(256) void conv0_hist_kernel(const float* __restrict__ x, long long L,
+                                                         const float* __restrict__ w, const float* __restrict__ bias,
+                                                         float* __restrict__ y, long long y_bstride,
+                                                         const float* __restrict__ hist, float* __restrict__ tail) {
+    conv0_body<COUT, KS, true>(x, L, w, bias, y, y_bstride, hist, tail);
+}
+
 hipError_t launch_conv0(const float* x, long long L, int batch, const float* w, const float* b, float* y,
                         int cout, int ksize, hipStream_t s) {
     if (cout != 64 || ksize != 7) return hipErrorInvalidValue;
     dim3 grid((unsigned)((L + 127) / 128), batch);
     hipLaunchKernelGGL((conv0_kernel<64, 7>), grid, dim3(256), 0, s, x, L, w, b, y);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv0_hist(const float* x, long long L, int batch, const float* w, const float* b, float* y,
+                             int cout, int ksize, long long y_bstride, const float* hist, float* tail, hipStream_t s) {
+    if (cout != 64 || ksize != 7 || L < 8 || batch <= 0 || batch > 65535 || (L + 127) / 128 > 0x7fffffffLL ||
+        y_bstride < L * cout || y_bstride % 4 || !x || !w || !b || !y || !hist || !tail)
+        return hipErrorInvalidValue;
+    dim3 grid((unsigned)((L + 127) / 128), batch);
+    hipLaunchKernelGGL((conv0_hist_kernel<64, 7>), grid, dim3(256), 0, s, x, L, w, b, y, y_bstride, hist, tail);
     return hipGetLastError();
 }
 

@@ -36,6 +36,9 @@ EXPORTED_SYMBOLS = (
     "mimi_decode_stream_create", "mimi_decode_stream_step", "mimi_decode_stream_reset", "mimi_decode_stream_position",
     "mimi_decode_stream_state_bytes", "mimi_decode_stream_destroy",
     "mimi_decode_stream_step_slots", "mimi_decode_stream_reset_slot", "mimi_decode_stream_slot_position",
+    "mimi_encode_stream_create", "mimi_encode_stream_step", "mimi_encode_stream_step_slots", "mimi_encode_stream_reset",
+    "mimi_encode_stream_reset_slot", "mimi_encode_stream_position", "mimi_encode_stream_slot_position",
+    "mimi_encode_stream_state_bytes", "mimi_encode_stream_destroy", "mimi_frame_samples_cfg",
     "mimi_bpe_model_create", "mimi_bpe_model_destroy", "mimi_bpe_encode", "mimi_bpe_model_info",
     "mimi_bpe_model_set_alphabet", "mimi_bpe_encode_codes",
     "mimi_bpe_create_opts", "mimi_bpe_info", "mimi_bpe_read_pairs", "mimi_bpe_read_words",
@@ -184,6 +187,16 @@ def _declare(lib):
         "mimi_decode_stream_step_slots": (c.c_int, [vp, c.POINTER(c.c_int32), c.c_int32, vp, c.c_int32, vp, vp]),
         "mimi_decode_stream_reset_slot": (c.c_int, [vp, c.c_int32]),
         "mimi_decode_stream_slot_position": (c.c_int64, [vp, c.c_int32]),
+        "mimi_encode_stream_create": (c.c_int, [vp, c.c_int32, c.c_int32, c.c_int32, c.POINTER(vp)]),
+        "mimi_encode_stream_step": (c.c_int, [vp, vp, c.c_int32, vp, vp]),
+        "mimi_encode_stream_step_slots": (c.c_int, [vp, c.POINTER(c.c_int32), c.c_int32, vp, c.c_int32, vp, vp]),
+        "mimi_encode_stream_reset": (c.c_int, [vp]),
+        "mimi_encode_stream_reset_slot": (c.c_int, [vp, c.c_int32]),
+        "mimi_encode_stream_position": (c.c_int64, [vp]),
+        "mimi_encode_stream_slot_position": (c.c_int64, [vp, c.c_int32]),
+        "mimi_encode_stream_state_bytes": (c.c_int64, [vp]),
+        "mimi_encode_stream_destroy": (None, [vp]),
+        "mimi_frame_samples_cfg": (c.c_int64, [c.POINTER(MimiConfigC)]),
         "mimi_resample_poly": (c.c_int, [vp, vp, vp, c.c_int32, vp, vp, vp, c.c_int64, vp, c.c_int32, c.c_int32,
                                          c.c_int32, c.c_int64, vp]),
     }

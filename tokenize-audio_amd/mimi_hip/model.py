@@ -15,6 +15,9 @@ Mirrors the model-level API every reference wrapper calls:
   the ``1920 n`` samples of the next ``n`` frames from a KV cache and per-stage carries (the same bits under any split
   of a sequence into steps); ``.step(codes[m, K, n], slots=[...])`` advances only the listed slots, each at its own
   position, and ``.reset(slot)`` frees one.
+* ``model.encode_stream(batch, num_quantizers, max_step_frames)`` -> ``EncodeStream``: ``.step(audio[B, 1920 n])``
+  returns the int32 codes ``[B, K, n]`` of the next ``n`` whole frames, with the same slot interface and the same
+  bit contract (``encode(use_streaming=True)`` and the reference's cache objects stay unprovided).
 * ``.to(device)``, ``.eval()``, ``get_encoded_length``, ``from_pretrained(local_dir | "kyutai/mimi")``.
 
 The arithmetic runs in ``libmimi_hip.so`` (HIP kernels for gfx950); torch only supplies device memory and
@@ -254,6 +257,129 @@ class DecodeStream:
             pass
 
 
+class EncodeStream:
+    """Streaming encode (``MimiHipModel.encode_stream``): ``batch`` items, ``n`` whole frames of audio (``frame_samples``
+    = 1920 samples each) in and their codes ``[., K, n]`` out per ``step``, on a KV cache and per-stage carries that the
+    stream owns in device memory (``state_bytes``, constant).  The codes of frames ``[p, p + n)`` are bitwise the same
+    under any split of a sequence into steps; the pre-quantizer embedding is within the activation tolerance of
+    ``encode`` of any sequence that holds those frames whole.  Always fp32 arithmetic, whatever ``set_precision`` says.
+
+    Every item is a SLOT with its own position, as in ``DecodeStream``: ``step(audio)`` advances all of them,
+    ``step(audio, slots=[...])`` only the listed ones, ``reset(slot)`` frees one.  A slot's codes are bitwise those of a
+    ``batch=1`` stream fed the same sequence, whatever its neighbours do.  A tail shorter than a frame is the caller's
+    to keep for the next step.  A context manager; ``close()`` frees the state (closing the model closes its streams)."""
+
+    def __init__(self, model: "MimiHipModel", batch: int, num_quantizers: int, max_step_frames: int):
+        self._model, self.batch, self.num_quantizers = model, int(batch), int(num_quantizers)
+        self.max_step_frames = int(max_step_frames)
+        self.frame_samples = int(model._lib.mimi_frame_samples_cfg(ctypes.byref(model._cfg_c)))
+        self._h = None
+        h = ctypes.c_void_p()
+        try:
+            _lib.check(model._lib.mimi_encode_stream_create(model._h, self.batch, self.num_quantizers,
+                                                            self.max_step_frames, ctypes.byref(h)))
+        except _lib.MimiHipError as err:
+            if err.status == 1:
+                raise ValueError(str(err)) from None
+            raise
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError("this EncodeStream is closed")
+        return self._h
+
+    @property
+    def position(self) -> int:
+        """Frames encoded so far (the furthest slot's)."""
+        return int(self._model._lib.mimi_encode_stream_position(self._handle()))
+
+    @property
+    def positions(self) -> List[int]:
+        """Frames encoded by each slot since its last reset."""
+        h = self._handle()
+        return [int(self._model._lib.mimi_encode_stream_slot_position(h, b)) for b in range(self.batch)]
+
+    @property
+    def state_bytes(self) -> int:
+        return int(self._model._lib.mimi_encode_stream_state_bytes(self._handle()))
+
+    def step(self, audio: torch.Tensor, slots: Optional[Sequence[int]] = None,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The next ``n`` frames: float32 audio ``[B, F n]`` or ``[B, 1, F n]`` (``F = frame_samples``) on any device ->
+        int32 codes ``[B, K, n]`` on the model's device (``out`` if given).  With ``slots`` (``m`` distinct ints in
+        ``[0, batch)``, any order) only those slots advance: ``audio`` holds ``m`` items, item ``i`` the next frames of
+        slot ``slots[i]``, the result is ``[m, K, n]``.  ``ValueError`` for a length that is not ``1 ..
+        max_step_frames`` whole frames and for a bad slot list or ``out`` (the state is untouched)."""
+        m = self._model
+        h = self._handle()
+        if not torch.is_tensor(audio):
+            audio = torch.as_tensor(np.asarray(audio))
+        if slots is not None:
+            slots = [int(x) for x in slots]
+            if not 1 <= len(slots) <= self.batch:
+                raise ValueError(f"a step lists 1 .. {self.batch} slots, got {len(slots)}")
+            if min(slots) < 0 or max(slots) >= self.batch or len(set(slots)) != len(slots):
+                raise ValueError(f"slots must be distinct and in [0, {self.batch}), got {slots}")
+        items = self.batch if slots is None else len(slots)
+        if audio.dim() == 3 and audio.shape[1] == 1:
+            audio = audio[:, 0]
+        if audio.dim() != 2 or audio.shape[0] != items:
+            raise ValueError(f"audio must be [{items}, F n] or [{items}, 1, F n], got {tuple(audio.shape)}")
+        F = self.frame_samples
+        L = int(audio.shape[1])
+        if L % F or not 1 <= L // F <= self.max_step_frames:
+            raise ValueError(f"a step takes 1 .. {self.max_step_frames} whole frames of {F} samples, got {L} samples")
+        n = L // F
+        out = m._out(items, self.num_quantizers, n, out)
+        x = audio.to(device=m.device, dtype=torch.float32).contiguous()
+        try:
+            if slots is None:
+                _lib.check(m._lib.mimi_encode_stream_step(h, ctypes.c_void_p(x.data_ptr()), n,
+                                                          ctypes.c_void_p(out.data_ptr()), m._stream()))
+            else:
+                tab = (ctypes.c_int32 * items)(*slots)
+                _lib.check(m._lib.mimi_encode_stream_step_slots(h, tab, items, ctypes.c_void_p(x.data_ptr()), n,
+                                                                ctypes.c_void_p(out.data_ptr()), m._stream()))
+        except _lib.MimiHipError as err:
+            if err.status == 1:
+                raise ValueError(str(err)) from None
+            raise
+        return out
+
+    def reset(self, slot: Optional[int] = None):
+        """Back to position 0 with a fresh state: what follows equals a fresh stream.  With ``slot`` only that slot, its
+        neighbours untouched (``ValueError`` for a slot outside ``[0, batch)``)."""
+        if slot is None:
+            _lib.check(self._model._lib.mimi_encode_stream_reset(self._handle()))
+            return
+        try:
+            _lib.check(self._model._lib.mimi_encode_stream_reset_slot(self._handle(), int(slot)))
+        except _lib.MimiHipError as err:
+            if err.status == 1:
+                raise ValueError(str(err)) from None
+            raise
+
+    def close(self):
+        h, self._h = self._h, None
+        if h is not None and self._model._h is not None:
+            self._model._lib.mimi_encode_stream_destroy(h)
+        self._model._streams.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MimiHipModel:
     """Mimi on MI355X: encode always; decode (codes -> waveform) when built with ``decode=True``, which makes the
     decoder half of the checkpoint (``decoder*``, ``upsample*``, ``decoder_transformer*``, ``output_proj``) required.
@@ -271,7 +397,7 @@ class MimiHipModel:
         _lib.check(self._lib.mimi_create(ctypes.byref(self._cfg_c), self.device.index, ctypes.byref(handle)))
         self._h = handle
         self._lock = threading.Lock()
-        self._streams = weakref.WeakSet()  # open DecodeStreams: closed before the engine
+        self._streams = weakref.WeakSet()  # open DecodeStreams / EncodeStreams: closed before the engine
         self._src = (state_dict, config, safetensors_path)  # for clone()
         self.decode_enabled = bool(decode)
         try:
@@ -392,6 +518,7 @@ class MimiHipModel:
                num_quantizers: Optional[int] = None, encoder_past_key_values=None, padding_cache=None,
                use_streaming: Optional[bool] = None, return_dict: Optional[bool] = None):
         if use_streaming:
+            # (the reference's cache objects are not provided: the chunked path is encode_stream)
             raise NotImplementedError("streaming encode (padding cache / KV cache) is not on the batch path")
         K = self._check_k(self.config.num_quantizers if num_quantizers is None else num_quantizers)
         if not torch.is_tensor(input_values):
@@ -416,6 +543,19 @@ class MimiHipModel:
         if return_dict is False:
             return (out, None, None)
         return MimiEncoderOutput(out)
+
+    def encode_stream(self, batch: int = 1, num_quantizers: Optional[int] = None,
+                      max_step_frames: int = 1) -> EncodeStream:
+        """A streaming encode of ``batch`` items (``mimi_encode_stream_*``): ``.step(audio[B, 1920 n])`` returns the int32
+        codes ``[B, K, n]`` of the next ``n <= max_step_frames`` frames of all of them, ``.step(audio[m, 1920 n],
+        slots=[...])`` of the listed slots only, each slot at its own position.  Works without the decode weights.
+        Several streams may be open on one model and interleave with ``encode`` / ``decode`` / ``decode_stream``."""
+        K = self._check_k(self.config.num_quantizers if num_quantizers is None else num_quantizers)
+        if int(batch) < 1 or int(max_step_frames) < 1:
+            raise ValueError(f"batch and max_step_frames must be >= 1, got {batch} and {max_step_frames}")
+        st = EncodeStream(self, batch, K, max_step_frames)
+        self._streams.add(st)
+        return st
 
     def encode_int32(self, audio: torch.Tensor, num_quantizers: int, out: Optional[torch.Tensor] = None
                      ) -> torch.Tensor:
