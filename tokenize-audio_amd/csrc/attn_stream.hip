@@ -9,6 +9,9 @@
 // and under the same bodies their slot forms (SL: a step over a subset of the stream's slots, each slot at its own
 // position): item b of the step takes its first row from pos_tab[b] and its rings / carries from slot slot_tab[b];
 // the step's own rows in the workspace stay indexed by b.  The tables are device memory (a step may list 65535 slots).
+// One launcher per body (launch_attention_stream, launch_attention_stream_append, launch_stream_carry,
+// launch_stream_ds_rows): null tables launch the lock-step kernel at the scalar pos0, non-null tables the slot kernel,
+// and *kname receives the name of the one launched.
 //
 // CHUNKING DOES NOT MOVE A BIT.  Query row a (absolute) attends keys jlo = max(0, a - W + 1) .. a.  One WAVE owns the
 // row.  Key jlo + t belongs to lane t % 64; a lane's score is one fmaf chain over d = 0 .. 63; the maximum is exact
@@ -126,29 +129,24 @@ __global__ __launch_bounds__(256) void attention_stream_slots_kernel(const float
     attention_stream_body<true>(sc_all, qkv, kring, vring, out, R, H, window, cap, 0, pos_tab, slot_tab, scale);
 }
 
+// pos_tab / slot_tab both null: the lock-step kernel at pos0; both set: the slot kernel (pos0 unused)
 hipError_t launch_attention_stream(const float* qkv, const float* kring, const float* vring, float* out, int batch,
-                                   int R, int H, int D, int window, int cap, long long pos0, float scale,
-                                   hipStream_t s) {
+                                   int R, int H, int D, int window, int cap, long long pos0, const long long* pos_tab,
+                                   const int* slot_tab, float scale, hipStream_t s, const char** kname) {
+    const bool sl = pos_tab || slot_tab;
     if (D != 64 || batch <= 0 || batch > 65535 || R <= 0 || H <= 0 || H > 65535 || window < 1 || cap < window - 1 ||
-        cap < 1 || pos0 < 0 || !qkv || !kring || !vring || !out)
+        cap < 1 || (sl ? !pos_tab || !slot_tab : pos0 < 0) || !qkv || !kring || !vring || !out)
         return hipErrorInvalidValue;
     const size_t lds = (size_t)4 * window * sizeof(float);
     if (lds > 64 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(attention_stream_kernel, dim3((unsigned)((R + 3) / 4), (unsigned)H, (unsigned)batch), dim3(256),
-                       lds, s, qkv, kring, vring, out, R, H, window, cap, pos0, scale);
-    return hipGetLastError();
-}
-
-hipError_t launch_attention_stream_slots(const float* qkv, const float* kring, const float* vring, float* out,
-                                         int batch, int R, int H, int D, int window, int cap, const long long* pos_tab,
-                                         const int* slot_tab, float scale, hipStream_t s) {
-    if (D != 64 || batch <= 0 || batch > 65535 || R <= 0 || H <= 0 || H > 65535 || window < 1 || cap < window - 1 ||
-        cap < 1 || !pos_tab || !slot_tab || !qkv || !kring || !vring || !out)
-        return hipErrorInvalidValue;
-    const size_t lds = (size_t)4 * window * sizeof(float);
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(attention_stream_slots_kernel, dim3((unsigned)((R + 3) / 4), (unsigned)H, (unsigned)batch),
-                       dim3(256), lds, s, qkv, kring, vring, out, R, H, window, cap, pos_tab, slot_tab, scale);
+    const dim3 grid((unsigned)((R + 3) / 4), (unsigned)H, (unsigned)batch);
+    if (sl)
+        hipLaunchKernelGGL(attention_stream_slots_kernel, grid, dim3(256), lds, s, qkv, kring, vring, out, R, H, window,
+                           cap, pos_tab, slot_tab, scale);
+    else
+        hipLaunchKernelGGL(attention_stream_kernel, grid, dim3(256), lds, s, qkv, kring, vring, out, R, H, window, cap,
+                           pos0, scale);
+    if (kname) *kname = sl ? "mimi::attention_stream_slots_kernel" : "mimi::attention_stream_kernel";
     return hipGetLastError();
 }
 
@@ -198,28 +196,23 @@ __global__ __launch_bounds__(256) void attention_stream_append_slots_kernel(cons
 }
 
 hipError_t launch_attention_stream_append(const float* qkv, float* kring, float* vring, int batch, int R, int H, int D,
-                                          int cap, long long pos0, hipStream_t s) {
+                                          int cap, long long pos0, const long long* pos_tab, const int* slot_tab,
+                                          hipStream_t s, const char** kname) {
+    const bool sl = pos_tab || slot_tab;
     // R <= cap: no two rows of the step share a slot
-    if (D != 64 || batch <= 0 || R <= 0 || R > cap || H <= 0 || pos0 < 0 || !qkv || !kring || !vring)
+    if (D != 64 || batch <= 0 || R <= 0 || R > cap || H <= 0 || (sl ? !pos_tab || !slot_tab : pos0 < 0) || !qkv ||
+        !kring || !vring)
         return hipErrorInvalidValue;
     const long long total = (long long)batch * R * 2 * H * (D / 4);
     const long long blocks = (total + 255) / 256;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(attention_stream_append_kernel, dim3((unsigned)blocks), dim3(256), 0, s, qkv, kring, vring, batch,
-                       R, H, cap, pos0);
-    return hipGetLastError();
-}
-
-hipError_t launch_attention_stream_append_slots(const float* qkv, float* kring, float* vring, int batch, int R, int H,
-                                                int D, int cap, const long long* pos_tab, const int* slot_tab,
-                                                hipStream_t s) {
-    if (D != 64 || batch <= 0 || R <= 0 || R > cap || H <= 0 || !pos_tab || !slot_tab || !qkv || !kring || !vring)
-        return hipErrorInvalidValue;
-    const long long total = (long long)batch * R * 2 * H * (D / 4);
-    const long long blocks = (total + 255) / 256;
-    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(attention_stream_append_slots_kernel, dim3((unsigned)blocks), dim3(256), 0, s, qkv, kring, vring,
-                       batch, R, H, cap, pos_tab, slot_tab);
+    if (sl)
+        hipLaunchKernelGGL(attention_stream_append_slots_kernel, dim3((unsigned)blocks), dim3(256), 0, s, qkv, kring,
+                           vring, batch, R, H, cap, pos_tab, slot_tab);
+    else
+        hipLaunchKernelGGL(attention_stream_append_kernel, dim3((unsigned)blocks), dim3(256), 0, s, qkv, kring, vring,
+                           batch, R, H, cap, pos0);
+    if (kname) *kname = sl ? "mimi::attention_stream_append_slots_kernel" : "mimi::attention_stream_append_kernel";
     return hipGetLastError();
 }
 
@@ -247,7 +240,7 @@ __global__ __launch_bounds__(256) void stream_carry_slots_kernel(CarryTable t, c
     stream_carry_body<true>(t, slot_tab);
 }
 
-static hipError_t carry_grid(const CarryTable& t, int batch, dim3* grid) {
+hipError_t launch_stream_carry(const CarryTable& t, int batch, const int* slot_tab, hipStream_t s, const char** kname) {
     if (t.n < 1 || t.n > CARRY_MAX || batch <= 0 || batch > 65535) return hipErrorInvalidValue;
     int most = 0;
     for (int d = 0; d < t.n; ++d) {
@@ -258,24 +251,12 @@ static hipError_t carry_grid(const CarryTable& t, int batch, dim3* grid) {
         most = c.count > most ? c.count : most;
     }
     const int blocks = (most / 4 + 255) / 256;
-    *grid = dim3((unsigned)(blocks < 64 ? blocks : 64), (unsigned)batch, (unsigned)t.n);
-    return hipSuccess;
-}
-
-hipError_t launch_stream_carry(const CarryTable& t, int batch, hipStream_t s) {
-    dim3 grid;
-    const hipError_t err = carry_grid(t, batch, &grid);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(stream_carry_kernel, grid, dim3(256), 0, s, t);
-    return hipGetLastError();
-}
-
-hipError_t launch_stream_carry_slots(const CarryTable& t, int batch, const int* slot_tab, hipStream_t s) {
-    dim3 grid;
-    const hipError_t err = carry_grid(t, batch, &grid);
-    if (err != hipSuccess) return err;
-    if (!slot_tab) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(stream_carry_slots_kernel, grid, dim3(256), 0, s, t, slot_tab);
+    const dim3 grid((unsigned)(blocks < 64 ? blocks : 64), (unsigned)batch, (unsigned)t.n);
+    if (slot_tab)
+        hipLaunchKernelGGL(stream_carry_slots_kernel, grid, dim3(256), 0, s, t, slot_tab);
+    else
+        hipLaunchKernelGGL(stream_carry_kernel, grid, dim3(256), 0, s, t);
+    if (kname) *kname = slot_tab ? "mimi::stream_carry_slots_kernel" : "mimi::stream_carry_kernel";
     return hipGetLastError();
 }
 
@@ -314,31 +295,18 @@ __global__ __launch_bounds__(256) void stream_ds_rows_slots_kernel(const float* 
     stream_ds_rows_body<true>(src, dst, R, C, 0, pos_tab);
 }
 
-static hipError_t ds_rows_grid(const float* src, float* dst, int batch, int R, int C, dim3* grid) {
+hipError_t launch_stream_ds_rows(const float* src, float* dst, int batch, int R, int C, long long pos0,
+                                 const long long* pos_tab, hipStream_t s, const char** kname) {
     if (!src || !dst || batch <= 0 || batch > 65535 || R <= 0 || C <= 0 || C % 4 ||
-        (reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 16)
+        (reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 16 || (!pos_tab && pos0 < 0))
         return hipErrorInvalidValue;
     const long long blocks = ((long long)(2 + R) * (C / 4) + 255) / 256;
-    *grid = dim3((unsigned)(blocks < 64 ? blocks : 64), (unsigned)batch);
-    return hipSuccess;
-}
-
-hipError_t launch_stream_ds_rows(const float* src, float* dst, int batch, int R, int C, long long pos0, hipStream_t s) {
-    dim3 grid;
-    const hipError_t err = ds_rows_grid(src, dst, batch, R, C, &grid);
-    if (err != hipSuccess) return err;
-    if (pos0 < 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(stream_ds_rows_kernel, grid, dim3(256), 0, s, src, dst, R, C, pos0);
-    return hipGetLastError();
-}
-
-hipError_t launch_stream_ds_rows_slots(const float* src, float* dst, int batch, int R, int C, const long long* pos_tab,
-                                       hipStream_t s) {
-    dim3 grid;
-    const hipError_t err = ds_rows_grid(src, dst, batch, R, C, &grid);
-    if (err != hipSuccess) return err;
-    if (!pos_tab) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(stream_ds_rows_slots_kernel, grid, dim3(256), 0, s, src, dst, R, C, pos_tab);
+    const dim3 grid((unsigned)(blocks < 64 ? blocks : 64), (unsigned)batch);
+    if (pos_tab)
+        hipLaunchKernelGGL(stream_ds_rows_slots_kernel, grid, dim3(256), 0, s, src, dst, R, C, pos_tab);
+    else
+        hipLaunchKernelGGL(stream_ds_rows_kernel, grid, dim3(256), 0, s, src, dst, R, C, pos0);
+    if (kname) *kname = pos_tab ? "mimi::stream_ds_rows_slots_kernel" : "mimi::stream_ds_rows_kernel";
     return hipGetLastError();
 }
 

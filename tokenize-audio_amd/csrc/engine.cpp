@@ -1240,9 +1240,8 @@ struct Recorder {
     }
 };
 
-static int save_tap(mimi_engine* e, const char* name, const float* src, int64_t b, int64_t t, int64_t ch,
-                    hipStream_t s) {
-    if (!e->taps) return MIMI_OK;
+// the tap `name` as [b][t][ch] floats: its buffer grown to hold them, its dims set; *d = where the caller puts them
+static int tap_buffer(mimi_engine* e, const char* name, int64_t b, int64_t t, int64_t ch, float** d) {
     auto& tp = e->tapmap[name];
     const size_t n = (size_t)(b * t * ch);
     if (tp.cap < n) {
@@ -1250,10 +1249,20 @@ static int save_tap(mimi_engine* e, const char* name, const float* src, int64_t 
         HIP_TRY(hipMalloc(&tp.d, n * 4));
         tp.cap = n;
     }
-    HIP_TRY(hipMemcpyAsync(tp.d, src, n * 4, hipMemcpyDeviceToDevice, s));
     tp.dims[0] = b;
     tp.dims[1] = t;
     tp.dims[2] = ch;
+    *d = tp.d;
+    return MIMI_OK;
+}
+
+static int save_tap(mimi_engine* e, const char* name, const float* src, int64_t b, int64_t t, int64_t ch,
+                    hipStream_t s) {
+    if (!e->taps) return MIMI_OK;
+    float* d;
+    int rc;
+    if ((rc = tap_buffer(e, name, b, t, ch, &d))) return rc;
+    HIP_TRY(hipMemcpyAsync(d, src, (size_t)(b * t * ch) * 4, hipMemcpyDeviceToDevice, s));
     return MIMI_OK;
 }
 
@@ -1262,17 +1271,11 @@ static int save_tap_planes(mimi_engine* e, const char* name, const void* planes,
                            int64_t ch, hipStream_t s, float hscale = 0.0f) {
     if (!e->taps) return MIMI_OK;
     if (ns == 0) return save_tap(e, name, reinterpret_cast<const float*>(planes), b, t, ch, s);
-    auto& tp = e->tapmap[name];
-    const size_t n = (size_t)(b * t * ch);
-    if (tp.cap < n) {
-        if (tp.d) HIP_TRY(hipFree(tp.d));
-        HIP_TRY(hipMalloc(&tp.d, n * 4));
-        tp.cap = n;
-    }
-    HIP_TRY(launch_planes_to_f32(planes, (long long)n, ns, tp.d, (long long)n, s, hscale));
-    tp.dims[0] = b;
-    tp.dims[1] = t;
-    tp.dims[2] = ch;
+    float* d;
+    int rc;
+    if ((rc = tap_buffer(e, name, b, t, ch, &d))) return rc;
+    const long long n = b * t * ch;
+    HIP_TRY(launch_planes_to_f32(planes, n, ns, d, n, s, hscale));
     return MIMI_OK;
 }
 
@@ -3087,26 +3090,25 @@ extern "C" int mimi_rvq_decode(mimi_engine* e, const int32_t* dev_codes, int64_t
     return read_decode_flag(e, s);
 }
 
-// The decoder transformer: the encoder's fp32 launches (LayerNorm, q/k/v + RoPE, attention, o_proj, fc1, fc2) on the
-// weight set xf over the rows of L's stage 1 (B items, T = the longest item's rows), residual stream in t0 (in
-// place).  The flat-row stages run on all rows whatever the layout; q/k/v and attention run per item, a ragged
-// batch's from the tables (2 tlen[b] rows at 2 toff[b])
-static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, const DecLayout& L, float* t0, float* t1,
-                               float* qkv, float* att, float* ff, hipStream_t s, Recorder& rec, const char* stage_prefix) {
+// The fp32 transformer layer loop of the one-shot decode (uniform and ragged), the decode stream and the encode stream
+// (lock-step and slot steps): the encoder's fp32 launches (LayerNorm, q/k/v + RoPE, attention, o_proj, fc1, fc2) on the
+// weight set xf over `rows` flat rows, residual stream in t0 (in place), every stage recorded as stage_prefix + its
+// name and tapped as [tapB][tapT][C] under the encode pass's names ("qkv3").  What differs between the callers arrives
+// as two callables:
+//   qkv_args(x)   the GemmArgs of layer x's q/k/v GEMM (t1 -> qkv): how the rows are batched and which RoPE table
+//   attention(l)  everything between q/k/v and o_proj of layer l (qkv -> att), with its records
+template <class QkvArgs, class Attention>
+static int transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, float* t0, float* t1, float* qkv, float* att,
+                           float* ff, int64_t rows, int64_t tapB, int64_t tapT, const char* stage_prefix, Recorder& rec,
+                           hipStream_t s, QkvArgs qkv_args, Attention attention) {
     const mimi_config& c = e->cfg;
     const int Hd = c.hidden_size, H = c.num_attention_heads, Dh = c.head_dim;
-    const int B = L.B;
-    const int64_t T = L.len(1), rows = L.rows(1);
     const std::string sp = stage_prefix;
     const char* kname = "?";
     int rc;
-    // the per-layer taps, under the encode pass's names (a ragged pass's are packed, like its other taps)
     auto tap = [&](const char* stage, size_t l, const float* src, int C) {
-        return L.ragged ? save_tap_layer(e, stage, l, src, 1, rows, C, s) : save_tap_layer(e, stage, l, src, B, T, C, s);
+        return save_tap_layer(e, stage, l, src, tapB, tapT, C, s);
     };
-    double att_flops = 0;
-    for (int64_t i = 0; i < T; ++i) att_flops += 4.0 * Dh * std::min<int64_t>(i + 1, c.sliding_window);
-    att_flops *= (double)H * B;
     auto fl = [](const GemmArgs& a) { return 2.0 * a.batch * (double)a.M * a.N * a.K; };
     auto by = [](const GemmArgs& a, bool res) {
         return ((double)a.batch * a.M * (a.K + a.N * (res ? 2 : 1)) + (double)a.N * a.K) * 4;
@@ -3117,44 +3119,11 @@ static int run_transformer_f32(mimi_engine* e, const std::vector<DevXfmr>& xf, c
                                     nullptr, 0, e->ln_rpw),
                    "ln1");
         rec.mark(sp + "layernorm", 0, 2.0 * rows * Hd * 4, ln_kname(e->ln_rpw));
-        GemmArgs aq = linear_args(t1, T, Hd, x.wqkv, 3 * H * Dh, qkv);
-        aq.batch = B;
-        aq.a_bstride = T * Hd;
-        aq.c_bstride = T * 3 * H * Dh;
-        aq.rope_cos = e->rope_cos;
-        aq.rope_sin = e->rope_sin;
-        aq.rope_cols = 2 * H * Dh;
-        // ragged, per item: rows, zero padding and RoPE position relative to the item's first row
-        aq.a_rows = aq.m_rows = L.tlen(1);
-        aq.a_boff = aq.c_boff = L.toff(1);
+        const GemmArgs aq = qkv_args(x);
         LAUNCH_TRY(launch_gemm(ROLE_QKV, aq, s, &kname, PREC_F32), "qkv");
         rec.mark(sp + "qkv", fl(aq), by(aq, false), kname);
         if ((rc = tap("qkv", l, qkv, 3 * H * Dh))) return rc;
-        const char* akn = T <= 256 ? "mimi::attention_t256_kernel" : "mimi::attention_kernel";
-        if (L.ragged) {
-            // each item the kernel it would run alone: one launch per regime present (and one record each), each
-            // kernel exiting on the other's items
-            const int lo = (int)(2 * L.minT), hi = (int)(2 * L.maxT);
-            const float sc = 1.0f / std::sqrt((float)Dh);
-            if (lo <= 256) {
-                LAUNCH_TRY(launch_attention(qkv, att, B, 0, H, Dh, c.sliding_window, sc, s, nullptr, 0, 0, 0.0f, nullptr,
-                                            false, L.tlen(1), std::min(hi, 256), lo, L.toff(1), &akn),
-                           "attention");
-                rec.mark(sp + "attention", att_flops, (double)rows * 4 * Hd * 4, akn);
-            }
-            if (hi > 256) {
-                LAUNCH_TRY(launch_attention(qkv, att, B, 0, H, Dh, c.sliding_window, sc, s, nullptr, 0, 0, 0.0f, nullptr,
-                                            false, L.tlen(1), hi, std::max(lo, 257), L.toff(1), &akn),
-                           "attention");
-                rec.mark(sp + "attention", att_flops, (double)rows * 4 * Hd * 4, akn);
-            }
-        } else {
-            LAUNCH_TRY(launch_attention(qkv, att, B, (int)T, H, Dh, c.sliding_window, 1.0f / std::sqrt((float)Dh), s, att,
-                                        rows * Hd, 0, 0.0f, nullptr, false, nullptr, 0, 0, nullptr, &akn,
-                                        e->attn_band_split),
-                       "attention");
-            rec.mark(sp + "attention", att_flops, (double)rows * 4 * Hd * 4, akn);
-        }
+        if ((rc = attention(l))) return rc;
         if ((rc = tap("att", l, att, H * Dh))) return rc;
         GemmArgs ao = linear_args(att, rows, H * Dh, x.wo, Hd, t0);
         ao.R = t0;
@@ -3224,7 +3193,60 @@ static int decode_pass(mimi_engine* e, const int32_t* dev_codes, const DecLayout
     if ((rc = tap("upsample", t0, 1, Hd))) return rc;
 
     // ---- decoder transformer ----
-    if ((rc = run_transformer_f32(e, e->dxf, L, t0, t1, qkv, att, ff, s, rec, "dec_"))) return rc;  // (taps inside)
+    // The flat-row stages run on all rows whatever the layout; q/k/v and attention run per item (T = the longest
+    // item's rows), a ragged batch's from the tables (2 tlen[b] rows at 2 toff[b]).  A ragged pass's taps are packed.
+    {
+        const int H = c.num_attention_heads, Dh = c.head_dim;
+        const int64_t T = L.len(1), rows = L.rows(1);
+        auto qkv_args = [&](const DevXfmr& x) {
+            GemmArgs aq = linear_args(t1, T, Hd, x.wqkv, 3 * H * Dh, qkv);
+            aq.batch = B;
+            aq.a_bstride = T * Hd;
+            aq.c_bstride = T * 3 * H * Dh;
+            aq.rope_cos = e->rope_cos;
+            aq.rope_sin = e->rope_sin;
+            aq.rope_cols = 2 * H * Dh;
+            // ragged, per item: rows, zero padding and RoPE position relative to the item's first row
+            aq.a_rows = aq.m_rows = L.tlen(1);
+            aq.a_boff = aq.c_boff = L.toff(1);
+            return aq;
+        };
+        double att_flops = 0;
+        for (int64_t i = 0; i < T; ++i) att_flops += 4.0 * Dh * std::min<int64_t>(i + 1, c.sliding_window);
+        att_flops *= (double)H * B;
+        const float sc = 1.0f / std::sqrt((float)Dh);
+        const char* akn = T <= 256 ? "mimi::attention_t256_kernel" : "mimi::attention_kernel";
+        auto att_mark = [&] { rec.mark("dec_attention", att_flops, (double)rows * 4 * Hd * 4, akn); };
+        auto attention = [&](size_t) {
+            LAUNCH_TRY(launch_attention(qkv, att, B, (int)T, H, Dh, c.sliding_window, sc, s, att, rows * Hd, 0, 0.0f,
+                                        nullptr, false, nullptr, 0, 0, nullptr, &akn, e->attn_band_split),
+                       "attention");
+            att_mark();
+            return (int)MIMI_OK;
+        };
+        // each item the kernel it would run alone: one launch per 256-row regime present (and one record each), each
+        // kernel exiting on the other's items
+        const int lo = (int)(2 * L.minT), hi = (int)(2 * L.maxT);
+        auto attention_ragged = [&](size_t) {
+            if (lo <= 256) {
+                LAUNCH_TRY(launch_attention(qkv, att, B, 0, H, Dh, c.sliding_window, sc, s, nullptr, 0, 0, 0.0f, nullptr,
+                                            false, L.tlen(1), std::min(hi, 256), lo, L.toff(1), &akn),
+                           "attention");
+                att_mark();
+            }
+            if (hi > 256) {
+                LAUNCH_TRY(launch_attention(qkv, att, B, 0, H, Dh, c.sliding_window, sc, s, nullptr, 0, 0, 0.0f, nullptr,
+                                            false, L.tlen(1), hi, std::max(lo, 257), L.toff(1), &akn),
+                           "attention");
+                att_mark();
+            }
+            return (int)MIMI_OK;
+        };
+        rc = L.ragged ? transformer_f32(e, e->dxf, t0, t1, qkv, att, ff, rows, 1, rows, "dec_", rec, s, qkv_args,
+                                        attention_ragged)
+                      : transformer_f32(e, e->dxf, t0, t1, qkv, att, ff, rows, B, T, "dec_", rec, s, qkv_args, attention);
+        if (rc) return rc;
+    }
     char nm[64];
 
     // ---- SEANet decoder ----
@@ -3313,23 +3335,16 @@ extern "C" int64_t mimi_decode_ragged_workspace_bytes(const mimi_engine* e, cons
 static int save_tap_audio_ragged(mimi_engine* e, const float* audio, const int64_t* lengths, const DecLayout& L,
                                  hipStream_t s) {
     if (!e->taps) return MIMI_OK;
-    auto& tp = e->tapmap["audio"];
     const int64_t up = L.f.back();
-    const size_t n = (size_t)(up * L.sumT);
-    if (tp.cap < n) {
-        if (tp.d) HIP_TRY(hipFree(tp.d));
-        HIP_TRY(hipMalloc(&tp.d, n * 4));
-        tp.cap = n;
-    }
+    float* d;
+    int rc;
+    if ((rc = tap_buffer(e, "audio", 1, up * L.sumT, 1, &d))) return rc;
     int64_t off = 0;
     for (int b = 0; b < L.B; ++b) {
-        HIP_TRY(hipMemcpyAsync(tp.d + up * off, audio + (size_t)b * (up * L.stride), (size_t)(up * lengths[b]) * 4,
+        HIP_TRY(hipMemcpyAsync(d + up * off, audio + (size_t)b * (up * L.stride), (size_t)(up * lengths[b]) * 4,
                                hipMemcpyDeviceToDevice, s));
         off += lengths[b];
     }
-    tp.dims[0] = 1;
-    tp.dims[1] = (int64_t)n;
-    tp.dims[2] = 1;
     return MIMI_OK;
 }
 
@@ -3545,8 +3560,12 @@ static int stream_reset_one(StreamBase* st, const char* what, int32_t slot) {
     return MIMI_OK;
 }
 
-static bool stream_in_lock_step(const StreamBase* st) {
-    return std::all_of(st->pos.begin(), st->pos.end(), [&](int64_t p) { return p == st->pos[0]; });
+// The slot list of a step over all of the stream's slots: nullptr while they all stand at one position (the lock-step
+// pass), otherwise 0 .. B - 1 (a slot step), kept in *all.
+static const int32_t* stream_all_slots(const StreamBase* st, std::vector<int32_t>* all) {
+    if (std::all_of(st->pos.begin(), st->pos.end(), [&](int64_t p) { return p == st->pos[0]; })) return nullptr;
+    for (int b = 0; b < st->B; ++b) all->push_back(b);
+    return all->data();
 }
 
 // the arguments of a slot step (the pointers apart): every table index is checked here -- the kernels index the rings
@@ -3618,6 +3637,18 @@ static int stream_step_upload(StreamBase* st, const int32_t* slots, int m, int n
                                hipMemcpyHostToDevice, s));
     }
     return MIMI_OK;
+}
+
+// the device tables of a step as the stream kernels' launchers take them: a slot step's, or nullptr for the lock-step
+// kernels
+struct StreamTabs {
+    const long long* pos;
+    const int* slot;
+};
+static StreamTabs stream_tabs(const StreamBase* st, bool slots) {
+    if (!slots) return {nullptr, nullptr};
+    return {reinterpret_cast<const long long*>(st->tab_dev),
+            reinterpret_cast<const int*>(st->tab_dev + (size_t)st->B * sizeof(int64_t))};
 }
 
 static void stream_step_done(StreamBase* st, const int32_t* slots, int m, int n) {
@@ -3734,114 +3765,62 @@ static int save_tap_strided(mimi_engine* e, const char* name, const float* src, 
                             int64_t bstride, hipStream_t s) {
     if (!e->taps) return MIMI_OK;
     if (bstride == rows * ch) return save_tap(e, name, src, b, rows, ch, s);
-    auto& tp = e->tapmap[name];
-    const size_t n = (size_t)(b * rows * ch);
-    if (tp.cap < n) {
-        if (tp.d) HIP_TRY(hipFree(tp.d));
-        HIP_TRY(hipMalloc(&tp.d, n * 4));
-        tp.cap = n;
-    }
-    HIP_TRY(hipMemcpy2DAsync(tp.d, (size_t)(rows * ch) * 4, src, (size_t)bstride * 4, (size_t)(rows * ch) * 4, (size_t)b,
+    float* d;
+    int rc;
+    if ((rc = tap_buffer(e, name, b, rows, ch, &d))) return rc;
+    HIP_TRY(hipMemcpy2DAsync(d, (size_t)(rows * ch) * 4, src, (size_t)bstride * 4, (size_t)(rows * ch) * 4, (size_t)b,
                              hipMemcpyDeviceToDevice, s));
-    tp.dims[0] = b;
-    tp.dims[1] = rows;
-    tp.dims[2] = ch;
     return MIMI_OK;
 }
 
-// The transformer section of a stream step, shared by the decode stream (xf = the decoder's layers, stage names
-// "dec_...") and the encode stream (the encoder's, "encs_..."): run_transformer_f32's launches with the stream's RoPE rows
-// and the attention on the stream's rings.  x in w.t0, the result in w.t0.  slots: the slot forms (sx.pos_tab / slot_tab);
-// pos0: per item (lock-step: [0] for all) the frame its first row belongs to.
-struct StreamXf {
-    const float *rope_cos, *rope_sin;
-    float *kring, *vring;
-    size_t ring_layer;
-    int cap;
-    const long long* pos_tab;
-    const int* slot_tab;
-};
-struct StreamXfWs {
-    float *t0, *t1, *qkv, *att, *ff;
-};
-static int stream_transformer(mimi_engine* e, const std::vector<DevXfmr>& xf, const StreamXf& sx, const StreamXfWs& w,
-                              int B, int R, bool slots, const int64_t* pos0, const char* prefix, Recorder& rec,
-                              hipStream_t s) {
-    const mimi_config& c = e->cfg;
-    const int Hd = c.hidden_size, H = c.num_attention_heads, Dh = c.head_dim;
-    const int64_t P = 2 * pos0[0];  // lock-step: the absolute 25 Hz row of the step's first
-    const std::string pre(prefix);
-    const char* kname = "?";
-    int rc;
-    const int64_t frows = (int64_t)B * R;
-    auto fl = [](const GemmArgs& a) { return 2.0 * a.batch * (double)a.M * a.N * a.K; };
-    auto by = [](const GemmArgs& a, bool res) {
-        return ((double)a.batch * a.M * (a.K + a.N * (res ? 2 : 1)) + (double)a.N * a.K) * 4;
-    };
-    double att_flops = 0;
-    for (int b = 0; b < (slots ? B : 1); ++b)
-        for (int i = 0; i < R; ++i)
-            att_flops += 4.0 * Dh * std::min<int64_t>(2 * pos0[b] + i + 1, c.sliding_window);
-    att_flops *= (double)H * (slots ? 1 : B);
-    for (size_t l = 0; l < xf.size(); ++l) {
-        const DevXfmr& x = xf[l];
-        LAUNCH_TRY(launch_layernorm(w.t0, x.ln1_w, x.ln1_b, w.t1, frows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f,
-                                    nullptr, nullptr, 0, e->ln_rpw),
-                   "ln1");
-        rec.mark(pre + "layernorm", 0, 2.0 * frows * Hd * 4, ln_kname(e->ln_rpw));
-        // lock-step: batched, row m of an item is absolute row P + m and the tables hold rows P ..; slots: the flat
-        // rows, the tables hold every item's rows in step order
-        GemmArgs aq = linear_args(w.t1, slots ? frows : R, Hd, x.wqkv, 3 * H * Dh, w.qkv);
+// The two callables that make transformer_f32 the transformer section of a stream step, decode or encode: B items of
+// R rows each, the step's RoPE rows in the stream's tables, the attention on the stream's rings.  pos_tab / slot_tab:
+// the slot step's device tables, both nullptr in lock-step; pos0: per item (lock-step: [0] for all) the frame its first
+// row belongs to.
+// q/k/v.  Lock-step: batched, row m of an item is absolute row P + m and the tables hold rows P ..; slots: the flat
+// rows, the tables hold every item's rows in step order
+static auto stream_qkv_args(const StreamBase* st, const float* t1, float* qkv, int B, int R, bool slots) {
+    const mimi_config& c = st->e->cfg;
+    const int Hd = c.hidden_size, HD = c.num_attention_heads * c.head_dim;
+    return [=](const DevXfmr& x) {
+        GemmArgs aq = linear_args(t1, slots ? (int64_t)B * R : R, Hd, x.wqkv, 3 * HD, qkv);
         if (!slots) {
             aq.batch = B;
             aq.a_bstride = (int64_t)R * Hd;
-            aq.c_bstride = (int64_t)R * 3 * H * Dh;
+            aq.c_bstride = (int64_t)R * 3 * HD;
         }
-        aq.rope_cos = sx.rope_cos;
-        aq.rope_sin = sx.rope_sin;
-        aq.rope_cols = 2 * H * Dh;
-        LAUNCH_TRY(launch_gemm(ROLE_QKV, aq, s, &kname, PREC_F32), "qkv");
-        rec.mark(pre + "qkv", fl(aq), by(aq, false), kname);
-        if ((rc = save_tap_layer(e, "qkv", l, w.qkv, B, R, 3 * H * Dh, s))) return rc;
-        float* kr = sx.kring + l * sx.ring_layer;
-        float* vr = sx.vring + l * sx.ring_layer;
-        const float qscale = 1.0f / std::sqrt((float)Dh);
-        LAUNCH_TRY(slots ? launch_attention_stream_slots(w.qkv, kr, vr, w.att, B, R, H, Dh, c.sliding_window, sx.cap,
-                                                         sx.pos_tab, sx.slot_tab, qscale, s)
-                         : launch_attention_stream(w.qkv, kr, vr, w.att, B, R, H, Dh, c.sliding_window, sx.cap, P,
-                                                   qscale, s),
+        aq.rope_cos = st->rope_cos;
+        aq.rope_sin = st->rope_sin;
+        aq.rope_cols = 2 * HD;
+        return aq;
+    };
+}
+// the attention on the rings, then the step's k / v rows into them
+static auto stream_attention(const StreamBase* st, const float* qkv, float* att, int B, int R, const int64_t* pos0,
+                             const long long* pos_tab, const int* slot_tab, const char* prefix, Recorder& rec,
+                             hipStream_t s) {
+    const mimi_config& c = st->e->cfg;
+    const int Hd = c.hidden_size, H = c.num_attention_heads, Dh = c.head_dim, W = c.sliding_window;
+    const int64_t P = 2 * pos0[0];  // lock-step: the absolute 25 Hz row of the step's first
+    const int64_t frows = (int64_t)B * R;
+    double att_flops = 0;
+    for (int b = 0; b < (pos_tab ? B : 1); ++b)
+        for (int i = 0; i < R; ++i) att_flops += 4.0 * Dh * std::min<int64_t>(2 * pos0[b] + i + 1, W);
+    att_flops *= (double)H * (pos_tab ? 1 : B);
+    const std::string pre(prefix);
+    return [=, &rec](size_t l) {
+        float* kr = st->kring + l * st->ring_layer;
+        float* vr = st->vring + l * st->ring_layer;
+        const char* kname = "?";
+        LAUNCH_TRY(launch_attention_stream(qkv, kr, vr, att, B, R, H, Dh, W, st->cap, P, pos_tab, slot_tab,
+                                           1.0f / std::sqrt((float)Dh), s, &kname),
                    "attention (stream)");
-        rec.mark(pre + "attention", att_flops, (double)frows * 4 * Hd * 4,
-                 slots ? "mimi::attention_stream_slots_kernel" : "mimi::attention_stream_kernel");
-        if ((rc = save_tap_layer(e, "att", l, w.att, B, R, H * Dh, s))) return rc;
-        LAUNCH_TRY(slots ? launch_attention_stream_append_slots(w.qkv, kr, vr, B, R, H, Dh, sx.cap, sx.pos_tab,
-                                                                sx.slot_tab, s)
-                         : launch_attention_stream_append(w.qkv, kr, vr, B, R, H, Dh, sx.cap, P, s),
+        rec.mark(pre + "attention", att_flops, (double)frows * 4 * Hd * 4, kname);
+        LAUNCH_TRY(launch_attention_stream_append(qkv, kr, vr, B, R, H, Dh, st->cap, P, pos_tab, slot_tab, s, &kname),
                    "kv append");
-        rec.mark(pre + "kv_append", 0, (double)frows * 4 * H * Dh * 4,
-                 slots ? "mimi::attention_stream_append_slots_kernel" : "mimi::attention_stream_append_kernel");
-        GemmArgs ao = linear_args(w.att, frows, H * Dh, x.wo, Hd, w.t0);
-        ao.R = w.t0;
-        ao.scale = x.ls1;
-        LAUNCH_TRY(launch_gemm(ROLE_OPROJ, ao, s, &kname, PREC_F32), "o_proj");
-        rec.mark(pre + "o_proj", fl(ao), by(ao, true), kname);
-        if ((rc = save_tap_layer(e, "oproj", l, w.t0, B, R, Hd, s))) return rc;
-        LAUNCH_TRY(launch_layernorm(w.t0, x.ln2_w, x.ln2_b, w.t1, frows, Hd, c.norm_eps, s, nullptr, 0, 0, 0.0f,
-                                    nullptr, nullptr, 0, e->ln_rpw),
-                   "ln2");
-        rec.mark(pre + "layernorm", 0, 2.0 * frows * Hd * 4, ln_kname(e->ln_rpw));
-        GemmArgs a1 = linear_args(w.t1, frows, Hd, x.w1, c.intermediate_size, w.ff);
-        LAUNCH_TRY(launch_gemm(ROLE_FC1, a1, s, &kname, PREC_F32), "fc1");
-        rec.mark(pre + "fc1", fl(a1), by(a1, false), kname);
-        if ((rc = save_tap_layer(e, "ff", l, w.ff, B, R, c.intermediate_size, s))) return rc;
-        GemmArgs a2 = linear_args(w.ff, frows, c.intermediate_size, x.w2, Hd, w.t0);
-        a2.R = w.t0;
-        a2.scale = x.ls2;
-        LAUNCH_TRY(launch_gemm(ROLE_FC2, a2, s, &kname, PREC_F32), "fc2");
-        rec.mark(pre + "fc2", fl(a2), by(a2, true), kname);
-        if ((rc = save_tap_layer(e, "xfmr", l, w.t0, B, R, Hd, s))) return rc;
-    }
-    return MIMI_OK;
+        rec.mark(pre + "kv_append", 0, (double)frows * 4 * H * Dh * 4, kname);
+        return (int)MIMI_OK;
+    };
 }
 
 // the launches of one step over B items (the workspace w sized for it, the step's RoPE rows already enqueued).
@@ -3853,17 +3832,13 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
     const mimi_config& c = e->cfg;
     const int K = st->K, Hd = c.hidden_size, Dq = c.vq_hidden_dim;
     const int R = 2 * n, H0 = c.kernel_size - 1, HL = c.last_kernel_size - 1;
-    const long long* pos_tab = reinterpret_cast<const long long*>(st->tab_dev);
-    const int* slot_tab = reinterpret_cast<const int*>(st->tab_dev + (size_t)st->B * sizeof(int64_t));
-    const char* carry_kn = slots ? "mimi::stream_carry_slots_kernel" : "mimi::stream_carry_kernel";
-    auto carry = [&](const CarryTable& t) {
-        return slots ? launch_stream_carry_slots(t, B, slot_tab, s) : launch_stream_carry(t, B, s);
-    };
+    const StreamTabs tabs = stream_tabs(st, slots != nullptr);
+    const char* kname = "?";
+    auto carry = [&](const CarryTable& t) { return launch_stream_carry(t, B, tabs.slot, s, &kname); };
     int rc;
     HIP_TRY(hipMemsetAsync(e->dec_flag, 0, sizeof(unsigned), s));
     Recorder rec{e, s};
     rec.begin();
-    const char* kname = "?";
     char nm[64];
     // where each carry's rows sit in the workspace, in the order of stream_carry_plan: in front of the item's chunk
     std::vector<float*> where = {w.emb, w.xin};
@@ -3888,7 +3863,7 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
     }
     in.n = outc.n = (int)where.size();
     LAUNCH_TRY(carry(in), "stream carry (in)");
-    rec.mark("dec_carry", 0, 0, carry_kn);
+    rec.mark("dec_carry", 0, 0, kname);
 
     // ---- quantizer.decode + upsample ----
     LAUNCH_TRY(launch_rvq_decode(dev_codes, (long long)B * n, n, K, c.num_semantic_quantizers, c.codebook_size,
@@ -3907,18 +3882,17 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
     rec.mark("dec_upsample", 4.0 * B * R * Hd, 3.0 * B * n * Hd * 4, "mimi::upsample_dw_hist_kernel");
     if ((rc = save_tap(e, "upsample", w.t0, B, R, Hd, s))) return rc;
 
-    // ---- decoder transformer: run_transformer_f32's launches with the stream's RoPE rows and ring attention ----
-    {
-        const StreamXf sx{st->rope_cos, st->rope_sin, st->kring, st->vring, st->ring_layer, st->cap, pos_tab, slot_tab};
-        const StreamXfWs xw{w.t0, w.t1, w.qkv, w.att, w.ff};
-        if ((rc = stream_transformer(e, e->dxf, sx, xw, B, R, slots != nullptr, pos0, "dec_", rec, s))) return rc;
-    }
+    // ---- decoder transformer with the stream's RoPE rows and ring attention ----
+    if ((rc = transformer_f32(e, e->dxf, w.t0, w.t1, w.qkv, w.att, w.ff, (int64_t)B * R, B, R, "dec_", rec, s,
+                              stream_qkv_args(st, w.t1, w.qkv, B, R, slots != nullptr),
+                              stream_attention(st, w.qkv, w.att, B, R, pos0, tabs.pos, tabs.slot, "dec_", rec, s))))
+        return rc;
     {  // the transformer's flat rows behind decoder.layers.0's carry
         CarryTable mv{};
         mv.c[0] = {w.t0, w.xin + (int64_t)H0 * Hd, (int64_t)R * Hd, (int64_t)(H0 + R) * Hd, R * Hd};
         mv.n = 1;
         LAUNCH_TRY(carry(mv), "stream carry (transformer rows)");  // (no state side: by the item's place either way)
-        rec.mark("dec_carry", 0, 2.0 * B * R * Hd * 4, carry_kn);
+        rec.mark("dec_carry", 0, 2.0 * B * R * Hd * 4, kname);
     }
 
     // ---- SEANet decoder ----
@@ -3981,7 +3955,7 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
     rec.mark("dec_final", 2.0 * B * len * C * c.last_kernel_size, (double)B * len * (C + 1) * 4,
              "mimi::final_conv_hist_kernel");
     LAUNCH_TRY(carry(outc), "stream carry (out)");
-    rec.mark("dec_carry", 0, 0, carry_kn);
+    rec.mark("dec_carry", 0, 0, kname);
     return MIMI_OK;
 }
 
@@ -4018,11 +3992,8 @@ extern "C" int mimi_decode_stream_step(mimi_decode_stream* st, const int32_t* de
     if (n < 1 || n > st->max_n || !dev_codes || !dev_audio)
         return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream step of %d frames outside [1, %d]", n, st->max_n);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    // all slots at one position: the lock-step pass; otherwise a slot step over 0 .. B - 1
-    if (stream_in_lock_step(st)) return stream_step_locked(st, nullptr, st->B, dev_codes, n, dev_audio, s);
-    std::vector<int32_t> all(st->B);
-    for (int b = 0; b < st->B; ++b) all[b] = b;
-    return stream_step_locked(st, all.data(), st->B, dev_codes, n, dev_audio, s);
+    std::vector<int32_t> all;
+    return stream_step_locked(st, stream_all_slots(st, &all), st->B, dev_codes, n, dev_audio, s);
 }
 
 extern "C" int mimi_decode_stream_step_slots(mimi_decode_stream* st, const int32_t* slots, int32_t m,
@@ -4058,7 +4029,7 @@ extern "C" int mimi_decode_stream_step_slots(mimi_decode_stream* st, const int32
 // engine mutex, every step synchronises its stream before it returns), on fp32 MFMA whatever mimi_set_precision says:
 // no activation scales, no calibration, no lanes, no graphs.  Layout and carries as in the decode stream: every stage's
 // tensor is per item [H carry rows | the chunk's rows]; one carry launch in front, one at the end.  The transformer
-// section is stream_transformer, shared with the decode stream; the RVQ runs the per-level kernels (the persistent
+// section is transformer_f32 with the decode stream's callables; the RVQ runs the per-level kernels (the persistent
 // chain needs its give-up flag read back: off here).  Slots as in the decode stream: what touches the state is
 // indirected through slot_tab / pos_tab (the carry kernel, the attention and the append), the downsample fill reads
 // pos_tab by the item's place, everything else works on the workspace by the item's place in the step.
@@ -4218,16 +4189,12 @@ static int encode_stream_pass(mimi_encode_stream* st, const float* dev_audio, in
     const int R = 2 * n, HR = c.residual_kernel_size - 1, HL = c.last_kernel_size - 1;
     const int HD = c.downsample_kernel - c.downsample_stride;
     const int64_t L = st->F * n;
-    const long long* pos_tab = reinterpret_cast<const long long*>(st->tab_dev);
-    const int* slot_tab = reinterpret_cast<const int*>(st->tab_dev + (size_t)st->B * sizeof(int64_t));
-    const char* carry_kn = slots ? "mimi::stream_carry_slots_kernel" : "mimi::stream_carry_kernel";
-    auto carry = [&](const CarryTable& t) {
-        return slots ? launch_stream_carry_slots(t, B, slot_tab, s) : launch_stream_carry(t, B, s);
-    };
+    const StreamTabs tabs = stream_tabs(st, slots != nullptr);
+    const char* kname = "?";
+    auto carry = [&](const CarryTable& t) { return launch_stream_carry(t, B, tabs.slot, s, &kname); };
     int rc;
     Recorder rec{e, s};
     rec.begin();
-    const char* kname = "?";
     char nm[64];
     // where each carry's rows sit in the workspace, in the order of enc_stream_carry_plan: in front of the item's chunk
     // (conv 0's apart: in from a_hist, out from a_tail, which conv0_hist_kernel fills)
@@ -4259,7 +4226,7 @@ static int encode_stream_pass(mimi_encode_stream* st, const float* dev_audio, in
     }
     in.n = outc.n = (int)where.size();
     LAUNCH_TRY(carry(in), "encode stream carry (in)");
-    rec.mark("encs_carry", 0, 0, carry_kn);
+    rec.mark("encs_carry", 0, 0, kname);
 
     // ---- SEANet encoder ----
     int C = c.num_filters;
@@ -4323,17 +4290,13 @@ static int encode_stream_pass(mimi_encode_stream* st, const float* dev_audio, in
     if ((rc = save_tap(e, "encoder", w.t0, B, R, Hd, s))) return rc;
 
     // ---- encoder transformer on the stream's rings ----
-    {
-        const StreamXf sx{st->rope_cos, st->rope_sin, st->kring, st->vring, st->ring_layer, st->cap, pos_tab, slot_tab};
-        const StreamXfWs xw{w.t0, w.t1, w.qkv, w.att, w.ff};
-        if ((rc = stream_transformer(e, e->xf, sx, xw, B, R, slots != nullptr, pos0, "encs_", rec, s))) return rc;
-    }
+    if ((rc = transformer_f32(e, e->xf, w.t0, w.t1, w.qkv, w.att, w.ff, (int64_t)B * R, B, R, "encs_", rec, s,
+                              stream_qkv_args(st, w.t1, w.qkv, B, R, slots != nullptr),
+                              stream_attention(st, w.qkv, w.att, B, R, pos0, tabs.pos, tabs.slot, "encs_", rec, s))))
+        return rc;
     // ---- downsample behind its carry (a slot at position 0: two copies of its first row) + projections + RVQ ----
-    LAUNCH_TRY(slots ? launch_stream_ds_rows_slots(w.t0, w.dsin, B, R, Hd, pos_tab, s)
-                     : launch_stream_ds_rows(w.t0, w.dsin, B, R, Hd, 2 * pos0[0], s),
-               "downsample rows");
-    rec.mark("encs_ds_rows", 0, 2.0 * B * R * Hd * 4,
-             slots ? "mimi::stream_ds_rows_slots_kernel" : "mimi::stream_ds_rows_kernel");
+    LAUNCH_TRY(launch_stream_ds_rows(w.t0, w.dsin, B, R, Hd, 2 * pos0[0], tabs.pos, s, &kname), "downsample rows");
+    rec.mark("encs_ds_rows", 0, 2.0 * B * R * Hd * 4, kname);
     GemmArgs ad = conv(e->ds, w.dsin, HD, R, w.dsout, n, (int64_t)n * Hd);
     LAUNCH_TRY(launch_gemm(ROLE_DOWNSAMPLE, ad, s, &kname, PREC_F32), "downsample");
     rec.mark("encs_downsample", fl(ad), by(ad), kname);
@@ -4366,7 +4329,7 @@ static int encode_stream_pass(mimi_encode_stream* st, const float* dev_audio, in
         rec.mark("encs_rvq", 2.0 * B * n * r.D * r.ncodes * K, (double)B * n * (2 * r.D + K) * 4, kname);
     }
     LAUNCH_TRY(carry(outc), "encode stream carry (out)");
-    rec.mark("encs_carry", 0, 0, carry_kn);
+    rec.mark("encs_carry", 0, 0, kname);
     return MIMI_OK;
 }
 
@@ -4402,11 +4365,8 @@ extern "C" int mimi_encode_stream_step(mimi_encode_stream* st, const float* dev_
     if (n < 1 || n > st->max_n)
         return set_err(MIMI_ERR_INVALID_ARGUMENT, "encode stream step of %d frames outside [1, %d]", n, st->max_n);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    // all slots at one position: the lock-step pass; otherwise a slot step over 0 .. B - 1
-    if (stream_in_lock_step(st)) return encode_stream_step_locked(st, nullptr, st->B, dev_audio, n, dev_codes, s);
-    std::vector<int32_t> all(st->B);
-    for (int b = 0; b < st->B; ++b) all[b] = b;
-    return encode_stream_step_locked(st, all.data(), st->B, dev_audio, n, dev_codes, s);
+    std::vector<int32_t> all;
+    return encode_stream_step_locked(st, stream_all_slots(st, &all), st->B, dev_audio, n, dev_codes, s);
 }
 
 extern "C" int mimi_encode_stream_step_slots(mimi_encode_stream* st, const int32_t* slots, int32_t m,

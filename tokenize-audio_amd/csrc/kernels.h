@@ -493,29 +493,29 @@ hipError_t launch_upsample_dw_hist(const float* x, const float* w, float* y, int
 hipError_t launch_final_conv_hist(const float* x, const float* w, const float* bias, float* y, int batch, long long L,
                                   int C, int ksize, long long x_bstride, hipStream_t s);
 
-// Streamed decode (attn_stream.hip).
+// Streamed decode (attn_stream.hip).  Each launcher serves both forms of its kernel body: with null tables the
+// lock-step kernel (every item's first row is absolute row pos0 >= 0, item b's rings and carries are b's), with
+// non-null tables the slot kernel (a step over a subset of a stream's slots, each at its own position: item b of the
+// step, b < batch, is slot slot_tab[b] of the rings / carries and its first row is absolute row pos_tab[b]; device
+// tables of `batch` entries, the caller has checked every slot against the state's item count and every position
+// >= 0; pos0 is not read).  The step's own rows and `out` stay indexed by b.  Same body, same orders: a row's bits in
+// the slot form are those of the lock-step form at pos0 = pos_tab[b].  *kname (if given) receives the launched
+// kernel's name, "mimi::<kernel>_kernel" or "mimi::<kernel>_slots_kernel".
 // attention_stream_kernel: the step's R query rows per (item, head) at absolute rows pos0 .. pos0 + R - 1 against the
 // keys / values of rows (row - window, row]: rows >= pos0 from the step's own fused qkv [B][R][3 H 64] (q, k rotated),
 // older ones from the ring ([B][H][cap][64] each for k and v, row r in slot r % cap).  fp32; out [B][R][H 64].
+// pos_tab and slot_tab: both or neither.
 hipError_t launch_attention_stream(const float* qkv, const float* kring, const float* vring, float* out, int batch,
-                                   int R, int H, int D, int window, int cap, long long pos0, float scale, hipStream_t s);
+                                   int R, int H, int D, int window, int cap, long long pos0, const long long* pos_tab,
+                                   const int* slot_tab, float scale, hipStream_t s, const char** kname = nullptr);
 // the step's k / v rows into their ring slots (after the attention that may still read the rows they replace)
 hipError_t launch_attention_stream_append(const float* qkv, float* kring, float* vring, int batch, int R, int H, int D,
-                                          int cap, long long pos0, hipStream_t s);
-// Slot forms (a step over a subset of a stream's slots, each at its own position): item b of the step, b < batch, is
-// slot slot_tab[b] of the rings and its first row is absolute row pos_tab[b] (device tables of `batch` entries; the
-// caller has checked every slot against the rings' item count and every position >= 0).  The step's own rows and
-// `out` stay indexed by b.  Same body, same orders: a row's bits are those of the forms above at pos0 = pos_tab[b].
-hipError_t launch_attention_stream_slots(const float* qkv, const float* kring, const float* vring, float* out,
-                                         int batch, int R, int H, int D, int window, int cap, const long long* pos_tab,
-                                         const int* slot_tab, float scale, hipStream_t s);
-hipError_t launch_attention_stream_append_slots(const float* qkv, float* kring, float* vring, int batch, int R, int H,
-                                                int D, int cap, const long long* pos_tab, const int* slot_tab,
-                                                hipStream_t s);
+                                          int cap, long long pos0, const long long* pos_tab, const int* slot_tab,
+                                          hipStream_t s, const char** kname = nullptr);
 // stream_carry_kernel: n strided copies in one launch; copy d moves `count` floats (a multiple of 4) per item from
 // src + b * src_bstride to dst + b * dst_bstride.  Source and destination never overlap.
-// stream_carry_slots_kernel: the same with the stream's side of a copy (`state`: CARRY_STATE_SRC for carry-in,
-// CARRY_STATE_DST for carry-out, 0 for neither) indexed by slot_tab[b] instead of b.
+// slot_tab set (stream_carry_slots_kernel): the same with the stream's side of a copy (`state`: CARRY_STATE_SRC for
+// carry-in, CARRY_STATE_DST for carry-out, 0 for neither) indexed by slot_tab[b] instead of b.
 enum { CARRY_STATE_SRC = 1, CARRY_STATE_DST = 2 };
 struct CarryCopy {
     const float* src;
@@ -529,8 +529,8 @@ struct CarryTable {
     CarryCopy c[CARRY_MAX];
     int n;
 };
-hipError_t launch_stream_carry(const CarryTable& t, int batch, hipStream_t s);
-hipError_t launch_stream_carry_slots(const CarryTable& t, int batch, const int* slot_tab, hipStream_t s);
+hipError_t launch_stream_carry(const CarryTable& t, int batch, const int* slot_tab, hipStream_t s,
+                               const char** kname = nullptr);
 
 // Streamed encode (engine.cpp "encode stream").
 // conv0_hist_kernel: launch_conv0 on a chunk of L >= 8 samples per item whose 6 samples of the past are the last ones
@@ -539,10 +539,10 @@ hipError_t launch_stream_carry_slots(const CarryTable& t, int batch, const int* 
 hipError_t launch_conv0_hist(const float* x, long long L, int batch, const float* w, const float* b, float* y, int cout,
                              int ksize, long long y_bstride, const float* hist, float* tail, hipStream_t s);
 // stream_ds_rows_kernel: src [batch][R][C] -> dst [batch][2 + R][C] rows 2 .., and where the item's first row is
-// absolute row 0 (pos0, or pos_tab[b] in the slot form) dst rows 0, 1 = src row 0: the downsample's replicate padding
-hipError_t launch_stream_ds_rows(const float* src, float* dst, int batch, int R, int C, long long pos0, hipStream_t s);
-hipError_t launch_stream_ds_rows_slots(const float* src, float* dst, int batch, int R, int C, const long long* pos_tab,
-                                       hipStream_t s);
+// absolute row 0 (pos0, or pos_tab[b] where pos_tab is set: stream_ds_rows_slots_kernel) dst rows 0, 1 = src row 0: the
+// downsample's replicate padding
+hipError_t launch_stream_ds_rows(const float* src, float* dst, int batch, int R, int C, long long pos0,
+                                 const long long* pos_tab, hipStream_t s, const char** kname = nullptr);
 
 // polyphase resampler (resample.hip): clips packed at in_off / out_off (device int64 arrays), one launch
 hipError_t launch_resample_poly(const float* x, const long long* in_off, const long long* in_len, int nclips,

@@ -135,7 +135,100 @@ class EncodeTicket:
         return self.out
 
 
-class DecodeStream:
+class _Stream:
+    """What ``DecodeStream`` and ``EncodeStream`` share: the handle, the slots' bookkeeping and the calls into
+    ``mimi_{decode,encode}_stream_*`` (``_direction`` names which)."""
+
+    _direction = ""
+
+    def __init__(self, model: "MimiHipModel", batch: int, num_quantizers: int, max_step_frames: int):
+        self._model, self.batch, self.num_quantizers = model, int(batch), int(num_quantizers)
+        self.max_step_frames = int(max_step_frames)
+        self._h = None
+        h = ctypes.c_void_p()
+        self._call("create", model._h, self.batch, self.num_quantizers, self.max_step_frames, ctypes.byref(h))
+        self._h = h
+
+    def _fn(self, name: str):
+        return getattr(self._model._lib, f"mimi_{self._direction}_stream_{name}")
+
+    def _call(self, name: str, *args):
+        """``mimi_<direction>_stream_<name>(*args)``; an invalid argument (status 1) is a ``ValueError``."""
+        try:
+            _lib.check(self._fn(name)(*args))
+        except _lib.MimiHipError as err:
+            if err.status == 1:
+                raise ValueError(str(err)) from None
+            raise
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError(f"this {type(self).__name__} is closed")
+        return self._h
+
+    @property
+    def position(self) -> int:
+        """Frames stepped so far (the furthest slot's)."""
+        return int(self._fn("position")(self._handle()))
+
+    @property
+    def positions(self) -> List[int]:
+        """Frames stepped by each slot since its last reset."""
+        h = self._handle()
+        return [int(self._fn("slot_position")(h, b)) for b in range(self.batch)]
+
+    @property
+    def state_bytes(self) -> int:
+        return int(self._fn("state_bytes")(self._handle()))
+
+    def _items(self, slots: Optional[Sequence[int]]):
+        """The checked slot list of a step (``None``: all slots) and the number of items it takes."""
+        if slots is None:
+            return None, self.batch
+        slots = [int(x) for x in slots]
+        if not 1 <= len(slots) <= self.batch:
+            raise ValueError(f"a step lists 1 .. {self.batch} slots, got {len(slots)}")
+        if min(slots) < 0 or max(slots) >= self.batch or len(set(slots)) != len(slots):
+            raise ValueError(f"slots must be distinct and in [0, {self.batch}), got {slots}")
+        return slots, len(slots)
+
+    def _step(self, slots: Optional[List[int]], src: torch.Tensor, n: int, out: torch.Tensor):
+        """One step of ``n`` frames from the device tensor ``src`` into ``out``, over all slots or the listed ones."""
+        io = (ctypes.c_void_p(src.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), self._model._stream())
+        if slots is None:
+            self._call("step", self._handle(), *io)
+        else:
+            self._call("step_slots", self._handle(), (ctypes.c_int32 * len(slots))(*slots), len(slots), *io)
+
+    def reset(self, slot: Optional[int] = None):
+        """Back to position 0 with a fresh state: what follows equals a fresh stream.  With ``slot`` only that slot, its
+        neighbours untouched (``ValueError`` for a slot outside ``[0, batch)``)."""
+        if slot is None:
+            self._call("reset", self._handle())
+        else:
+            self._call("reset_slot", self._handle(), int(slot))
+
+    def close(self):
+        h, self._h = self._h, None
+        if h is not None and self._model._h is not None:
+            self._fn("destroy")(h)
+        self._model._streams.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DecodeStream(_Stream):
     """Streaming decode (``MimiHipModel.decode_stream``): ``batch`` items, ``n`` new frames of codes in and their
     ``1920 n`` samples out per ``step``, on a KV cache and per-stage carries that the stream owns in device memory
     (``state_bytes``, constant).  The samples are bitwise the same under any split of a sequence into steps, and within
@@ -146,39 +239,7 @@ class DecodeStream:
     frees it).  A slot's samples are bitwise those of a ``batch=1`` stream fed the same sequence, whatever its
     neighbours do.  A context manager; ``close()`` frees the state (closing the model closes its streams)."""
 
-    def __init__(self, model: "MimiHipModel", batch: int, num_quantizers: int, max_step_frames: int):
-        self._model, self.batch, self.num_quantizers = model, int(batch), int(num_quantizers)
-        self.max_step_frames = int(max_step_frames)
-        self._h = None
-        h = ctypes.c_void_p()
-        try:
-            _lib.check(model._lib.mimi_decode_stream_create(model._h, self.batch, self.num_quantizers,
-                                                            self.max_step_frames, ctypes.byref(h)))
-        except _lib.MimiHipError as err:
-            if err.status == 1:
-                raise ValueError(str(err)) from None
-            raise
-        self._h = h
-
-    def _handle(self):
-        if self._h is None:
-            raise RuntimeError("this DecodeStream is closed")
-        return self._h
-
-    @property
-    def position(self) -> int:
-        """Frames decoded so far (the furthest slot's)."""
-        return int(self._model._lib.mimi_decode_stream_position(self._handle()))
-
-    @property
-    def positions(self) -> List[int]:
-        """Frames decoded by each slot since its last reset."""
-        h = self._handle()
-        return [int(self._model._lib.mimi_decode_stream_slot_position(h, b)) for b in range(self.batch)]
-
-    @property
-    def state_bytes(self) -> int:
-        return int(self._model._lib.mimi_decode_stream_state_bytes(self._handle()))
+    _direction = "decode"
 
     def step(self, codes: torch.Tensor, out: Optional[torch.Tensor] = None,
              slots: Optional[Sequence[int]] = None) -> torch.Tensor:
@@ -188,16 +249,10 @@ class DecodeStream:
         ``[m, 1, 1920 n]``.  ``ValueError`` for ``n`` outside ``[1, max_step_frames]`` and a bad slot list (the state is
         untouched) and for a code outside ``[0, codebook_size)`` (the slots of that call then refuse until ``reset``)."""
         m = self._model
-        h = self._handle()
+        self._handle()
         if not torch.is_tensor(codes):
             codes = torch.as_tensor(np.asarray(codes))
-        if slots is not None:
-            slots = [int(x) for x in slots]
-            if not 1 <= len(slots) <= self.batch:
-                raise ValueError(f"a step lists 1 .. {self.batch} slots, got {len(slots)}")
-            if min(slots) < 0 or max(slots) >= self.batch or len(set(slots)) != len(slots):
-                raise ValueError(f"slots must be distinct and in [0, {self.batch}), got {slots}")
-        items = self.batch if slots is None else len(slots)
+        slots, items = self._items(slots)
         if codes.dim() != 3 or codes.shape[0] != items or codes.shape[1] != self.num_quantizers:
             raise ValueError(f"codes must be [{items}, {self.num_quantizers}, n], got {tuple(codes.shape)}")
         n = int(codes.shape[2])
@@ -209,55 +264,11 @@ class DecodeStream:
         elif (tuple(out.shape) != (items, 1, L) or out.dtype != torch.float32 or out.device != m.device
               or not out.is_contiguous()):
             raise ValueError(f"out must be a contiguous float32 [{items}, 1, {L}] tensor on {m.device}")
-        c = codes.to(device=m.device, dtype=torch.int32).contiguous()
-        try:
-            if slots is None:
-                _lib.check(m._lib.mimi_decode_stream_step(h, ctypes.c_void_p(c.data_ptr()), n,
-                                                          ctypes.c_void_p(out.data_ptr()), m._stream()))
-            else:
-                tab = (ctypes.c_int32 * items)(*slots)
-                _lib.check(m._lib.mimi_decode_stream_step_slots(h, tab, items, ctypes.c_void_p(c.data_ptr()), n,
-                                                                ctypes.c_void_p(out.data_ptr()), m._stream()))
-        except _lib.MimiHipError as err:
-            if err.status == 1:
-                raise ValueError(str(err)) from None
-            raise
+        self._step(slots, codes.to(device=m.device, dtype=torch.int32).contiguous(), n, out)
         return out
 
-    def reset(self, slot: Optional[int] = None):
-        """Back to position 0 with zero state: what follows equals a fresh stream.  With ``slot`` only that slot, its
-        neighbours untouched (``ValueError`` for a slot outside ``[0, batch)``)."""
-        if slot is None:
-            _lib.check(self._model._lib.mimi_decode_stream_reset(self._handle()))
-            return
-        try:
-            _lib.check(self._model._lib.mimi_decode_stream_reset_slot(self._handle(), int(slot)))
-        except _lib.MimiHipError as err:
-            if err.status == 1:
-                raise ValueError(str(err)) from None
-            raise
 
-    def close(self):
-        h, self._h = self._h, None
-        if h is not None and self._model._h is not None:
-            self._model._lib.mimi_decode_stream_destroy(h)
-        self._model._streams.discard(self)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class EncodeStream:
+class EncodeStream(_Stream):
     """Streaming encode (``MimiHipModel.encode_stream``): ``batch`` items, ``n`` whole frames of audio (``frame_samples``
     = 1920 samples each) in and their codes ``[., K, n]`` out per ``step``, on a KV cache and per-stage carries that the
     stream owns in device memory (``state_bytes``, constant).  The codes of frames ``[p, p + n)`` are bitwise the same
@@ -269,40 +280,11 @@ class EncodeStream:
     ``batch=1`` stream fed the same sequence, whatever its neighbours do.  A tail shorter than a frame is the caller's
     to keep for the next step.  A context manager; ``close()`` frees the state (closing the model closes its streams)."""
 
+    _direction = "encode"
+
     def __init__(self, model: "MimiHipModel", batch: int, num_quantizers: int, max_step_frames: int):
-        self._model, self.batch, self.num_quantizers = model, int(batch), int(num_quantizers)
-        self.max_step_frames = int(max_step_frames)
         self.frame_samples = int(model._lib.mimi_frame_samples_cfg(ctypes.byref(model._cfg_c)))
-        self._h = None
-        h = ctypes.c_void_p()
-        try:
-            _lib.check(model._lib.mimi_encode_stream_create(model._h, self.batch, self.num_quantizers,
-                                                            self.max_step_frames, ctypes.byref(h)))
-        except _lib.MimiHipError as err:
-            if err.status == 1:
-                raise ValueError(str(err)) from None
-            raise
-        self._h = h
-
-    def _handle(self):
-        if self._h is None:
-            raise RuntimeError("this EncodeStream is closed")
-        return self._h
-
-    @property
-    def position(self) -> int:
-        """Frames encoded so far (the furthest slot's)."""
-        return int(self._model._lib.mimi_encode_stream_position(self._handle()))
-
-    @property
-    def positions(self) -> List[int]:
-        """Frames encoded by each slot since its last reset."""
-        h = self._handle()
-        return [int(self._model._lib.mimi_encode_stream_slot_position(h, b)) for b in range(self.batch)]
-
-    @property
-    def state_bytes(self) -> int:
-        return int(self._model._lib.mimi_encode_stream_state_bytes(self._handle()))
+        super().__init__(model, batch, num_quantizers, max_step_frames)
 
     def step(self, audio: torch.Tensor, slots: Optional[Sequence[int]] = None,
              out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -312,16 +294,10 @@ class EncodeStream:
         slot ``slots[i]``, the result is ``[m, K, n]``.  ``ValueError`` for a length that is not ``1 ..
         max_step_frames`` whole frames and for a bad slot list or ``out`` (the state is untouched)."""
         m = self._model
-        h = self._handle()
+        self._handle()
         if not torch.is_tensor(audio):
             audio = torch.as_tensor(np.asarray(audio))
-        if slots is not None:
-            slots = [int(x) for x in slots]
-            if not 1 <= len(slots) <= self.batch:
-                raise ValueError(f"a step lists 1 .. {self.batch} slots, got {len(slots)}")
-            if min(slots) < 0 or max(slots) >= self.batch or len(set(slots)) != len(slots):
-                raise ValueError(f"slots must be distinct and in [0, {self.batch}), got {slots}")
-        items = self.batch if slots is None else len(slots)
+        slots, items = self._items(slots)
         if audio.dim() == 3 and audio.shape[1] == 1:
             audio = audio[:, 0]
         if audio.dim() != 2 or audio.shape[0] != items:
@@ -332,52 +308,8 @@ class EncodeStream:
             raise ValueError(f"a step takes 1 .. {self.max_step_frames} whole frames of {F} samples, got {L} samples")
         n = L // F
         out = m._out(items, self.num_quantizers, n, out)
-        x = audio.to(device=m.device, dtype=torch.float32).contiguous()
-        try:
-            if slots is None:
-                _lib.check(m._lib.mimi_encode_stream_step(h, ctypes.c_void_p(x.data_ptr()), n,
-                                                          ctypes.c_void_p(out.data_ptr()), m._stream()))
-            else:
-                tab = (ctypes.c_int32 * items)(*slots)
-                _lib.check(m._lib.mimi_encode_stream_step_slots(h, tab, items, ctypes.c_void_p(x.data_ptr()), n,
-                                                                ctypes.c_void_p(out.data_ptr()), m._stream()))
-        except _lib.MimiHipError as err:
-            if err.status == 1:
-                raise ValueError(str(err)) from None
-            raise
+        self._step(slots, audio.to(device=m.device, dtype=torch.float32).contiguous(), n, out)
         return out
-
-    def reset(self, slot: Optional[int] = None):
-        """Back to position 0 with a fresh state: what follows equals a fresh stream.  With ``slot`` only that slot, its
-        neighbours untouched (``ValueError`` for a slot outside ``[0, batch)``)."""
-        if slot is None:
-            _lib.check(self._model._lib.mimi_encode_stream_reset(self._handle()))
-            return
-        try:
-            _lib.check(self._model._lib.mimi_encode_stream_reset_slot(self._handle(), int(slot)))
-        except _lib.MimiHipError as err:
-            if err.status == 1:
-                raise ValueError(str(err)) from None
-            raise
-
-    def close(self):
-        h, self._h = self._h, None
-        if h is not None and self._model._h is not None:
-            self._model._lib.mimi_encode_stream_destroy(h)
-        self._model._streams.discard(self)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class MimiHipModel:

@@ -10,7 +10,13 @@ a ragged batch, the quantizer alone, and a loud clip and a loud pair that take t
 `lib_codes.py <tag> decode` writes the decode path's entries instead: the uniform decode of B = 3 x T = 13 x K = 8 and of
 B = 2 x T = 129 x K = 1, the ragged decode of T = [13, 1, 129, 2, 64, 65, 5, 3] at K = 8 (an odd T, 1- to 3-frame items,
 both sides of 256 rows and of the 1024-row tile change), the sha-256 of every tap and the profiled launch sequence and
-records of one uniform and one ragged pass, and the workspace sizes with taps off and on."""
+records of one uniform and one ragged pass, and the workspace sizes with taps off and on.
+
+`lib_codes.py <tag> stream` writes the streams' entries: per direction (dec_ / enc_; K = 8, max_step_frames 3, random
+codes / 1920 n samples of speech-like audio per item) a batch-2 stream in lock-step steps of n = 1, 2, 3, 1 and a batch-3
+stream through slots [0] n = 2, [0, 1] n = 1, [2, 0] n = 3, reset(1), [1, 2] n = 1 and a plain step of n = 1 with the
+positions diverged -- every step's result and the positions -- and one more lock-step step and one more slot step with
+taps and profiling on: the launch sequence, the records and the sha-256 of a tap of each section of the pass."""
 import hashlib
 import os
 import sys
@@ -46,6 +52,21 @@ def profiled(m, name, fn):
     out[f"{name}_records"] = text((k, v["kernel"], v["launches"], v["flops"], v["bytes"]) for k, v in prof.items())
     m.set_profiling(0)
     m.profile_reset()
+
+
+def traced(m, name, fn, taps):
+    """One pass with taps and profiling on: the sha-256 of the listed taps, the launch sequence and the records."""
+    m.set_taps(True)
+    m.set_profiling(1)
+    m.profile_reset()
+    fn()
+    prof = m.profile_read()
+    out[f"{name}_sequence"] = text(m.profile_sequence())
+    out[f"{name}_records"] = text((k, v["kernel"], v["launches"], v["flops"], v["bytes"]) for k, v in prof.items())
+    m.set_profiling(0)
+    for t in taps:
+        out[f"{name}_{t}"] = tap_sha(m, t)
+    m.set_taps(False)
 
 
 def counters_script():
@@ -125,28 +146,14 @@ def decode_section():
     def codes(B, K, T):
         return torch.from_numpy(rng.integers(0, m.config.codebook_size, (B, K, T)).astype(np.int32)).cuda()
 
-    def traced(name, fn):
-        """One pass with taps and profiling on: every tap's sha-256, the launch sequence and the records."""
-        m.set_taps(True)
-        m.set_profiling(1)
-        m.profile_reset()
-        fn()
-        prof = m.profile_read()
-        out[f"{name}_sequence"] = text(m.profile_sequence())
-        out[f"{name}_records"] = text((k, v["kernel"], v["launches"], v["flops"], v["bytes"]) for k, v in prof.items())
-        m.set_profiling(0)
-        for t in TAPS:
-            out[f"{name}_{t}"] = tap_sha(m, t)
-        m.set_taps(False)
-
     cu, c1, cr = codes(3, 8, 13), codes(2, 1, 129), codes(len(LENS), 8, max(LENS))
     out["u_b3_t13_k8"] = m.decode(cu).audio_values.cpu().numpy()
     out["u_b2_t129_k1"] = m.decode(c1).audio_values.cpu().numpy()
     buf = torch.zeros((len(LENS), m.get_decoded_length(max(LENS))), dtype=torch.float32, device="cuda:0")
     m.decode_ragged(cr, LENS, out=buf)
     out["ragged"] = buf.cpu().numpy()  # (the samples past an item's length stay 0: never written)
-    traced("tu", lambda: m.decode(cu))
-    traced("tr", lambda: m.decode_ragged(cr, LENS))
+    traced(m, "tu", lambda: m.decode(cu), TAPS)
+    traced(m, "tr", lambda: m.decode_ragged(cr, LENS), TAPS)
     for taps in (False, True):
         m.set_taps(taps)
         out[f"workspace_taps{int(taps)}"] = np.array(
@@ -156,8 +163,51 @@ def decode_section():
     print(tag, "workspace", out["workspace_taps0"].tolist(), out["workspace_taps1"].tolist())
 
 
+def stream_section():
+    sd = synthetic.make_state_dict(seed=0)
+    sd.update(synthetic.make_decoder_state_dict(seed=0))
+    m = MimiHipModel(sd, device="cuda:0", decode=True)
+    K, F = 8, 1920
+    rng = np.random.default_rng(701)
+    clips = iter(range(1 << 20))
+
+    def codes(items, n):
+        return torch.from_numpy(rng.integers(0, m.config.codebook_size, (items, K, n)).astype(np.int32)).cuda()
+
+    def audio(items, n):
+        return torch.from_numpy(np.stack([synthetic.speech_like(F * n, 702, next(clips)) for _ in range(items)])).cuda()
+
+    # the slot schedule: (slots, n), a reset, then a plain step that finds the positions diverged
+    SLOTS = [([0], 2), ([0, 1], 1), ([2, 0], 3), "reset 1", ([1, 2], 1), (None, 1)]
+    for d, open_stream, chunk, taps in (
+            ("dec", m.decode_stream, codes, ["quantized", "upsample", "qkv0", "att0", "xfmr7", "dres1_elu", "audio"]),
+            ("enc", m.encode_stream, audio,
+             ["conv0", "res1_elu", "encoder", "qkv0", "att0", "xfmr7", "downsample", "proj"])):
+        with open_stream(batch=2, num_quantizers=K, max_step_frames=3) as st:  # lock-step
+            for i, n in enumerate((1, 2, 3, 1)):
+                out[f"{d}_lock{i}_n{n}"] = st.step(chunk(2, n)).cpu().numpy()
+            x = chunk(2, 2)
+            traced(m, f"{d}_tlock", lambda: st.step(x), taps)
+            out[f"{d}_lock_positions"] = np.array(st.positions, dtype=np.int64)
+        with open_stream(batch=3, num_quantizers=K, max_step_frames=3) as st:  # slots
+            for i, op in enumerate(SLOTS):
+                if op == "reset 1":
+                    st.reset(1)
+                else:
+                    slots, n = op
+                    out[f"{d}_slots{i}_n{n}"] = st.step(chunk(3 if slots is None else len(slots), n),
+                                                        slots=slots).cpu().numpy()
+                out[f"{d}_slots{i}_positions"] = np.array(st.positions, dtype=np.int64)
+            x = chunk(2, 2)
+            traced(m, f"{d}_tslots", lambda: st.step(x, slots=[2, 0]), taps)
+            out[f"{d}_slots_positions"] = np.array(st.positions, dtype=np.int64)
+    m.close()
+
+
 if sys.argv[2:] == ["decode"]:
     decode_section()
+elif sys.argv[2:] == ["stream"]:
+    stream_section()
 else:
     encode_section()
 os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
