@@ -302,8 +302,26 @@ int64_t mimi_decode_ragged_workspace_bytes(const mimi_engine* e, const int64_t* 
  * reset.)  mimi_decode_stream_position: the largest slot position (the position, on a stream stepped in lock-step);
  * mimi_decode_stream_slot_position: one slot's, -1 for NULL or a slot out of range.  mimi_decode_stream_state_bytes
  * counts the state; a slot step's two tables (12 bytes per slot) are a separate allocation.
- * Not provided: a different n per slot within one call (group the sessions by n), hipGraph capture of a step, f16x3
- * arithmetic.
+ *
+ * A COUNT PER SLOT.  mimi_decode_stream_step_ragged is step_slots with item i (slot slots[i]) advancing by its own
+ * frames[i] frames (`frames`: host, [m], need not outlive the call), 1 <= frames[i] <= max_frames <= max_step_frames; a
+ * slot with nothing to do is not listed.  The I/O layout is mimi_decode_ragged's: dev_codes [m][num_quantizers]
+ * [max_frames] and dev_audio [m][1920 max_frames], padded rows.  Codes past an item's frames[i] are never read (any
+ * value), samples past 1920 frames[i] never written; afterwards slot slots[i] stands frames[i] further.  CONTRACT as
+ * step_slots, over per-item counts: a listed slot's samples are bitwise those of a batch = 1 stream fed that slot's
+ * sequence since its last reset, under any split, in any order of `slots`, whatever counts its neighbours bring.
+ * Counts that all equal max_frames make the call step_slots itself (the same launches under the same recorded names).
+ * Otherwise the launches are those of a slot step plus one more small host-to-device copy (the step's tables: per
+ * stage the items' rows and first rows, see mimi_stream_step_layout), whatever the counts, and the per-item kernels
+ * record as rvq_decode_ragged_kernel, upsample_dw_hist_ragged_kernel, attention_stream_ragged_kernel,
+ * attention_stream_append_ragged_kernel, stream_carry_ragged_kernel, resblock_hist_ragged_kernel<...>,
+ * final_conv_hist_ragged_kernel and the packed-rows GEMM instantiations; the workspace is sized by the sum of the
+ * counts.  Errors as step_slots (the 2^24-row limit per listed slot at its own count; a bad code inside an item's
+ * frames fails every slot listed in that call), and MIMI_ERR_INVALID_ARGUMENT with nothing launched and no state
+ * touched also for a NULL `frames`, a count outside [1, max_frames] and max_frames outside [1, max_step_frames].
+ * Taps of a step with unequal counts: every stage and "audio" without carry rows or padding, packed
+ * [1][sum of rows][C] as mimi_decode_ragged's.
+ * Not provided: a count of 0, hipGraph capture of a step, f16x3 arithmetic.
  */
 typedef struct mimi_decode_stream mimi_decode_stream;
 int mimi_decode_stream_create(mimi_engine* e, int32_t batch, int32_t num_quantizers, int32_t max_step_frames,
@@ -313,6 +331,33 @@ int mimi_decode_stream_step(mimi_decode_stream* st, const int32_t* dev_codes /* 
 int mimi_decode_stream_step_slots(mimi_decode_stream* st, const int32_t* slots /* host, [m] */, int32_t m,
                                   const int32_t* dev_codes /* [m][num_quantizers][n] */, int32_t n,
                                   float* dev_audio /* [m][1920 n] */, void* stream);
+int mimi_decode_stream_step_ragged(mimi_decode_stream* st, const int32_t* slots /* host, [m] */,
+                                   const int32_t* frames /* host, [m] */, int32_t m, int32_t max_frames,
+                                   const int32_t* dev_codes /* [m][num_quantizers][max_frames] */,
+                                   float* dev_audio /* [m][1920 max_frames] */, void* stream);
+/*
+ * The layout of a ragged stream step, host-only (no device, no engine): for `direction` and the items' counts
+ * (`frames`: [m], each in [1, max_frames]) the stages that carry rows from step to step, in the order of the stream's
+ * carries, and the step's workspace.  Stage j has carry_rows[j] = H rows per item in front of the chunk, rate[j] = f
+ * rows per frame and channels[j] floats per row; item i's block [H + f frames[i]][C] starts at row first_row[j * m + i]
+ * = H i + f off[i] (off = the prefix sum of frames) of one packed tensor that begins byte_offset[j] bytes into the
+ * workspace, and has row_count[j * m + i] rows: blocks in order, back to back.  The arrays of stages hold
+ * MIMI_STREAM_MAX_STAGES entries, first_row and row_count MIMI_STREAM_MAX_STAGES * m.  *workspace_bytes: what the step
+ * needs of the engine's decode workspace (taps != 0: with the engine's taps on) -- sized by the sum of the counts, so
+ * never more than the step of m items at max_frames each, and equal to it when every count is max_frames.
+ * MIMI_STREAM_DECODE: the embedding (H 1, f 1), the transformer output (6, 2), then per ratio the up conv's input (1)
+ * and output (2), the last conv's input (2).  MIMI_STREAM_ENCODE: conv 0's carry (one row of 8 samples per item, f 0:
+ * the audio itself stays in the caller's rows), then per ratio the residual block's input (H 2, f 1920 / the ratios so
+ * far) and the down conv's (H r), the final conv's input (2, 2) and the downsample's (2, 2).  MIMI_ERR_INVALID_ARGUMENT: a NULL pointer, another direction, m outside [1, 65535], max_frames
+ * outside [1, 2^20], a count outside [1, max_frames].
+ */
+#define MIMI_STREAM_DECODE 0
+#define MIMI_STREAM_ENCODE 1
+#define MIMI_STREAM_MAX_STAGES 16
+int mimi_stream_step_layout(const mimi_config* cfg, int32_t direction, const int32_t* frames /* [m] */, int32_t m,
+                            int32_t max_frames, int32_t taps, int32_t* n_stages, int32_t* carry_rows, int32_t* rate,
+                            int32_t* channels, int64_t* byte_offset, int64_t* first_row, int64_t* row_count,
+                            int64_t* workspace_bytes);
 int mimi_decode_stream_reset(mimi_decode_stream* st);
 int mimi_decode_stream_reset_slot(mimi_decode_stream* st, int32_t slot);
 int64_t mimi_decode_stream_position(const mimi_decode_stream* st);    /* frames decoded so far (the largest slot's) */
@@ -369,8 +414,8 @@ void mimi_decode_stream_destroy(mimi_decode_stream* st);
  * untouched).  mimi_encode_stream_position: the largest slot position; _slot_position: one slot's, -1 for NULL or a slot
  * out of range.  Destroy every stream before its engine.
  * Not provided: a tail shorter than a frame (the caller keeps it for the next step; mimi_encode's last, right-padded
- * frame of a length that is not a multiple of F has no streamed equivalent here), a different n per slot within one
- * call, f16x3 arithmetic, hipGraph capture of a step, the reference's encoder_past_key_values / padding_cache objects.
+ * frame of a length that is not a multiple of F has no streamed equivalent here), a count of 0 in a ragged step
+ * (mimi_encode_stream_step_ragged, below), f16x3 arithmetic, hipGraph capture of a step, the reference's encoder_past_key_values / padding_cache objects.
  */
 typedef struct mimi_encode_stream mimi_encode_stream;
 int mimi_encode_stream_create(mimi_engine* e, int32_t batch, int32_t num_quantizers, int32_t max_step_frames,
@@ -380,6 +425,22 @@ int mimi_encode_stream_step(mimi_encode_stream* st, const float* dev_audio /* [b
 int mimi_encode_stream_step_slots(mimi_encode_stream* st, const int32_t* slots /* host, [m] */, int32_t m,
                                   const float* dev_audio /* [m][F n] */, int32_t n,
                                   int32_t* dev_codes /* [m][num_quantizers][n] */, void* stream);
+/* A count per slot, as mimi_decode_stream_step_ragged: item i (slot slots[i]) advances by frames[i] whole frames, 1 <=
+ * frames[i] <= max_frames <= max_step_frames.  dev_audio [m][F max_frames] and dev_codes [m][num_quantizers][max_frames]
+ * are padded rows: audio past F frames[i] samples is never read (NaN there is harmless), codes past frames[i] are never
+ * written.  A listed slot's codes are bitwise those of a batch = 1 stream fed that slot's audio since its last reset,
+ * whatever counts its neighbours bring; a fresh slot's replicate padding comes from its own first row.  Counts that all
+ * equal max_frames make the call step_slots itself.  Otherwise the launches are those of a slot step plus one small
+ * host-to-device copy, recorded as conv0_hist_ragged_kernel, resblock_hist_ragged_kernel<...>, the packed-rows GEMMs
+ * (..., 102> / 103> / 104> / 109>), attention_stream_ragged_kernel, attention_stream_append_ragged_kernel,
+ * stream_ds_rows_ragged_kernel and stream_carry_ragged_kernel; the RVQ kernels store through a per-frame map into the
+ * padded rows.  Errors as step_slots, and MIMI_ERR_INVALID_ARGUMENT with nothing launched and no state touched for a
+ * NULL pointer, a count outside [1, max_frames] and max_frames outside [1, max_step_frames].  Taps of a step with unequal
+ * counts are packed [1][sum of rows][C]. */
+int mimi_encode_stream_step_ragged(mimi_encode_stream* st, const int32_t* slots /* host, [m] */,
+                                   const int32_t* frames /* host, [m] */, int32_t m, int32_t max_frames,
+                                   const float* dev_audio /* [m][F max_frames] */,
+                                   int32_t* dev_codes /* [m][num_quantizers][max_frames] */, void* stream);
 int mimi_encode_stream_reset(mimi_encode_stream* st);
 int mimi_encode_stream_reset_slot(mimi_encode_stream* st, int32_t slot);
 int64_t mimi_encode_stream_position(const mimi_encode_stream* st);    /* frames encoded so far (the largest slot's) */

@@ -9,6 +9,13 @@
 // and under the same bodies their slot forms (SL: a step over a subset of the stream's slots, each slot at its own
 // position): item b of the step takes its first row from pos_tab[b] and its rings / carries from slot slot_tab[b];
 // the step's own rows in the workspace stay indexed by b.  The tables are device memory (a step may list 65535 slots).
+// A RAGGED step (every listed slot its own number of frames; engine.cpp StreamLayout) packs the items' rows: item b's
+// rlen[b] rows start at row roff[b] of qkv / out.  attention_stream_ragged_kernel is the slot body with the item's rows
+// and first row from those tables (the grid covers the longest item; a wave past its item's rows exits before any load
+// of a row); attention_stream_append_ragged_kernel runs a 2-D grid with the item uniform per workgroup;
+// stream_carry_ragged_kernel takes both sides' element offsets and the count per (copy, item) from tables the host
+// worked out.  Lane assignment, fmaf chains, butterfly and P.V order stay functions of the absolute row alone, so a
+// row's bits are those of the slot form.
 // One launcher per body (launch_attention_stream, launch_attention_stream_append, launch_stream_carry,
 // launch_stream_ds_rows): null tables launch the lock-step kernel at the scalar pos0, non-null tables the slot kernel,
 // and *kname receives the name of the one launched.
@@ -32,19 +39,30 @@ namespace mimi {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // SL: pos0 is pos_tab[b] and the ring is slot slot_tab[b]'s; b = blockIdx.z is uniform, so both are scalar loads
-template <bool SL>
+// RG (a ragged step: SL with a frame count per item): item b has rlen[b] rows starting at row roff[b] of the packed
+// qkv / out; the grid covers the longest item and a wave past its item's rows exits before any load of a row
+template <bool SL, bool RG = false>
 __device__ __forceinline__ void attention_stream_body(float* sc_all, const float* __restrict__ qkv,
                                                       const float* __restrict__ kring,
                                                       const float* __restrict__ vring, float* __restrict__ out, int R,
                                                       int H, int window, int cap, long long pos0,
                                                       const long long* __restrict__ pos_tab,
-                                                      const int* __restrict__ slot_tab, float scale) {
+                                                      const int* __restrict__ slot_tab, float scale,
+                                                      const int* __restrict__ rlen = nullptr,
+                                                      const int* __restrict__ roff = nullptr) {
+    static_assert(SL || !RG, "a ragged step is a slot step");
     constexpr int D = 64;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = blockIdx.x * 4 + wave;  // the query's row in the step
-    if (i >= R) return;
+    if constexpr (!RG)
+        if (i >= R) return;
     const int h = blockIdx.y, b = blockIdx.z;
+    long long r0 = (long long)b * R;  // the item's first row in qkv / out
+    if constexpr (RG) {
+        if (i >= rlen[b]) return;
+        r0 = roff[b];
+    }
     int rb = b;  // the item's place among the rings
     if constexpr (SL) {
         pos0 = pos_tab[b];
@@ -52,7 +70,7 @@ __device__ __forceinline__ void attention_stream_body(float* sc_all, const float
     }
     float* sc = sc_all + wave * window;
     const long long ld = 3LL * H * D;
-    const float* step = qkv + (long long)b * R * ld;               // the item's rows of this step
+    const float* step = qkv + r0 * ld;                            // the item's rows of this step
     const long long ring = ((long long)rb * H + h) * cap * D;     // the (item, head)'s ring
     const long long a = pos0 + i;
     const long long jlo = a - window + 1 > 0 ? a - window + 1 : 0;
@@ -107,7 +125,7 @@ __device__ __forceinline__ void attention_stream_body(float* sc_all, const float
         acc = __builtin_fmaf(sc[t + 3], v3, acc);
     }
     for (; t < cnt; ++t) acc = __builtin_fmaf(sc[t], vrow(jlo + t)[lane], acc);
-    out[((long long)b * R + i) * (H * D) + h * D + lane] = acc * (1.0f / l);
+    out[(r0 + i) * (H * D) + h * D + lane] = acc * (1.0f / l);
 }
 
 __global__ __launch_bounds__(256) void attention_stream_kernel(const float* __restrict__ qkv,
@@ -129,6 +147,19 @@ __global__ __launch_bounds__(256) void attention_stream_slots_kernel(const float
     attention_stream_body<true>(sc_all, qkv, kring, vring, out, R, H, window, cap, 0, pos_tab, slot_tab, scale);
 }
 
+__global__ __launch_bounds__(256) void attention_stream_ragged_kernel(const float* __restrict__ qkv,
+                                                                      const float* __restrict__ kring,
+                                                                      const float* __restrict__ vring,
+                                                                      float* __restrict__ out, int H, int window, int cap,
+                                                                      const long long* __restrict__ pos_tab,
+                                                                      const int* __restrict__ slot_tab,
+                                                                      const int* __restrict__ rlen,
+                                                                      const int* __restrict__ roff, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float sc_all[];
+    attention_stream_body<true, true>(sc_all, qkv, kring, vring, out, 0, H, window, cap, 0, pos_tab, slot_tab, scale,
+                                      rlen, roff);
+}
+
 // pos_tab / slot_tab both null: the lock-step kernel at pos0; both set: the slot kernel (pos0 unused)
 hipError_t launch_attention_stream(const float* qkv, const float* kring, const float* vring, float* out, int batch,
                                    int R, int H, int D, int window, int cap, long long pos0, const long long* pos_tab,
@@ -147,6 +178,23 @@ hipError_t launch_attention_stream(const float* qkv, const float* kring, const f
         hipLaunchKernelGGL(attention_stream_kernel, grid, dim3(256), lds, s, qkv, kring, vring, out, R, H, window, cap,
                            pos0, scale);
     if (kname) *kname = sl ? "mimi::attention_stream_slots_kernel" : "mimi::attention_stream_kernel";
+    return hipGetLastError();
+}
+
+// the ragged step: R = the longest item's rows (the grid); every table holds `batch` entries checked by the caller
+hipError_t launch_attention_stream_ragged(const float* qkv, const float* kring, const float* vring, float* out,
+                                          int batch, int R, int H, int D, int window, int cap, const long long* pos_tab,
+                                          const int* slot_tab, const int* rlen, const int* roff, float scale,
+                                          hipStream_t s, const char** kname) {
+    if (D != 64 || batch <= 0 || batch > 65535 || R <= 0 || H <= 0 || H > 65535 || window < 1 || cap < window - 1 ||
+        cap < 1 || !pos_tab || !slot_tab || !rlen || !roff || !qkv || !kring || !vring || !out)
+        return hipErrorInvalidValue;
+    const size_t lds = (size_t)4 * window * sizeof(float);
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((R + 3) / 4), (unsigned)H, (unsigned)batch);
+    hipLaunchKernelGGL(attention_stream_ragged_kernel, grid, dim3(256), lds, s, qkv, kring, vring, out, H, window, cap,
+                       pos_tab, slot_tab, rlen, roff, scale);
+    if (kname) *kname = "mimi::attention_stream_ragged_kernel";
     return hipGetLastError();
 }
 
@@ -216,6 +264,45 @@ hipError_t launch_attention_stream_append(const float* qkv, float* kring, float*
     return hipGetLastError();
 }
 
+// The ragged step's append: item b = blockIdx.y (uniform per workgroup: its table entries are scalar loads) has rlen[b]
+// rows at row roff[b] of the packed qkv; blockIdx.x covers the longest item's [row][k | v][head][16 float4] and a thread
+// past its item's exits before any load of a row.
+__global__ __launch_bounds__(256) void attention_stream_append_ragged_kernel(
+    const float* __restrict__ qkv, float* __restrict__ kring, float* __restrict__ vring, int H, int cap,
+    const long long* __restrict__ pos_tab, const int* __restrict__ slot_tab, const int* __restrict__ rlen,
+    const int* __restrict__ roff) {
+    constexpr int D = 64;
+    const int b = blockIdx.y;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)rlen[b] * 2 * H * (D / 4)) return;
+    const int c4 = (int)(idx % (D / 4));
+    long long r = idx / (D / 4);
+    const int h = (int)(r % H);
+    r /= H;
+    const int kv = (int)(r % 2);
+    const int i = (int)(r / 2);
+    const long long pos0 = pos_tab[b];
+    const int rb = slot_tab[b];
+    const float* src = qkv + ((long long)roff[b] + i) * (3LL * H * D) + (long long)(1 + kv) * H * D + h * D + 4 * c4;
+    float* dst = (kv ? vring : kring) + (((long long)rb * H + h) * cap + (pos0 + i) % cap) * D + 4 * c4;
+    *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(src);
+}
+
+// R = the longest item's rows (the grid; R <= cap: no two rows of an item share a ring slot)
+hipError_t launch_attention_stream_append_ragged(const float* qkv, float* kring, float* vring, int batch, int R, int H,
+                                                 int D, int cap, const long long* pos_tab, const int* slot_tab,
+                                                 const int* rlen, const int* roff, hipStream_t s, const char** kname) {
+    if (D != 64 || batch <= 0 || batch > 65535 || R <= 0 || R > cap || H <= 0 || !pos_tab || !slot_tab || !rlen ||
+        !roff || !qkv || !kring || !vring)
+        return hipErrorInvalidValue;
+    const long long blocks = ((long long)R * 2 * H * (D / 4) + 255) / 256;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attention_stream_append_ragged_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(256), 0, s,
+                       qkv, kring, vring, H, cap, pos_tab, slot_tab, rlen, roff);
+    if (kname) *kname = "mimi::attention_stream_append_ragged_kernel";
+    return hipGetLastError();
+}
+
 // copy blockIdx.z of the table, item blockIdx.y; 16 B per thread, grid-stride along x
 // SL: the stream's side of the copy (c.state) is slot slot_tab[item]'s, the workspace side the item's
 template <bool SL>
@@ -260,6 +347,38 @@ hipError_t launch_stream_carry(const CarryTable& t, int batch, const int* slot_t
     return hipGetLastError();
 }
 
+// The ragged step's copies: copy d of the table moves, for item b, cnt[d][b] floats (a multiple of 4, 0 allowed) from
+// t.c[d].src + off[d][0][b] to t.c[d].dst + off[d][1][b] -- element offsets the host worked out for both sides (the
+// state side: the item's slot; the workspace side: the item's block in the packed tensor), so the kernel indexes by
+// nothing but the item's place.  off: [t.n][2][batch] int64, cnt: [t.n][batch] int32, device memory.
+__global__ __launch_bounds__(256) void stream_carry_ragged_kernel(CarryTable t, const long long* __restrict__ off,
+                                                                  const int* __restrict__ cnt) {
+    const int d = blockIdx.z, b = blockIdx.y, m = gridDim.y;
+    const CarryCopy& c = t.c[d];
+    const float* __restrict__ src = c.src + off[((long long)d * 2) * m + b];
+    float* __restrict__ dst = c.dst + off[((long long)d * 2 + 1) * m + b];
+    const int n4 = cnt[(long long)d * m + b] / 4;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256)
+        *reinterpret_cast<f32x4*>(dst + 4LL * i) = *reinterpret_cast<const f32x4*>(src + 4LL * i);
+}
+
+// most: the largest count of any (copy, item), which sizes the grid; the caller has checked every offset and count
+// (multiples of 4 inside their buffers)
+hipError_t launch_stream_carry_ragged(const CarryTable& t, int batch, const long long* off, const int* cnt, int most,
+                                      hipStream_t s, const char** kname) {
+    if (t.n < 1 || t.n > CARRY_MAX || batch <= 0 || batch > 65535 || !off || !cnt || most <= 0 || most % 4)
+        return hipErrorInvalidValue;
+    for (int d = 0; d < t.n; ++d)
+        if (!t.c[d].src || !t.c[d].dst ||
+            (reinterpret_cast<uintptr_t>(t.c[d].src) | reinterpret_cast<uintptr_t>(t.c[d].dst)) % 16)
+            return hipErrorInvalidValue;
+    const int blocks = (most / 4 + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 64 ? blocks : 64), (unsigned)batch, (unsigned)t.n);
+    hipLaunchKernelGGL(stream_carry_ragged_kernel, grid, dim3(256), 0, s, t, off, cnt);
+    if (kname) *kname = "mimi::stream_carry_ragged_kernel";
+    return hipGetLastError();
+}
+
 // Encode stream: item b's R transformer rows (flat [batch][R][C]) go behind the downsample's 2 carry rows in
 // dst [batch][2 + R][C].  An item whose first row is absolute row 0 -- a fresh or reset slot -- has no past: its two
 // carry rows are copies of its row 0 (the reference pads the downsample with mode = "replicate"), written here over
@@ -293,6 +412,42 @@ __global__ __launch_bounds__(256) void stream_ds_rows_slots_kernel(const float* 
                                                                    float* __restrict__ dst, int R, int C,
                                                                    const long long* __restrict__ pos_tab) {
     stream_ds_rows_body<true>(src, dst, R, C, 0, pos_tab);
+}
+
+// The ragged step's form: item b's rlen[b] rows at row roff[b] of the packed src, its block [2 + rlen[b]][C] at row
+// doff[b] of dst; the replicate fill is per item, from the item's own position and its own first row.
+__global__ __launch_bounds__(256) void stream_ds_rows_ragged_kernel(const float* __restrict__ src,
+                                                                    float* __restrict__ dst, int C,
+                                                                    const long long* __restrict__ pos_tab,
+                                                                    const int* __restrict__ rlen,
+                                                                    const int* __restrict__ roff,
+                                                                    const int* __restrict__ doff) {
+    const int b = blockIdx.y;
+    const bool fresh = pos_tab[b] == 0;
+    const int c4 = C / 4;
+    const long long n4 = (long long)(2 + rlen[b]) * c4;
+    const float* __restrict__ sb = src + (long long)roff[b] * C;
+    float* __restrict__ db = dst + (long long)doff[b] * C;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const long long r = i / c4;
+        const int c = (int)(i % c4) * 4;
+        if (r < 2 && !fresh) continue;
+        const long long sr = r < 2 ? 0 : r - 2;
+        *reinterpret_cast<f32x4*>(db + r * C + c) = *reinterpret_cast<const f32x4*>(sb + sr * C + c);
+    }
+}
+
+hipError_t launch_stream_ds_rows_ragged(const float* src, float* dst, int batch, int max_R, int C,
+                                        const long long* pos_tab, const int* rlen, const int* roff, const int* doff,
+                                        hipStream_t s, const char** kname) {
+    if (!src || !dst || batch <= 0 || batch > 65535 || max_R <= 0 || C <= 0 || C % 4 || !pos_tab || !rlen || !roff ||
+        !doff || (reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 16)
+        return hipErrorInvalidValue;
+    const long long blocks = ((long long)(2 + max_R) * (C / 4) + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 64 ? blocks : 64), (unsigned)batch);
+    hipLaunchKernelGGL(stream_ds_rows_ragged_kernel, grid, dim3(256), 0, s, src, dst, C, pos_tab, rlen, roff, doff);
+    if (kname) *kname = "mimi::stream_ds_rows_ragged_kernel";
+    return hipGetLastError();
 }
 
 hipError_t launch_stream_ds_rows(const float* src, float* dst, int batch, int R, int C, long long pos0,

@@ -117,16 +117,18 @@ template <bool RG, bool HS = false>
 __device__ __forceinline__ void upsample_dw_body(const float* __restrict__ x, const float* __restrict__ w,
                                                  float* __restrict__ y, long long rows, int T, int C4,
                                                  const int* __restrict__ tlen, const int* __restrict__ toff,
-                                                 long long xbs = 0) {
+                                                 long long xbs = 0, const int* __restrict__ xoff = nullptr) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     long long row;
     int c4, t;
+    long long xrow = 0;  // RG and HS: the row of x that holds the item's frame t
     if constexpr (RG) {
         const int b = blockIdx.y;
         t = (int)(i / C4);
         if (t >= tlen[b]) return;
         c4 = (int)(i - (long long)t * C4);
         row = (long long)toff[b] + t;
+        if constexpr (HS) xrow = (long long)xoff[b] + t;
     } else {
         if (i >= rows * C4) return;
         row = i / C4;  // b * T + t
@@ -135,7 +137,10 @@ __device__ __forceinline__ void upsample_dw_body(const float* __restrict__ x, co
     }
     const int C = C4 * 4;
     const float* xr = x + row * C + 4 * c4;
-    if constexpr (HS) xr = x + (row / T) * xbs + (long long)t * C + 4 * c4;
+    if constexpr (HS && RG)
+        xr = x + xrow * C + 4 * c4;
+    else if constexpr (HS)
+        xr = x + (row / T) * xbs + (long long)t * C + 4 * c4;
     const f32x4 x1 = *reinterpret_cast<const f32x4*>(xr);
     f32x4 x0 = {0.0f, 0.0f, 0.0f, 0.0f};
     if (HS || t > 0) x0 = *reinterpret_cast<const f32x4*>(xr - C);
@@ -167,6 +172,28 @@ __global__ __launch_bounds__(256) void upsample_dw_hist_kernel(const float* __re
                                                                float* __restrict__ y, long long rows, int T, int C4,
                                                                long long xbs) {
     upsample_dw_body<false, true>(x, w, y, rows, T, C4, nullptr, nullptr, xbs);
+}
+
+// RG and HS together (a ragged step of a decode stream): item b's tlen[b] frames sit at rows xoff[b] .. of x, each
+// item's carry row right in front of its first (x = the packed [carry | chunk] blocks); y packed, rows 2 toff[b] ..
+__global__ __launch_bounds__(256) void upsample_dw_hist_ragged_kernel(const float* __restrict__ x,
+                                                                      const float* __restrict__ w, float* __restrict__ y,
+                                                                      int C4, const int* __restrict__ tlen,
+                                                                      const int* __restrict__ toff,
+                                                                      const int* __restrict__ xoff) {
+    upsample_dw_body<true, true>(x, w, y, 0, 0, C4, tlen, toff, 0, xoff);
+}
+
+hipError_t launch_upsample_dw_hist_ragged(const float* x, const float* w, float* y, int batch, long long max_T, int C,
+                                          const int* tlen, const int* toff, const int* xoff, hipStream_t s) {
+    if (batch <= 0 || batch > 65535 || max_T <= 0 || max_T > 0x7fffffffLL || C <= 0 || C % 4 || !x || !w || !y || !tlen ||
+        !toff || !xoff)
+        return hipErrorInvalidValue;
+    const long long blocks = (max_T * (C / 4) + 255) / 256;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(upsample_dw_hist_ragged_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(256), 0, s, x, w, y,
+                       C / 4, tlen, toff, xoff);
+    return hipGetLastError();
 }
 
 hipError_t launch_upsample_dw_hist(const float* x, const float* w, float* y, int batch, long long T, int C,
@@ -271,6 +298,30 @@ __global__ __launch_bounds__(FC_TILE) void final_conv_hist_kernel(const float* _
                                                                   const float* __restrict__ bias, float* __restrict__ y,
                                                                   long long L, long long xbs) {
     final_conv_body<false, true>(x, w, bias, y, L, nullptr, nullptr, xbs);
+}
+
+// RG and HS together (a ragged step of a decode stream): item b's llen[b] rows start at row loff[b] of x with its two
+// carry rows in front of them; y the caller's padded [B][Ls], samples >= llen[b] of row b left untouched
+__global__ __launch_bounds__(FC_TILE) void final_conv_hist_ragged_kernel(const float* __restrict__ x,
+                                                                         const float* __restrict__ w,
+                                                                         const float* __restrict__ bias,
+                                                                         float* __restrict__ y, long long Ls,
+                                                                         const int* __restrict__ llen,
+                                                                         const int* __restrict__ loff) {
+    final_conv_body<true, true>(x, w, bias, y, Ls, llen, loff);
+}
+
+hipError_t launch_final_conv_hist_ragged(const float* x, const float* w, const float* bias, float* y, int batch,
+                                         long long Ls, int C, int ksize, const int* llen, const int* loff,
+                                         long long max_llen, hipStream_t s) {
+    if (C != FC_C || ksize != 3 || batch <= 0 || batch > 65535 || Ls <= 0 || !x || !w || !bias || !y || !llen || !loff ||
+        max_llen <= 0 || max_llen > Ls)
+        return hipErrorInvalidValue;
+    const long long tiles = (max_llen + FC_TILE - 1) / FC_TILE;
+    if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(final_conv_hist_ragged_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(FC_TILE), 0, s, x, w,
+                       bias, y, Ls, llen, loff);
+    return hipGetLastError();
 }
 
 hipError_t launch_final_conv_hist(const float* x, const float* w, const float* bias, float* y, int batch, long long L,

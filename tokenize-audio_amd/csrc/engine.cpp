@@ -3436,6 +3436,78 @@ extern "C" int mimi_decode_ragged(mimi_engine* e, const int32_t* dev_codes, cons
 // k rings | v rings | RoPE cos | RoPE sin), the pinned images of a step's RoPE rows and slot tables.  The stream_*
 // helpers below are the parts of create / reset / step that do not depend on the direction (`what`: "decode" /
 // "encode", for the messages).
+//
+// THE LAYOUT OF A STEP (StreamLayout).  Item i of a step brings frames[i] frames; off = the prefix sum of frames.  A
+// stage whose tensor has H carry rows per item and f rows per frame holds item i's block [H + f frames[i]][C] at row
+// H i + f off[i] of one packed tensor of H m + f sum rows.  With equal counts n this is [m][H + f n][C], the layout the
+// lock-step and slot steps always had, and they run on the scalars alone.  With unequal counts (`ragged`) the kernels
+// take each item's rows and first row from device tables, already multiplied per stage: one image per step (StreamRag),
+// filled in pinned memory the stream owns and uploaded beside slot_tab / pos_tab.  The flat-row stages (the RVQ sums,
+// LayerNorm, q/k/v, o_proj, fc1, fc2) have H = 0: item i's rows at f off[i], no gaps, and run on all f sum rows as ever.
+struct StreamStage {
+    int H;      // carry rows in front of every item's chunk
+    int64_t f;  // rows per frame
+    int C;      // channels
+};
+struct StreamLayout {
+    int m = 0;
+    bool ragged = false;                    // counts given per item: the *_ragged kernels and the tables
+    int64_t sum = 0, maxn = 0, stride = 0;  // frames: of all items, of the longest, per item of the caller's padded rows
+    std::vector<int32_t> frames, off;
+    std::vector<StreamStage> st;  // the stages that have a carry, in the order of the stream's carries
+    int64_t len(size_t j, int i) const { return st[j].f * frames[i]; }
+    int64_t base(size_t j, int i) const { return (int64_t)st[j].H * i + st[j].f * off[i]; }  // the block's first row
+    int64_t rows(size_t j) const { return (int64_t)st[j].H * m + st[j].f * sum; }             // of the whole tensor
+};
+
+// frames: the items' counts (each in [1, stride], checked by the caller), or null for n = stride frames each
+static void plan_stream(const std::vector<StreamStage>& stages, const int32_t* frames, int m, int64_t stride,
+                        StreamLayout* L) {
+    L->m = m;
+    L->st = stages;
+    L->stride = stride;
+    L->frames.assign(m, (int32_t)stride);
+    L->off.assign(m, 0);
+    L->sum = L->maxn = 0;
+    for (int i = 0; i < m; ++i) {
+        if (frames) L->frames[i] = frames[i];
+        L->off[i] = (int32_t)L->sum;
+        L->sum += L->frames[i];
+        L->maxn = std::max<int64_t>(L->maxn, L->frames[i]);
+    }
+    L->ragged = frames != nullptr;
+}
+
+// The device image of a ragged step's tables for nc carry stages and nr ratios, m entries per table, int64 tables first:
+//   eoff [nr][m]       up conv s: item i's first output element (its block of stage 3 + 2 s behind the 2 carry rows)
+//   coff [2 nc + 1][2][m]  the carry copies' (source, destination) element offsets: carry-in x nc, the transformer's
+//                      rows, carry-out x nc
+//   len | base | alen [nc][3][m]  per stage: the item's rows, its block's first row, H + rows
+//   off1 | off2 | frames [3][m]  the item's first row in the flat tensors at 12.5 and 25 Hz, and its frames
+//   cnt [2 nc + 1][m]   the carry copies' floats
+// (an encode stream: nr = 0 up convs, and behind the image, 8-byte aligned, the RVQ's code map: per packed frame the
+// place of its level-0 code in the caller's padded [m][K][max_frames], int64 [sum])
+static size_t stream_rag_bytes(size_t nc, size_t nr, size_t m) {
+    return (nr + 2 * (2 * nc + 1)) * m * sizeof(int64_t) + (3 * nc + 3 + 2 * nc + 1) * m * sizeof(int32_t);
+}
+static size_t stream_rag_map_at(size_t nc, size_t nr, size_t m) { return (stream_rag_bytes(nc, nr, m) + 7) / 8 * 8; }
+struct StreamRag {
+    const char* dev = nullptr;  // null: not a ragged step
+    size_t nc = 0, nr = 0, m = 0;
+    const long long* i64() const { return reinterpret_cast<const long long*>(dev); }
+    const int* i32() const { return reinterpret_cast<const int*>(dev + (nr + 2 * (2 * nc + 1)) * m * sizeof(int64_t)); }
+    const long long* eoff(size_t s) const { return i64() + s * m; }
+    const long long* coff(size_t copy) const { return i64() + (nr + 2 * copy) * m; }
+    const int* len(size_t j) const { return i32() + (3 * j) * m; }
+    const int* base(size_t j) const { return i32() + (3 * j + 1) * m; }
+    const int* alen(size_t j) const { return i32() + (3 * j + 2) * m; }
+    const int* off1() const { return i32() + (3 * nc) * m; }
+    const int* off2() const { return i32() + (3 * nc + 1) * m; }
+    const int* frames() const { return i32() + (3 * nc + 2) * m; }
+    const int* cnt(size_t copy) const { return i32() + (3 * nc + 3 + copy) * m; }
+    const long long* code_map() const { return reinterpret_cast<const long long*>(dev + stream_rag_map_at(nc, nr, m)); }
+};
+
 struct StreamBase {
     mimi_engine* e = nullptr;
     int B = 0, K = 0, max_n = 0, cap = 0;
@@ -3450,31 +3522,43 @@ struct StreamBase {
     float* rope_host = nullptr;  // pinned: [cos | sin] of the step's rows (a slot step: of every item's, in step order)
     // a slot step's tables, [B] first rows (int64) then [B] slots (int32): the pinned image and its device copy
     char *tab_host = nullptr, *tab_dev = nullptr;
+    // a ragged step's tables (StreamLayout: per stage the items' rows and first rows, the carry copies' offsets and
+    // counts): the pinned image and its device copy, sized for B items
+    char *rag_host = nullptr, *rag_dev = nullptr;
+    size_t rag_bytes = 0;
     int64_t max_pos() const { return *std::max_element(pos.begin(), pos.end()); }
 };
 struct mimi_decode_stream : StreamBase {};
 
 // The RoPE rows of a stream step by ensure_rope's expressions, into a pinned image: item b's rows 2 pos0[b] ..
 // 2 pos0[b] + R - 1 at table rows b R .. (cs, sn: [items * R][head_dim / 2]).  Shared by the decode and the encode stream.
-static void stream_rope_rows(const mimi_config& c, const int64_t* pos0, int items, int R, float* cs, float* sn) {
+// frames (a ragged step; else null): item b has 2 frames[b] rows, at table rows 2 off[b] .. (off = the prefix sum)
+static void stream_rope_rows(const mimi_config& c, const int64_t* pos0, int items, int R, float* cs, float* sn,
+                             const int32_t* frames = nullptr) {
     const int half = c.head_dim / 2;
     for (int d = 0; d < half; ++d) {
         const float expo = (float)(2 * d) / (float)c.head_dim;
         const float pw = (float)std::pow((double)c.rope_theta, (double)expo);
         const float inv = 1.0f / pw;
+        size_t row0 = 0;
         for (int b = 0; b < items; ++b) {
             const int64_t P = 2 * pos0[b];
-            for (int i = 0; i < R; ++i) {
+            const int Rb = frames ? 2 * frames[b] : R;
+            for (int i = 0; i < Rb; ++i) {
                 volatile float fr = inv * (float)(P + i);
-                cs[((size_t)b * R + i) * half + d] = (float)std::cos((double)fr);
-                sn[((size_t)b * R + i) * half + d] = (float)std::sin((double)fr);
+                cs[(row0 + i) * half + d] = (float)std::cos((double)fr);
+                sn[(row0 + i) * half + d] = (float)std::sin((double)fr);
             }
+            row0 += Rb;
         }
     }
 }
 
 // lays the state out for st->carry_h / carry_c (already planned) and allocates it, zeroed, with the pinned images
-static int stream_alloc(StreamBase* st, mimi_engine* e, const char* what, int batch, int K, int max_step_frames) {
+// (nr_up: the up convs of the stream's ragged step, whose tables' images the stream owns; code_map: with the RVQ's code
+// map behind them, one entry per frame of a step)
+static int stream_alloc(StreamBase* st, mimi_engine* e, const char* what, int batch, int K, int max_step_frames,
+                        int nr_up, bool code_map) {
     const mimi_config& c = e->cfg;
     st->e = e;
     st->B = batch;
@@ -3499,6 +3583,8 @@ static int stream_alloc(StreamBase* st, mimi_engine* e, const char* what, int ba
     const size_t tab_bytes = (size_t)batch * (sizeof(int64_t) + sizeof(int32_t));
     const size_t rc_ = take(rope_floats), rs_ = take(rope_floats);
     st->state_bytes = off * sizeof(float);
+    st->rag_bytes = stream_rag_map_at(st->carry_h.size(), nr_up, batch) +
+                    (code_map ? (size_t)batch * max_step_frames * sizeof(int64_t) : 0);
     hipError_t err = hipMalloc(reinterpret_cast<void**>(&st->state), st->state_bytes);
     if (err != hipSuccess) {
         (void)hipGetLastError();
@@ -3514,11 +3600,16 @@ static int stream_alloc(StreamBase* st, mimi_engine* e, const char* what, int ba
         (err = hipHostMalloc(reinterpret_cast<void**>(&st->rope_host), 2 * rope_floats * sizeof(float),
                              hipHostMallocDefault)) != hipSuccess ||
         (err = hipHostMalloc(reinterpret_cast<void**>(&st->tab_host), tab_bytes, hipHostMallocDefault)) != hipSuccess ||
-        (err = hipMalloc(reinterpret_cast<void**>(&st->tab_dev), tab_bytes)) != hipSuccess) {
+        (err = hipMalloc(reinterpret_cast<void**>(&st->tab_dev), tab_bytes)) != hipSuccess ||
+        (st->rag_bytes &&
+         ((err = hipHostMalloc(reinterpret_cast<void**>(&st->rag_host), st->rag_bytes, hipHostMallocDefault)) != hipSuccess ||
+          (err = hipMalloc(reinterpret_cast<void**>(&st->rag_dev), st->rag_bytes)) != hipSuccess))) {
         (void)hipGetLastError();
         (void)hipFree(st->state);
         if (st->rope_host) (void)hipHostFree(st->rope_host);
         if (st->tab_host) (void)hipHostFree(st->tab_host);
+        if (st->tab_dev) (void)hipFree(st->tab_dev);
+        if (st->rag_host) (void)hipHostFree(st->rag_host);
         return set_err(MIMI_ERR_HIP, "%s stream state: %s", what, hipGetErrorString(err));
     }
     return MIMI_OK;
@@ -3531,6 +3622,8 @@ static void stream_free(StreamBase* st) {
     if (st->rope_host) (void)hipHostFree(st->rope_host);
     if (st->tab_host) (void)hipHostFree(st->tab_host);
     if (st->tab_dev) (void)hipFree(st->tab_dev);
+    if (st->rag_host) (void)hipHostFree(st->rag_host);
+    if (st->rag_dev) (void)hipFree(st->rag_dev);
 }
 
 static int stream_reset_all(StreamBase* st) {
@@ -3570,11 +3663,17 @@ static const int32_t* stream_all_slots(const StreamBase* st, std::vector<int32_t
 
 // the arguments of a slot step (the pointers apart): every table index is checked here -- the kernels index the rings
 // and carries by slots[i] and read m entries
-static int stream_check_slots(const StreamBase* st, const char* what, const int32_t* slots, int32_t m, int32_t n) {
+// frames (a ragged step; else null): per item, each in [1, n] (n = the caller's max_frames)
+static int stream_check_slots(const StreamBase* st, const char* what, const int32_t* slots, int32_t m, int32_t n,
+                              const int32_t* frames = nullptr) {
     if (m < 1 || m > st->B)
         return set_err(MIMI_ERR_INVALID_ARGUMENT, "%s stream step over %d slots outside [1, %d]", what, m, st->B);
     if (n < 1 || n > st->max_n)
         return set_err(MIMI_ERR_INVALID_ARGUMENT, "%s stream step of %d frames outside [1, %d]", what, n, st->max_n);
+    for (int i = 0; frames && i < m; ++i)
+        if (frames[i] < 1 || frames[i] > n)
+            return set_err(MIMI_ERR_INVALID_ARGUMENT, "%s stream step: item %d brings %d frames outside [1, %d]", what, i,
+                           frames[i], n);
     std::vector<char> seen(st->B, 0);
     for (int i = 0; i < m; ++i) {
         if (slots[i] < 0 || slots[i] >= st->B)
@@ -3586,18 +3685,21 @@ static int stream_check_slots(const StreamBase* st, const char* what, const int3
 }
 
 // the listed slots' state before a step touches anything (slots == nullptr: all st->B in order)
-static int stream_step_check(const StreamBase* st, const char* what, const int32_t* slots, int m, int n) {
-    const int R = 2 * n;
+static int stream_step_check(const StreamBase* st, const char* what, const int32_t* slots, int m, int n,
+                             const int32_t* frames = nullptr) {
     auto slot_of = [&](int i) { return slots ? slots[i] : i; };
     for (int i = 0; i < m; ++i)
         if (st->failed[slot_of(i)])
             return set_err(MIMI_ERR_STATE, "%s stream: a step of slot %d failed; mimi_%s_stream_reset(_slot) first", what,
                            slot_of(i), what);
     // RoPE multiplies inv_freq by (float)row: exact only while the row fits float32's 24-bit significand
-    for (int i = 0; i < m; ++i)
+    for (int i = 0; i < m; ++i) {
+        const int R = 2 * (frames ? frames[i] : n);  // a listed slot at its own count
         if (2 * st->pos[slot_of(i)] + R > (1LL << 24))
             return set_err(MIMI_ERR_UNSUPPORTED, "%s stream: row %lld no longer fits a float32 exactly", what,
                            (long long)(2 * st->pos[slot_of(i)] + R));
+    }
+    const int R = 2 * n;
     if (slots && (int64_t)m * R > 0x7fffffffLL)
         return set_err(MIMI_ERR_UNSUPPORTED, "%s stream: %d slots x %d rows exceed the 32-bit row range", what, m, R);
     return MIMI_OK;
@@ -3607,8 +3709,9 @@ static int stream_step_check(const StreamBase* st, const char* what, const int32
 // reads them any more).  The tables: item i's first frame and its slot.  The RoPE rows: lock-step rows P .. P + R - 1, a
 // slot step item i's rows 2 pos_i .. 2 pos_i + R - 1 at table rows i R ..  pos0: the items' first frames.  From here on
 // a failure leaves the listed slots half-advanced: they are marked failed until stream_step_done.
+// frames (a ragged step, slots set; else null): item i has 2 frames[i] RoPE rows, packed in step order.
 static int stream_step_upload(StreamBase* st, const int32_t* slots, int m, int n, std::vector<int64_t>* pos0,
-                              hipStream_t s) {
+                              hipStream_t s, const int32_t* frames = nullptr) {
     const mimi_config& c = st->e->cfg;
     const int R = 2 * n, half = c.head_dim / 2;
     auto slot_of = [&](int i) { return slots ? slots[i] : i; };
@@ -3623,10 +3726,14 @@ static int stream_step_upload(StreamBase* st, const int32_t* slots, int m, int n
         }
     }
     const int items = slots ? m : 1;
-    const size_t rope_rows = (size_t)items * R;
+    size_t rope_rows = (size_t)items * R;
+    if (frames) {
+        rope_rows = 0;
+        for (int i = 0; i < m; ++i) rope_rows += 2 * (size_t)frames[i];
+    }
     float* cs = st->rope_host;
     float* sn = cs + rope_rows * half;
-    stream_rope_rows(c, pos0->data(), items, R, cs, sn);
+    stream_rope_rows(c, pos0->data(), items, R, cs, sn, frames);
     for (int i = 0; i < m; ++i) st->failed[slot_of(i)] = 1;
     HIP_TRY(hipMemcpyAsync(st->rope_cos, cs, rope_rows * half * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(st->rope_sin, sn, rope_rows * half * 4, hipMemcpyHostToDevice, s));
@@ -3651,11 +3758,11 @@ static StreamTabs stream_tabs(const StreamBase* st, bool slots) {
             reinterpret_cast<const int*>(st->tab_dev + (size_t)st->B * sizeof(int64_t))};
 }
 
-static void stream_step_done(StreamBase* st, const int32_t* slots, int m, int n) {
+static void stream_step_done(StreamBase* st, const int32_t* slots, int m, int n, const int32_t* frames = nullptr) {
     for (int i = 0; i < m; ++i) {
         const int b = slots ? slots[i] : i;
         st->failed[b] = 0;
-        st->pos[b] += n;
+        st->pos[b] += frames ? frames[i] : n;
     }
 }
 
@@ -3678,42 +3785,126 @@ static void stream_carry_plan(const mimi_config& c, std::vector<int>* h, std::ve
     ch->push_back(C);
 }
 
-// a step's workspace: flat-row buffers of the dequantizer and the transformer, then per stage its [B][H + rows][C]
+// the decode stream's stages in the order of its carries (stream_carry_plan), with their rates
+static std::vector<StreamStage> stream_stages_decode(const mimi_config& c) {
+    std::vector<int> h, ch;
+    stream_carry_plan(c, &h, &ch);
+    std::vector<StreamStage> st;
+    int64_t f = 2;
+    st.push_back({h[0], 1, ch[0]});  // the embedding in front of the upsample
+    st.push_back({h[1], 2, ch[1]});  // the transformer output in front of decoder.layers.0
+    for (int s = 0; s < c.num_ratios; ++s) {
+        st.push_back({h[2 + 2 * s], f, ch[2 + 2 * s]});  // up conv s's ELU'd input
+        f *= c.upsampling_ratios[s];
+        st.push_back({h[3 + 2 * s], f, ch[3 + 2 * s]});  // its raw output, the residual block's input
+    }
+    st.push_back({h.back(), f, ch.back()});  // the last conv's ELU'd input
+    return st;
+}
+
+// a step's workspace: flat-row buffers of the dequantizer and the transformer, then per stage its packed blocks (H m +
+// f sum rows: [m][H + f n][C] when every item brings n frames).  B items, `sum` frames in all.
 struct StreamWs {
     float *sums, *emb, *t0, *t1, *qkv, *att, *ff, *xin, *tap;
     std::vector<float*> xe, raw;  // xe[s]: ELU'd input of up conv s (xe[num_ratios]: of the last conv); raw[s]: its output
     size_t bytes;
 };
-static StreamWs stream_ws_layout(const mimi_engine* e, int B, int n, bool taps) {
-    const mimi_config& c = e->cfg;
-    const size_t h = c.hidden_size, Bn = (size_t)B * n, R = 2 * (size_t)n;
+static StreamWs stream_ws_layout(const mimi_config& c, void* ws, int B, int64_t sum, bool taps) {
+    const size_t h = c.hidden_size, Bn = (size_t)sum;
     StreamWs w{};
-    char* base = reinterpret_cast<char*>(e->dws);
+    char* base = reinterpret_cast<char*>(ws);
     size_t off = 0;
     auto take = [&](size_t floats) {
         float* p = reinterpret_cast<float*>(base + off);
         off += pad256(floats * sizeof(float));
         return p;
     };
+    const size_t BR = 2 * Bn;  // the 25 Hz rows of all items
     w.sums = take(Bn * 2 * c.vq_hidden_dim);
-    w.emb = take((size_t)B * (1 + n) * h);
-    w.t0 = take(B * R * h);
-    w.t1 = take(B * R * h);
-    w.qkv = take(B * R * 3 * c.num_attention_heads * c.head_dim);
-    w.att = take(B * R * h);
-    w.ff = take(B * R * c.intermediate_size);
-    w.xin = take((size_t)B * (c.kernel_size - 1 + R) * h);
-    size_t C = (size_t)c.num_filters << c.num_ratios, len = R;
-    w.tap = take(taps ? B * R * C : 0);
+    w.emb = take(((size_t)B + Bn) * h);
+    w.t0 = take(BR * h);
+    w.t1 = take(BR * h);
+    w.qkv = take(BR * 3 * c.num_attention_heads * c.head_dim);
+    w.att = take(BR * h);
+    w.ff = take(BR * c.intermediate_size);
+    w.xin = take(((size_t)B * (c.kernel_size - 1) + BR) * h);
+    size_t C = (size_t)c.num_filters << c.num_ratios, len = BR;
+    w.tap = take(taps ? BR * C : 0);
     for (int s = 0; s < c.num_ratios; ++s) {
-        w.xe.push_back(take((size_t)B * (1 + len) * C));
+        w.xe.push_back(take(((size_t)B + len) * C));
         len *= c.upsampling_ratios[s];
         C /= 2;
-        w.raw.push_back(take((size_t)B * (2 + len) * C));
+        w.raw.push_back(take(((size_t)B * 2 + len) * C));
     }
-    w.xe.push_back(take((size_t)B * (c.last_kernel_size - 1 + len) * C));
+    w.xe.push_back(take(((size_t)B * (c.last_kernel_size - 1) + len) * C));
     w.bytes = off;
     return w;
+}
+
+// The pinned image of a ragged decode step's tables (StreamRag) for the layout L and the listed slots.  Every offset is
+// worked out here from L alone; before anything is written, every block is checked against its tensor (it ends where
+// the next one starts, the last one at the tensor's end, inside the 32-bit row range), every row against the 16-byte
+// copies (C a multiple of 4), every slot against the state and the stage list against the stream's carries.  The
+// kernels index by nothing else.  *most: the largest count of any carry copy.
+// dec: a decode stream (the transformer's rows are moved by a carry copy, the up convs take element offsets); else an
+// encode stream (stage 0 is conv 0's 8 samples: no chunk rows, f = 0; K > 0 levels: the code map for rows of
+// L.stride frames behind the image).
+static int stream_rag_fill(const StreamBase* st, const StreamLayout& L, const int32_t* slots, char* img, int* most,
+                           bool dec = true, int K = 0) {
+    const size_t nc = L.st.size(), nr = dec ? st->e->cfg.num_ratios : 0, m = L.m;
+    if (nc != st->carry_h.size() || nc != 3 + 2 * (size_t)st->e->cfg.num_ratios || !img || L.m < 1 || L.m > st->B ||
+        stream_rag_map_at(nc, nr, m) + (dec ? 0 : (size_t)L.sum * sizeof(int64_t)) > st->rag_bytes)
+        return set_err(MIMI_ERR_STATE, "stream: a ragged step's tables do not fit the stream");
+    for (size_t j = 0; j < nc; ++j) {
+        const StreamStage& g = L.st[j];
+        if (g.C < 4 || g.C % 4 || g.H != st->carry_h[j] || g.C != st->carry_c[j] || g.f < ((dec || j) ? 1 : 0) ||
+            L.rows(j) > 0x7fffffffLL)
+            return set_err(MIMI_ERR_STATE, "decode stream: stage %zu of a ragged step (%d carry rows, %d channels)", j, g.H, g.C);
+        for (int i = 0; i < L.m; ++i) {
+            const int64_t end = L.base(j, i) + g.H + L.len(j, i);
+            if (L.frames[i] < 1 || L.base(j, i) < 0 || end != (i + 1 < L.m ? L.base(j, i + 1) : L.rows(j)))
+                return set_err(MIMI_ERR_STATE, "decode stream: item %d's block of stage %zu leaves its tensor", i, j);
+        }
+    }
+    for (int i = 0; i < L.m; ++i)
+        if (slots[i] < 0 || slots[i] >= st->B) return set_err(MIMI_ERR_STATE, "decode stream: slot %d", slots[i]);
+    StreamRag r{img, nc, nr, m};
+    long long* i64 = const_cast<long long*>(r.i64());
+    int* i32 = const_cast<int*>(r.i32());
+    auto coff = [&](size_t copy, int side, int i) -> long long& { return i64[(nr + 2 * copy + side) * m + i]; };
+    auto cnt = [&](size_t copy, int i) -> int& { return i32[(3 * nc + 3 + copy) * m + i]; };
+    *most = 0;
+    for (int i = 0; i < L.m; ++i) {
+        for (size_t j = 0; j < nc; ++j) {
+            const int64_t C = L.st[j].C, H = L.st[j].H, hc = H * C;
+            i32[(3 * j) * m + i] = (int)L.len(j, i);
+            i32[(3 * j + 1) * m + i] = (int)L.base(j, i);
+            i32[(3 * j + 2) * m + i] = (int)(H + L.len(j, i));
+            // carry-in: the slot's rows of the state -> the head of the item's block; carry-out: the last H rows of the
+            // item's own [carry | chunk] (also where the chunk is shorter than H) -> the slot's rows of the state
+            coff(j, 0, i) = (int64_t)slots[i] * hc;
+            coff(j, 1, i) = L.base(j, i) * C;
+            coff(nc + 1 + j, 0, i) = (L.base(j, i) + L.len(j, i)) * C;
+            coff(nc + 1 + j, 1, i) = (int64_t)slots[i] * hc;
+            cnt(j, i) = cnt(nc + 1 + j, i) = (int)hc;
+            *most = std::max(*most, (int)hc);
+        }
+        // decode: the transformer's flat rows behind decoder.layers.0's carry (stage 1)
+        coff(nc, 0, i) = dec ? 2 * (int64_t)L.off[i] * L.st[1].C : 0;
+        coff(nc, 1, i) = dec ? (L.base(1, i) + L.st[1].H) * L.st[1].C : 0;
+        cnt(nc, i) = dec ? (int)(L.len(1, i) * L.st[1].C) : 0;
+        *most = std::max(*most, cnt(nc, i));
+        i32[(3 * nc) * m + i] = L.off[i];
+        i32[(3 * nc + 1) * m + i] = 2 * L.off[i];
+        i32[(3 * nc + 2) * m + i] = L.frames[i];
+        for (size_t s = 0; s < nr; ++s) i64[s * m + i] = L.base(3 + 2 * s, i) * L.st[3 + 2 * s].C;
+    }
+    if (!dec) {  // packed frame off[i] + t -> codes[(i K + level) stride + t]
+        long long* map = const_cast<long long*>(r.code_map());
+        for (int i = 0; i < L.m; ++i)
+            for (int t = 0; t < L.frames[i]; ++t) map[L.off[i] + t] = (int64_t)i * K * L.stride + t;
+    }
+    return MIMI_OK;
 }
 
 extern "C" int mimi_decode_stream_create(mimi_engine* e, int32_t batch, int32_t K, int32_t max_step_frames,
@@ -3731,7 +3922,7 @@ extern "C" int mimi_decode_stream_create(mimi_engine* e, int32_t batch, int32_t 
     HIP_TRY(hipSetDevice(e->device));
     std::unique_ptr<mimi_decode_stream> st(new mimi_decode_stream);
     stream_carry_plan(c, &st->carry_h, &st->carry_c);
-    if ((rc = stream_alloc(st.get(), e, "decode", batch, K, max_step_frames))) return rc;
+    if ((rc = stream_alloc(st.get(), e, "decode", batch, K, max_step_frames, c.num_ratios, false))) return rc;
     *out = st.release();
     return MIMI_OK;
 }
@@ -3773,17 +3964,35 @@ static int save_tap_strided(mimi_engine* e, const char* name, const float* src, 
     return MIMI_OK;
 }
 
+// a tap of a ragged step's stage j (buf: its packed [carry | chunk] blocks): the items' chunks without their carry rows,
+// packed [1][f sum][C] in step order as ragged decode's taps -- one device copy per item by the layout
+static int save_tap_packed(mimi_engine* e, const char* name, const float* buf, const StreamLayout& L, size_t j,
+                           hipStream_t s) {
+    if (!e->taps) return MIMI_OK;
+    const StreamStage& g = L.st[j];
+    float* d;
+    int rc;
+    if ((rc = tap_buffer(e, name, 1, g.f * L.sum, g.C, &d))) return rc;
+    for (int i = 0; i < L.m; ++i)
+        HIP_TRY(hipMemcpyAsync(d + g.f * L.off[i] * g.C, buf + (L.base(j, i) + g.H) * g.C,
+                               (size_t)(L.len(j, i) * g.C) * 4, hipMemcpyDeviceToDevice, s));
+    return MIMI_OK;
+}
+
 // The two callables that make transformer_f32 the transformer section of a stream step, decode or encode: B items of
 // R rows each, the step's RoPE rows in the stream's tables, the attention on the stream's rings.  pos_tab / slot_tab:
 // the slot step's device tables, both nullptr in lock-step; pos0: per item (lock-step: [0] for all) the frame its first
 // row belongs to.
 // q/k/v.  Lock-step: batched, row m of an item is absolute row P + m and the tables hold rows P ..; slots: the flat
 // rows, the tables hold every item's rows in step order
-static auto stream_qkv_args(const StreamBase* st, const float* t1, float* qkv, int B, int R, bool slots) {
+// (frows: the flat rows of all items, B R, or in a ragged step the sum of the items' rows)
+static auto stream_qkv_args(const StreamBase* st, const float* t1, float* qkv, int B, int R, bool slots,
+                            int64_t frows = 0) {
     const mimi_config& c = st->e->cfg;
     const int Hd = c.hidden_size, HD = c.num_attention_heads * c.head_dim;
+    if (!frows) frows = (int64_t)B * R;
     return [=](const DevXfmr& x) {
-        GemmArgs aq = linear_args(t1, slots ? (int64_t)B * R : R, Hd, x.wqkv, 3 * HD, qkv);
+        GemmArgs aq = linear_args(t1, slots ? frows : R, Hd, x.wqkv, 3 * HD, qkv);
         if (!slots) {
             aq.batch = B;
             aq.a_bstride = (int64_t)R * Hd;
@@ -3796,28 +4005,47 @@ static auto stream_qkv_args(const StreamBase* st, const float* t1, float* qkv, i
     };
 }
 // the attention on the rings, then the step's k / v rows into them
+// (a ragged step: rlen / roff the items' rows and first rows in the packed qkv / att, frames the host's counts, R the
+// longest item's rows)
 static auto stream_attention(const StreamBase* st, const float* qkv, float* att, int B, int R, const int64_t* pos0,
                              const long long* pos_tab, const int* slot_tab, const char* prefix, Recorder& rec,
-                             hipStream_t s) {
+                             hipStream_t s, const int* rlen = nullptr, const int* roff = nullptr,
+                             const int32_t* frames = nullptr) {
     const mimi_config& c = st->e->cfg;
     const int Hd = c.hidden_size, H = c.num_attention_heads, Dh = c.head_dim, W = c.sliding_window;
     const int64_t P = 2 * pos0[0];  // lock-step: the absolute 25 Hz row of the step's first
-    const int64_t frows = (int64_t)B * R;
+    int64_t frows = (int64_t)B * R;
     double att_flops = 0;
     for (int b = 0; b < (pos_tab ? B : 1); ++b)
-        for (int i = 0; i < R; ++i) att_flops += 4.0 * Dh * std::min<int64_t>(2 * pos0[b] + i + 1, W);
+        for (int i = 0; i < (frames ? 2 * frames[b] : R); ++i)
+            att_flops += 4.0 * Dh * std::min<int64_t>(2 * pos0[b] + i + 1, W);
     att_flops *= (double)H * (pos_tab ? 1 : B);
+    if (frames) {
+        frows = 0;
+        for (int b = 0; b < B; ++b) frows += 2 * (int64_t)frames[b];
+    }
     const std::string pre(prefix);
     return [=, &rec](size_t l) {
         float* kr = st->kring + l * st->ring_layer;
         float* vr = st->vring + l * st->ring_layer;
         const char* kname = "?";
-        LAUNCH_TRY(launch_attention_stream(qkv, kr, vr, att, B, R, H, Dh, W, st->cap, P, pos_tab, slot_tab,
-                                           1.0f / std::sqrt((float)Dh), s, &kname),
-                   "attention (stream)");
+        const float sc = 1.0f / std::sqrt((float)Dh);
+        if (rlen)
+            LAUNCH_TRY(launch_attention_stream_ragged(qkv, kr, vr, att, B, R, H, Dh, W, st->cap, pos_tab, slot_tab, rlen,
+                                                      roff, sc, s, &kname),
+                       "attention (stream)");
+        else
+            LAUNCH_TRY(launch_attention_stream(qkv, kr, vr, att, B, R, H, Dh, W, st->cap, P, pos_tab, slot_tab, sc, s,
+                                               &kname),
+                       "attention (stream)");
         rec.mark(pre + "attention", att_flops, (double)frows * 4 * Hd * 4, kname);
-        LAUNCH_TRY(launch_attention_stream_append(qkv, kr, vr, B, R, H, Dh, st->cap, P, pos_tab, slot_tab, s, &kname),
-                   "kv append");
+        if (rlen)
+            LAUNCH_TRY(launch_attention_stream_append_ragged(qkv, kr, vr, B, R, H, Dh, st->cap, pos_tab, slot_tab, rlen,
+                                                             roff, s, &kname),
+                       "kv append");
+        else
+            LAUNCH_TRY(launch_attention_stream_append(qkv, kr, vr, B, R, H, Dh, st->cap, P, pos_tab, slot_tab, s, &kname),
+                       "kv append");
         rec.mark(pre + "kv_append", 0, (double)frows * 4 * H * Dh * 4, kname);
         return (int)MIMI_OK;
     };
@@ -3826,15 +4054,27 @@ static auto stream_attention(const StreamBase* st, const float* qkv, float* att,
 // the launches of one step over B items (the workspace w sized for it, the step's RoPE rows already enqueued).
 // slots == nullptr: the lock-step pass, B = st->B items that all stand at frame pos0[0].  Otherwise item i is slot
 // slots[i] at frame pos0[i] (host copies of the tables already enqueued to st->tab_dev).
-static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, int n, const int32_t* slots,
-                       const int64_t* pos0, const StreamWs& w, float* dev_audio, hipStream_t s) {
+// L: the step's layout.  Equal counts (!L.ragged): everything below runs on the scalars n = L.maxn, exactly the lock-step
+// / slot step.  Unequal counts (slots set, rg the tables' device image, carry_most the largest carry copy): the same
+// launches in the same order, each in its ragged form -- the flat-row stages unchanged on the sum of the rows, the convs
+// through the GEMM's packed-rows form, the per-item kernels with the item's rows and first row from the tables.
+static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, const StreamLayout& L, const StreamRag& rg,
+                       int carry_most, const int32_t* slots, const int64_t* pos0, const StreamWs& w, float* dev_audio,
+                       hipStream_t s) {
     mimi_engine* e = st->e;
     const mimi_config& c = e->cfg;
+    const int B = L.m, n = (int)L.maxn;
+    const bool RG = L.ragged;
     const int K = st->K, Hd = c.hidden_size, Dq = c.vq_hidden_dim;
     const int R = 2 * n, H0 = c.kernel_size - 1, HL = c.last_kernel_size - 1;
     const StreamTabs tabs = stream_tabs(st, slots != nullptr);
     const char* kname = "?";
-    auto carry = [&](const CarryTable& t) { return launch_stream_carry(t, B, tabs.slot, s, &kname); };
+    const size_t nc = L.st.size();
+    // a carry launch: `copy` = its first copy in the ragged tables (carry-in 0, the transformer's rows nc, carry-out nc + 1)
+    auto carry = [&](const CarryTable& t, size_t copy) {
+        if (RG) return launch_stream_carry_ragged(t, B, rg.coff(copy), rg.cnt(copy), carry_most, s, &kname);
+        return launch_stream_carry(t, B, tabs.slot, s, &kname);
+    };
     int rc;
     HIP_TRY(hipMemsetAsync(e->dec_flag, 0, sizeof(unsigned), s));
     Recorder rec{e, s};
@@ -3862,71 +4102,119 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
         outc.c[i] = {where[i] + rows[i] * st->carry_c[i], st->state + st->carry_off[i], bs, hc, (int)hc, CARRY_STATE_DST};
     }
     in.n = outc.n = (int)where.size();
-    LAUNCH_TRY(carry(in), "stream carry (in)");
+    if (RG)  // the tables hold every offset from its tensor's first element
+        for (size_t i = 0; i < where.size(); ++i) {
+            in.c[i].dst = where[i];
+            outc.c[i].src = where[i];
+        }
+    LAUNCH_TRY(carry(in, 0), "stream carry (in)");
     rec.mark("dec_carry", 0, 0, kname);
 
     // ---- quantizer.decode + upsample ----
-    LAUNCH_TRY(launch_rvq_decode(dev_codes, (long long)B * n, n, K, c.num_semantic_quantizers, c.codebook_size,
-                                 c.codebook_dim, e->cb_rows, w.sums, e->dec_flag, s, nullptr, nullptr, 0),
+    const int64_t Sn = L.sum, SR = 2 * L.sum;  // the frames and the 25 Hz rows of all items
+    LAUNCH_TRY(launch_rvq_decode(dev_codes, (long long)B * L.stride, (int)L.stride, K, c.num_semantic_quantizers,
+                                 c.codebook_size, c.codebook_dim, e->cb_rows, w.sums, e->dec_flag, s,
+                                 RG ? rg.len(0) : nullptr, RG ? rg.off1() : nullptr, RG ? n : 0),
                "rvq_decode");
-    rec.mark("dec_rvq", (double)B * n * K * Dq, (double)B * n * (K * Dq + 2 * Dq) * 4, "mimi::rvq_decode_kernel");
+    rec.mark("dec_rvq", (double)Sn * K * Dq, (double)Sn * (K * Dq + 2 * Dq) * 4,
+             RG ? "mimi::rvq_decode_ragged_kernel" : "mimi::rvq_decode_kernel");
     const int64_t emb_bs = (int64_t)(1 + n) * Hd;
     GemmArgs ap = linear_args(w.sums, n, 2 * Dq, e->outproj, Hd, w.emb + Hd);
     ap.batch = B;
     ap.a_bstride = (int64_t)n * 2 * Dq;
     ap.c_bstride = emb_bs;
+    if (RG) {  // the packed sums -> each item's block of the embedding, behind its carry row
+        ap.a_rows = ap.m_rows = rg.len(0);
+        ap.a_boff = rg.off1();
+        ap.c_boff = rg.base(0);
+    }
     LAUNCH_TRY(launch_gemm(ROLE_INPROJ, ap, s, &kname, PREC_F32), "output_proj");
-    rec.mark("dec_output_proj", 2.0 * B * n * 2 * Dq * Hd, (double)B * n * (2 * Dq + Hd) * 4, kname);
-    if ((rc = save_tap_strided(e, "quantized", w.emb + Hd, B, n, Hd, emb_bs, s))) return rc;
-    LAUNCH_TRY(launch_upsample_dw_hist(w.emb + Hd, e->upsample_w, w.t0, B, n, Hd, emb_bs, s), "upsample");
-    rec.mark("dec_upsample", 4.0 * B * R * Hd, 3.0 * B * n * Hd * 4, "mimi::upsample_dw_hist_kernel");
-    if ((rc = save_tap(e, "upsample", w.t0, B, R, Hd, s))) return rc;
+    rec.mark("dec_output_proj", 2.0 * Sn * 2 * Dq * Hd, (double)Sn * (2 * Dq + Hd) * 4, kname);
+    if (RG) {
+        LAUNCH_TRY(launch_upsample_dw_hist_ragged(w.emb + Hd, e->upsample_w, w.t0, B, n, Hd, rg.len(0), rg.off1(),
+                                                  rg.base(0), s),
+                   "upsample");
+        rec.mark("dec_upsample", 4.0 * SR * Hd, 3.0 * Sn * Hd * 4, "mimi::upsample_dw_hist_ragged_kernel");
+        if ((rc = save_tap_packed(e, "quantized", w.emb, L, 0, s))) return rc;
+    } else {
+        if ((rc = save_tap_strided(e, "quantized", w.emb + Hd, B, n, Hd, emb_bs, s))) return rc;
+        LAUNCH_TRY(launch_upsample_dw_hist(w.emb + Hd, e->upsample_w, w.t0, B, n, Hd, emb_bs, s), "upsample");
+        rec.mark("dec_upsample", 4.0 * B * R * Hd, 3.0 * B * n * Hd * 4, "mimi::upsample_dw_hist_kernel");
+    }
+    // (a ragged step's flat tensors are packed: tapped as one item of all rows, as ragged decode's)
+    if ((rc = RG ? save_tap(e, "upsample", w.t0, 1, SR, Hd, s) : save_tap(e, "upsample", w.t0, B, R, Hd, s))) return rc;
 
     // ---- decoder transformer with the stream's RoPE rows and ring attention ----
-    if ((rc = transformer_f32(e, e->dxf, w.t0, w.t1, w.qkv, w.att, w.ff, (int64_t)B * R, B, R, "dec_", rec, s,
-                              stream_qkv_args(st, w.t1, w.qkv, B, R, slots != nullptr),
-                              stream_attention(st, w.qkv, w.att, B, R, pos0, tabs.pos, tabs.slot, "dec_", rec, s))))
+    if ((rc = transformer_f32(e, e->dxf, w.t0, w.t1, w.qkv, w.att, w.ff, SR, RG ? 1 : B, RG ? SR : R, "dec_", rec, s,
+                              stream_qkv_args(st, w.t1, w.qkv, B, R, slots != nullptr, SR),
+                              stream_attention(st, w.qkv, w.att, B, R, pos0, tabs.pos, tabs.slot, "dec_", rec, s,
+                                               RG ? rg.len(1) : nullptr, RG ? rg.off2() : nullptr,
+                                               RG ? L.frames.data() : nullptr))))
         return rc;
     {  // the transformer's flat rows behind decoder.layers.0's carry
         CarryTable mv{};
         mv.c[0] = {w.t0, w.xin + (int64_t)H0 * Hd, (int64_t)R * Hd, (int64_t)(H0 + R) * Hd, R * Hd};
+        if (RG) mv.c[0].dst = w.xin;
         mv.n = 1;
-        LAUNCH_TRY(carry(mv), "stream carry (transformer rows)");  // (no state side: by the item's place either way)
-        rec.mark("dec_carry", 0, 2.0 * B * R * Hd * 4, kname);
+        LAUNCH_TRY(carry(mv, nc), "stream carry (transformer rows)");  // (no state side: by the item's place either way)
+        rec.mark("dec_carry", 0, 2.0 * SR * Hd * 4, kname);
     }
 
     // ---- SEANet decoder ----
     // a conv over `len` rows per item whose input has hh carry rows in front: the carry is read where conv_args pads
-    auto conv = [&](const DevConv& cv, const float* in, int hh, int64_t len, float* out, int64_t out_bs) {
+    // (`len`: of the longest item, what the launch covers.)  A ragged step: stage `sin`'s blocks -> stage `sout`'s, the
+    // item's rows and first rows from the tables; out already points behind the first block's carry rows
+    auto conv = [&](const DevConv& cv, const float* in, int hh, int64_t len, float* out, int64_t out_bs, size_t sin,
+                    size_t sout) {
         GemmArgs a = conv_args(cv, in, hh + len, out, len, B);
         a.a_off += (int64_t)hh * cv.cin;
         a.c_bstride = out_bs;
+        if (RG) {
+            a.a_rows = rg.alen(sin);
+            a.a_boff = rg.base(sin);
+            a.m_rows = rg.len(sin);
+            a.c_boff = rg.base(sout);
+        }
         return a;
     };
-    auto fl = [&](const GemmArgs& a) { return 2.0 * B * (double)a.M * a.N * a.K; };
-    auto by = [&](const GemmArgs& a) { return ((double)B * a.M * (a.a_rs + a.N) + (double)a.N * a.K) * 4; };
+    // (B a.M = the rows of all items with equal counts; a ragged step's are stage sin's f times the sum of the counts)
+    auto mrows = [&](const GemmArgs& a, size_t sin) { return RG ? (double)(L.st[sin].f * L.sum) : (double)B * a.M; };
+    auto fl = [&](const GemmArgs& a, size_t sin) { return 2.0 * mrows(a, sin) * a.N * a.K; };
+    auto by = [&](const GemmArgs& a, size_t sin) { return (mrows(a, sin) * (a.a_rs + a.N) + (double)a.N * a.K) * 4; };
     int C = c.num_filters << c.num_ratios;
+    // a stage's tap: [B][rows][C] with equal counts, packed [1][f sum][C] in a ragged step (buf: the stage's tensor)
+    auto tap_stage = [&](const char* name, const float* buf, size_t j) {
+        const StreamStage& g = L.st[j];
+        if (RG) return save_tap_packed(e, name, buf, L, j, s);
+        return save_tap_strided(e, name, buf + (int64_t)g.H * g.C, B, g.f * n, g.C, (g.H + g.f * n) * g.C, s);
+    };
     if (e->taps) {  // the raw layer-0 output (the pass itself only needs its ELU)
-        GemmArgs at = conv(e->dec_first, w.xin, H0, R, w.tap, (int64_t)R * C);
+        GemmArgs at = conv(e->dec_first, w.xin, H0, R, w.tap, (int64_t)R * C, 1, 1);
+        if (RG) at.c_boff = rg.off2();  // packed, no carry rows
         LAUNCH_TRY(launch_gemm(ROLE_DOWN, at, s, &kname, PREC_F32), "decoder conv 0 (tap)");
-        rec.mark("dec_conv0_tap", fl(at), by(at), kname);
-        if ((rc = save_tap(e, "dconv0", w.tap, B, R, C, s))) return rc;
+        rec.mark("dec_conv0_tap", fl(at, 1), by(at, 1), kname);
+        if ((rc = RG ? save_tap(e, "dconv0", w.tap, 1, SR, C, s) : save_tap(e, "dconv0", w.tap, B, R, C, s))) return rc;
     }
     int64_t len = R;
-    GemmArgs a0 = conv(e->dec_first, w.xin, H0, R, w.xe[0] + C, (1 + len) * C);
+    GemmArgs a0 = conv(e->dec_first, w.xin, H0, R, w.xe[0] + C, (1 + len) * C, 1, 2);
     LAUNCH_TRY(launch_gemm(ROLE_DOWN_ELU, a0, s, &kname, PREC_F32), "decoder conv 0");
-    rec.mark("dec_conv0", fl(a0), by(a0), kname);
-    if ((rc = save_tap_strided(e, "dconv0_elu", w.xe[0] + C, B, len, C, (1 + len) * C, s))) return rc;
+    rec.mark("dec_conv0", fl(a0, 1), by(a0, 1), kname);
+    if ((rc = tap_stage("dconv0_elu", w.xe[0], 2))) return rc;
     for (int si = 0; si < c.num_ratios; ++si) {
         const int r = c.upsampling_ratios[si], Co = C / 2;
         const int64_t olen = len * r;
+        const size_t sx = 2 + 2 * si;  // the stage of the up conv's input; its output is sx + 1, the block's sx + 2
         // [len][C] -> [len][r * C/2] = [len * r][C/2], behind the residual block's 2 carry rows
-        GemmArgs au = conv(e->dec_up[si], w.xe[si], 1, len, w.raw[si] + 2 * Co, (2 + olen) * Co);
+        GemmArgs au = conv(e->dec_up[si], w.xe[si], 1, len, w.raw[si] + 2 * Co, (2 + olen) * Co, sx, sx + 1);
+        if (RG) {  // a block of 2 + r len rows of Co starts at no multiple of the GEMM's r Co output row
+            au.c_boff = nullptr;
+            au.c_eoff = rg.eoff(si);
+        }
         LAUNCH_TRY(launch_gemm(ROLE_UPCONV, au, s, &kname, PREC_F32), "up conv");
         snprintf(nm, sizeof nm, "dec_up_s%d", si);
-        rec.mark(nm, fl(au), by(au), kname);
+        rec.mark(nm, fl(au, sx), by(au, sx), kname);
         snprintf(nm, sizeof nm, "up%d", si);
-        if ((rc = save_tap_strided(e, nm, w.raw[si] + 2 * Co, B, olen, Co, (2 + olen) * Co, s))) return rc;
+        if ((rc = tap_stage(nm, w.raw[si], sx + 1))) return rc;
         const int hn = si + 1 < c.num_ratios ? 1 : HL;  // the carry rows of the stage that reads this block's output
         ResArgs ra{};
         ra.x = w.raw[si] + 2 * Co;
@@ -3940,44 +4228,86 @@ static int stream_pass(mimi_decode_stream* st, const int32_t* dev_codes, int B, 
         ra.hist = 2;
         ra.x_bstride = (2 + olen) * Co;
         ra.y_bstride = (hn + olen) * Co;
+        if (RG) {
+            ra.ilen = rg.len(sx + 1);
+            ra.ioff = rg.base(sx + 1);
+            ra.yoff = rg.base(sx + 2);
+        }
         LAUNCH_TRY(launch_resblock(Co, ra, s, &kname), "decoder resblock");
         snprintf(nm, sizeof nm, "dec_res_s%d", si);
-        const double Hh = Co / c.compress;
-        rec.mark(nm, 2.0 * B * olen * (3.0 * Co * Hh + Hh * Co), (double)B * olen * 2 * Co * 4, kname);
+        const double Hh = Co / c.compress, orows = RG ? (double)(L.st[sx + 1].f * L.sum) : (double)B * olen;
+        rec.mark(nm, 2.0 * orows * (3.0 * Co * Hh + Hh * Co), orows * 2 * Co * 4, kname);
         snprintf(nm, sizeof nm, "dres%d_elu", si);
-        if ((rc = save_tap_strided(e, nm, ra.y, B, olen, Co, ra.y_bstride, s))) return rc;
+        if ((rc = tap_stage(nm, w.xe[si + 1], sx + 2))) return rc;
         C = Co;
         len = olen;
     }
-    LAUNCH_TRY(launch_final_conv_hist(w.xe[c.num_ratios] + (int64_t)HL * C, e->dec_last.w, e->dec_last.b, dev_audio, B,
-                                      len, C, c.last_kernel_size, (HL + len) * C, s),
-               "final conv");
-    rec.mark("dec_final", 2.0 * B * len * C * c.last_kernel_size, (double)B * len * (C + 1) * 4,
-             "mimi::final_conv_hist_kernel");
-    LAUNCH_TRY(carry(outc), "stream carry (out)");
+    if (RG) {  // the caller's padded rows: samples past an item's length are left alone
+        const double lrows = (double)(L.st[nc - 1].f * L.sum);
+        LAUNCH_TRY(launch_final_conv_hist_ragged(w.xe[c.num_ratios] + (int64_t)HL * C, e->dec_last.w, e->dec_last.b,
+                                                 dev_audio, B, L.st[nc - 1].f * L.stride, C, c.last_kernel_size,
+                                                 rg.len(nc - 1), rg.base(nc - 1), len, s),
+                   "final conv");
+        rec.mark("dec_final", 2.0 * lrows * C * c.last_kernel_size, lrows * (C + 1) * 4,
+                 "mimi::final_conv_hist_ragged_kernel");
+    } else {
+        LAUNCH_TRY(launch_final_conv_hist(w.xe[c.num_ratios] + (int64_t)HL * C, e->dec_last.w, e->dec_last.b, dev_audio,
+                                          B, len, C, c.last_kernel_size, (HL + len) * C, s),
+                   "final conv");
+        rec.mark("dec_final", 2.0 * B * len * C * c.last_kernel_size, (double)B * len * (C + 1) * 4,
+                 "mimi::final_conv_hist_kernel");
+    }
+    LAUNCH_TRY(carry(outc, nc + 1), "stream carry (out)");
     rec.mark("dec_carry", 0, 0, kname);
     return MIMI_OK;
 }
 
 // One step over the m listed slots (slots == nullptr: all st->B in order, at one position: the lock-step pass).
 // Called with the engine mutex held and every argument checked but the slots' state.
+// frames (mimi_decode_stream_step_ragged; else null): item i advances by frames[i] <= n frames, the caller's rows hold n.
+// Counts that are all n make the slot step itself: frames is dropped here and nothing below knows the difference.
 static int stream_step_locked(mimi_decode_stream* st, const int32_t* slots, int m, const int32_t* dev_codes, int n,
-                              float* dev_audio, hipStream_t s) {
+                              float* dev_audio, hipStream_t s, const int32_t* frames = nullptr) {
     mimi_engine* e = st->e;
     int rc;
-    if ((rc = stream_step_check(st, "decode", slots, m, n))) return rc;
+    if (frames && std::all_of(frames, frames + m, [&](int32_t f) { return f == n; })) frames = nullptr;
+    if ((rc = stream_step_check(st, "decode", slots, m, n, frames))) return rc;
+    StreamLayout L;
+    plan_stream(stream_stages_decode(e->cfg), frames, m, n, &L);
+    if (L.rows(L.st.size() - 1) > 0x7fffffffLL)
+        return set_err(MIMI_ERR_UNSUPPORTED, "decode stream: %lld rows exceed the 32-bit row range",
+                       (long long)L.rows(L.st.size() - 1));
     HIP_TRY(hipSetDevice(e->device));
-    if ((rc = ensure_dws(e, stream_ws_layout(e, m, n, e->taps).bytes))) return rc;  // (state untouched so far)
-    const StreamWs w = stream_ws_layout(e, m, n, e->taps);
+    if ((rc = ensure_dws(e, stream_ws_layout(e->cfg, nullptr, m, L.sum, e->taps).bytes))) return rc;  // (state untouched so far)
+    const StreamWs w = stream_ws_layout(e->cfg, e->dws, m, L.sum, e->taps);
     std::vector<int64_t> pos0;  // frames
-    if ((rc = stream_step_upload(st, slots, m, n, &pos0, s))) return rc;
-    if ((rc = stream_pass(st, dev_codes, m, n, slots, pos0.data(), w, dev_audio, s))) {
+    // a ragged step's tables: built and checked before anything is enqueued or a slot is marked (the previous step
+    // synchronised s before it returned: nothing reads the image any more)
+    StreamRag rg{};
+    int carry_most = 0;
+    if (L.ragged && (rc = stream_rag_fill(st, L, slots, st->rag_host, &carry_most))) return rc;
+    if ((rc = stream_step_upload(st, slots, m, n, &pos0, s, frames))) return rc;
+    if (L.ragged) {
+        const size_t bytes = stream_rag_bytes(L.st.size(), e->cfg.num_ratios, m);
+        HIP_TRY(hipMemcpyAsync(st->rag_dev, st->rag_host, bytes, hipMemcpyHostToDevice, s));
+        rg = StreamRag{st->rag_dev, L.st.size(), (size_t)e->cfg.num_ratios, (size_t)m};
+    }
+    if ((rc = stream_pass(st, dev_codes, L, rg, carry_most, slots, pos0.data(), w, dev_audio, s))) {
         (void)hipStreamSynchronize(s);
         return rc;
     }
-    if ((rc = save_tap(e, "audio", dev_audio, m, decode_upsampling(e->cfg) * n, 1, s))) return rc;
+    if (L.ragged && e->taps) {  // the padded rows' valid samples, packed [1][1920 sum][1]
+        const int64_t up = decode_upsampling(e->cfg);
+        float* d;
+        if ((rc = tap_buffer(e, "audio", 1, up * L.sum, 1, &d))) return rc;
+        for (int i = 0; i < m; ++i)
+            HIP_TRY(hipMemcpyAsync(d + up * L.off[i], dev_audio + (int64_t)i * up * n, (size_t)(up * L.frames[i]) * 4,
+                                   hipMemcpyDeviceToDevice, s));
+    } else if ((rc = save_tap(e, "audio", dev_audio, m, decode_upsampling(e->cfg) * n, 1, s))) {
+        return rc;
+    }
     if ((rc = read_decode_flag(e, s))) return rc;
-    stream_step_done(st, slots, m, n);
+    stream_step_done(st, slots, m, n, frames);
     return MIMI_OK;
 }
 
@@ -4005,6 +4335,104 @@ extern "C" int mimi_decode_stream_step_slots(mimi_decode_stream* st, const int32
     int rc;
     if ((rc = stream_check_slots(st, "decode", slots, m, n))) return rc;
     return stream_step_locked(st, slots, m, dev_codes, n, dev_audio, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mimi_decode_stream_step_ragged(mimi_decode_stream* st, const int32_t* slots, const int32_t* frames,
+                                              int32_t m, int32_t max_frames, const int32_t* dev_codes, float* dev_audio,
+                                              void* stream) {
+    if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
+    mimi_engine* e = st->e;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!slots || !frames || !dev_codes || !dev_audio)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "decode stream step: null argument");
+    int rc;
+    if ((rc = stream_check_slots(st, "decode", slots, m, max_frames, frames))) return rc;
+    return stream_step_locked(st, slots, m, dev_codes, max_frames, dev_audio, reinterpret_cast<hipStream_t>(stream),
+                              frames);
+}
+
+static int encode_step_layout(const mimi_config& c, const int32_t* frames, int32_t m, int32_t max_frames,
+                              std::vector<StreamStage>* st, StreamLayout* L, std::vector<int64_t>* byte_offset,
+                              int64_t* bytes);  // (with the encode stream, below)
+// The layout of a ragged step without a device: what stream_step_locked plans, from the configuration alone.
+extern "C" int mimi_stream_step_layout(const mimi_config* cfg, int32_t direction, const int32_t* frames, int32_t m,
+                                       int32_t max_frames, int32_t taps, int32_t* n_stages, int32_t* carry_rows,
+                                       int32_t* rate, int32_t* channels, int64_t* byte_offset, int64_t* first_row,
+                                       int64_t* row_count, int64_t* workspace_bytes) {
+    if (!cfg || !frames || !n_stages || !carry_rows || !rate || !channels || !byte_offset || !first_row || !row_count ||
+        !workspace_bytes)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "stream step layout: null argument");
+    if (direction != MIMI_STREAM_DECODE && direction != MIMI_STREAM_ENCODE)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "stream step layout: direction %d", direction);
+    if (m < 1 || m > 65535) return set_err(MIMI_ERR_INVALID_ARGUMENT, "stream step layout over %d items outside [1, 65535]", m);
+    if (max_frames < 1 || max_frames > (1 << 20))
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "stream step layout: max_frames %d outside [1, 2^20]", max_frames);
+    for (int i = 0; i < m; ++i)
+        if (frames[i] < 1 || frames[i] > max_frames)
+            return set_err(MIMI_ERR_INVALID_ARGUMENT, "stream step layout: item %d brings %d frames outside [1, %d]", i,
+                           frames[i], max_frames);
+    // every field the stage list and the workspace are made of
+    bool ok = cfg->num_ratios >= 1 && cfg->num_ratios <= 6 && cfg->hidden_size >= 4 && cfg->hidden_size <= (1 << 16) &&
+              cfg->hidden_size % 4 == 0 && cfg->num_filters >= 4 && cfg->num_filters <= (1 << 12) &&
+              cfg->num_filters % 4 == 0 && cfg->kernel_size >= 1 && cfg->kernel_size <= 64 &&
+              cfg->last_kernel_size >= 1 && cfg->last_kernel_size <= 64 && cfg->vq_hidden_dim >= 1 &&
+              cfg->vq_hidden_dim <= (1 << 16) && cfg->num_attention_heads >= 1 && cfg->num_attention_heads <= 4096 &&
+              cfg->head_dim >= 1 && cfg->head_dim <= 4096 && cfg->intermediate_size >= 1 &&
+              cfg->intermediate_size <= (1 << 20);
+    for (int s = 0; ok && s < cfg->num_ratios; ++s) ok = cfg->upsampling_ratios[s] >= 1 && cfg->upsampling_ratios[s] <= 64;
+    if (!ok)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "stream step layout: a configuration field outside the range a stream takes");
+    if (direction == MIMI_STREAM_ENCODE) {
+        std::vector<StreamStage> est;
+        StreamLayout EL;
+        std::vector<int64_t> at;
+        int64_t bytes = 0;
+        int rc;
+        if ((rc = encode_step_layout(*cfg, frames, m, max_frames, &est, &EL, &at, &bytes))) return rc;
+        if (est.size() > MIMI_STREAM_MAX_STAGES) return set_err(MIMI_ERR_UNSUPPORTED, "stream step layout: %zu stages", est.size());
+        if (EL.rows(1) > 0x7fffffffLL || EL.rows(2) > 0x7fffffffLL)
+            return set_err(MIMI_ERR_UNSUPPORTED, "stream step layout: %lld rows exceed the 32-bit row range", (long long)EL.rows(2));
+        *n_stages = (int32_t)est.size();
+        for (size_t j = 0; j < est.size(); ++j) {
+            carry_rows[j] = est[j].H;
+            rate[j] = (int32_t)est[j].f;
+            channels[j] = est[j].C;
+            byte_offset[j] = at[j];
+            for (int i = 0; i < m; ++i) {
+                first_row[j * m + i] = EL.base(j, i);
+                row_count[j * m + i] = est[j].H + EL.len(j, i);
+            }
+        }
+        *workspace_bytes = bytes;
+        return MIMI_OK;
+    }
+    StreamLayout L;
+    plan_stream(stream_stages_decode(*cfg), frames, m, max_frames, &L);
+    const size_t nc = L.st.size();
+    if (nc > MIMI_STREAM_MAX_STAGES) return set_err(MIMI_ERR_UNSUPPORTED, "stream step layout: %zu stages", nc);
+    if (L.rows(nc - 1) > 0x7fffffffLL)
+        return set_err(MIMI_ERR_UNSUPPORTED, "stream step layout: %lld rows exceed the 32-bit row range",
+                       (long long)L.rows(nc - 1));
+    const StreamWs w = stream_ws_layout(*cfg, nullptr, m, L.sum, taps != 0);
+    std::vector<const float*> where = {w.emb, w.xin};
+    for (int s = 0; s < cfg->num_ratios; ++s) {
+        where.push_back(w.xe[s]);
+        where.push_back(w.raw[s]);
+    }
+    where.push_back(w.xe[cfg->num_ratios]);
+    *n_stages = (int32_t)nc;
+    for (size_t j = 0; j < nc; ++j) {
+        carry_rows[j] = L.st[j].H;
+        rate[j] = (int32_t)L.st[j].f;
+        channels[j] = L.st[j].C;
+        byte_offset[j] = (int64_t)reinterpret_cast<uintptr_t>(where[j]);  // (laid out from a null base)
+        for (int i = 0; i < m; ++i) {
+            first_row[j * m + i] = L.base(j, i);
+            row_count[j * m + i] = L.st[j].H + L.len(j, i);
+        }
+    }
+    *workspace_bytes = (int64_t)w.bytes;
+    return MIMI_OK;
 }
 
 // ================================================================================================
@@ -4085,39 +4513,59 @@ struct EncStreamWs {
     float *t0, *t1, *qkv, *att, *ff, *dsin, *dsout, *proj;
     void* rvq;
     size_t bytes;
+    std::vector<size_t> at;  // every buffer's byte offset, in the order they are taken
 };
-static EncStreamWs enc_stream_ws_layout(const mimi_engine* e, int B, int n) {
-    const mimi_config& c = e->cfg;
-    const size_t h = c.hidden_size, R = 2 * (size_t)n;
+// the encode stream's stages in the order of its carries (enc_stream_carry_plan), with their rates: conv 0's 8 samples
+// (no chunk rows of its own: the audio stays in the caller's rows), then every [carry | chunk] tensor
+static std::vector<StreamStage> stream_stages_encode(const mimi_config& c) {
+    std::vector<int> h, ch;
+    enc_stream_carry_plan(c, &h, &ch);
+    std::vector<StreamStage> st;
+    st.push_back({h[0], 0, ch[0]});
+    int64_t f = frame_samples(c);
+    for (int s = 0; s < c.num_ratios; ++s) {
+        st.push_back({h[1 + 2 * s], f, ch[1 + 2 * s]});  // block s's raw input
+        st.push_back({h[2 + 2 * s], f, ch[2 + 2 * s]});  // its ELU'd output, down conv s's input
+        f /= enc_ratio(c, s);
+    }
+    st.push_back({h[h.size() - 2], f, ch[ch.size() - 2]});  // the final conv's input
+    st.push_back({h.back(), f, ch.back()});                  // the downsample's input
+    return st;
+}
+
+// B items, `sum` frames in all: every stage's tensor holds H B + f sum rows ([B][H + f n][C] when every item brings n)
+static EncStreamWs enc_stream_ws_layout(const mimi_config& c, void* ws, int B, int64_t sum) {
+    const size_t h = c.hidden_size, SR = 2 * (size_t)sum;
     EncStreamWs w{};
     // (sized before the workspace exists: without a base only the byte count is formed, no pointer)
-    char* base = reinterpret_cast<char*>(e->dws);
+    char* base = reinterpret_cast<char*>(ws);
     size_t off = 0;
     auto take = [&](size_t floats) {
+        w.at.push_back(off);
         float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
         off += pad256(floats * sizeof(float));
         return p;
     };
     w.a_hist = take((size_t)B * 8);
     w.a_tail = take((size_t)B * 8);
-    size_t C = c.num_filters, len = (size_t)frame_samples(c) * n;
+    size_t C = c.num_filters, len = (size_t)frame_samples(c) * sum;  // the rows of all items
     for (int s = 0; s < c.num_ratios; ++s) {
-        w.x.push_back(take((size_t)B * (c.residual_kernel_size - 1 + len) * C));
-        w.y.push_back(take((size_t)B * (enc_ratio(c, s) + len) * C));
+        w.x.push_back(take(((size_t)B * (c.residual_kernel_size - 1) + len) * C));
+        w.y.push_back(take(((size_t)B * enc_ratio(c, s) + len) * C));
         len /= enc_ratio(c, s);
         C *= 2;
     }
-    w.xl = take((size_t)B * (c.last_kernel_size - 1 + len) * C);
-    w.t0 = take(B * R * h);
-    w.t1 = take(B * R * h);
-    w.qkv = take(B * R * 3 * c.num_attention_heads * c.head_dim);
-    w.att = take(B * R * h);
-    w.ff = take(B * R * c.intermediate_size);
-    w.dsin = take((size_t)B * (c.downsample_kernel - c.downsample_stride + R) * h);
-    w.dsout = take((size_t)B * n * h);
-    w.proj = take((size_t)B * n * 2 * c.vq_hidden_dim);
+    w.xl = take(((size_t)B * (c.last_kernel_size - 1) + len) * C);
+    w.t0 = take(SR * h);
+    w.t1 = take(SR * h);
+    w.qkv = take(SR * 3 * c.num_attention_heads * c.head_dim);
+    w.att = take(SR * h);
+    w.ff = take(SR * c.intermediate_size);
+    w.dsin = take(((size_t)B * (c.downsample_kernel - c.downsample_stride) + SR) * h);
+    w.dsout = take((size_t)sum * h);
+    w.proj = take((size_t)sum * 2 * c.vq_hidden_dim);
     w.rvq = base ? base + off : nullptr;
-    off += pad256(rvq_work_bytes((long long)B * n));
+    off += pad256(rvq_work_bytes((long long)sum));
     w.bytes = off;
     return w;
 }
@@ -4149,7 +4597,7 @@ extern "C" int mimi_encode_stream_create(mimi_engine* e, int32_t batch, int32_t 
     st->F = frame_samples(c);
     enc_stream_carry_plan(c, &st->carry_h, &st->carry_c);
     int rc;
-    if ((rc = stream_alloc(st.get(), e, "encode", batch, K, max_step_frames))) return rc;
+    if ((rc = stream_alloc(st.get(), e, "encode", batch, K, max_step_frames, 0, true))) return rc;
     *out = st.release();
     return MIMI_OK;
 }
@@ -4181,17 +4629,28 @@ extern "C" int64_t mimi_encode_stream_state_bytes(const mimi_encode_stream* st) 
 // the launches of one step over B items (the workspace w sized for it, the step's RoPE rows and tables already
 // enqueued).  slots == nullptr: the lock-step pass, B = st->B items that all stand at frame pos0[0].  Otherwise item i
 // is slot slots[i] at frame pos0[i].
-static int encode_stream_pass(mimi_encode_stream* st, const float* dev_audio, int B, int n, const int32_t* slots,
-                              const int64_t* pos0, const EncStreamWs& w, int32_t* dev_codes, hipStream_t s) {
+// LY: the step's layout (StreamLayout, stream_stages_encode).  Equal counts (!LY.ragged): everything runs on the scalars
+// n = LY.maxn, exactly the lock-step / slot step.  Unequal counts (slots set, rg the tables' device image, carry_most the
+// largest carry copy): the same launches in the same order, each in its ragged form, as the decode stream's.
+static int encode_stream_pass(mimi_encode_stream* st, const float* dev_audio, const StreamLayout& LY, const StreamRag& rg,
+                              int carry_most, const int32_t* slots, const int64_t* pos0, const EncStreamWs& w,
+                              int32_t* dev_codes, hipStream_t s) {
     mimi_engine* e = st->e;
     const mimi_config& c = e->cfg;
+    const int B = LY.m, n = (int)LY.maxn;
+    const bool RG = LY.ragged;
+    const size_t nc = LY.st.size();
+    const int64_t Sn = LY.sum, SR = 2 * LY.sum;  // the frames and the 25 Hz rows of all items
     const int K = st->K, Hd = c.hidden_size, Dq = c.vq_hidden_dim;
     const int R = 2 * n, HR = c.residual_kernel_size - 1, HL = c.last_kernel_size - 1;
     const int HD = c.downsample_kernel - c.downsample_stride;
     const int64_t L = st->F * n;
     const StreamTabs tabs = stream_tabs(st, slots != nullptr);
     const char* kname = "?";
-    auto carry = [&](const CarryTable& t) { return launch_stream_carry(t, B, tabs.slot, s, &kname); };
+    auto carry = [&](const CarryTable& t, size_t copy) {
+        if (RG) return launch_stream_carry_ragged(t, B, rg.coff(copy), rg.cnt(copy), carry_most, s, &kname);
+        return launch_stream_carry(t, B, tabs.slot, s, &kname);
+    };
     int rc;
     Recorder rec{e, s};
     rec.begin();
@@ -4225,28 +4684,59 @@ static int encode_stream_pass(mimi_encode_stream* st, const float* dev_audio, in
         outc.c[i] = {where[i] + rows[i] * st->carry_c[i], st->state + st->carry_off[i], bs, hc, (int)hc, CARRY_STATE_DST};
     }
     in.n = outc.n = (int)where.size();
-    LAUNCH_TRY(carry(in), "encode stream carry (in)");
+    if (RG)  // the tables hold every offset from its tensor's first element
+        for (size_t i = 1; i < where.size(); ++i) outc.c[i].src = where[i];
+    LAUNCH_TRY(carry(in, 0), "encode stream carry (in)");
     rec.mark("encs_carry", 0, 0, kname);
+    // a stage's tap: [B][rows][C] with equal counts, packed [1][f sum][C] in a ragged step (buf: the stage's tensor)
+    auto tap_stage = [&](const char* name, const float* buf, size_t j) {
+        const StreamStage& g = LY.st[j];
+        if (RG) return save_tap_packed(e, name, buf, LY, j, s);
+        return save_tap_strided(e, name, buf + (int64_t)g.H * g.C, B, g.f * n, g.C, (g.H + g.f * n) * g.C, s);
+    };
+    auto tap_flat = [&](const char* name, const float* src, int64_t f, int64_t ch) {  // a flat tensor of f rows per frame
+        return RG ? save_tap(e, name, src, 1, f * Sn, ch, s) : save_tap(e, name, src, B, f * n, ch, s);
+    };
 
     // ---- SEANet encoder ----
     int C = c.num_filters;
     int64_t len = L;
-    LAUNCH_TRY(launch_conv0_hist(dev_audio, L, B, e->conv0.w, e->conv0.b, w.x[0] + (int64_t)HR * C, C, c.kernel_size,
-                                 (HR + len) * C, w.a_hist, w.a_tail, s),
-               "conv0 (history)");
-    rec.mark("encs_conv0", 2.0 * B * len * C * c.kernel_size, (double)B * len * (1 + C) * 4,
-             "mimi::conv0_hist_kernel<64, 7>");
-    if ((rc = save_tap_strided(e, "conv0", w.x[0] + (int64_t)HR * C, B, len, C, (HR + len) * C, s))) return rc;
+    if (RG) {  // the caller's padded rows: nothing past an item's samples is read
+        LAUNCH_TRY(launch_conv0_hist_ragged(dev_audio, st->F * LY.stride, L, B, e->conv0.w, e->conv0.b,
+                                            w.x[0] + (int64_t)HR * C, C, c.kernel_size, w.a_hist, w.a_tail, rg.len(1),
+                                            rg.base(1), s),
+                   "conv0 (history)");
+        rec.mark("encs_conv0", 2.0 * st->F * Sn * C * c.kernel_size, (double)st->F * Sn * (1 + C) * 4,
+                 "mimi::conv0_hist_ragged_kernel<64, 7>");
+    } else {
+        LAUNCH_TRY(launch_conv0_hist(dev_audio, L, B, e->conv0.w, e->conv0.b, w.x[0] + (int64_t)HR * C, C,
+                                     c.kernel_size, (HR + len) * C, w.a_hist, w.a_tail, s),
+                   "conv0 (history)");
+        rec.mark("encs_conv0", 2.0 * B * len * C * c.kernel_size, (double)B * len * (1 + C) * 4,
+                 "mimi::conv0_hist_kernel<64, 7>");
+    }
+    if ((rc = tap_stage("conv0", w.x[0], 1))) return rc;
     // a conv over olen output rows per item whose input has hh carry rows in front of its ilen rows: the carry is
     // read where conv_args pads
-    auto conv = [&](const DevConv& cv, const float* inp, int hh, int64_t ilen, float* out, int64_t olen, int64_t out_bs) {
+    // A ragged step: stage sin's blocks -> olens / obase, the items' output rows and first output rows (device tables)
+    auto conv = [&](const DevConv& cv, const float* inp, int hh, int64_t ilen, float* out, int64_t olen, int64_t out_bs,
+                    size_t sin, const int* olens, const int* obase) {
         GemmArgs a = conv_args(cv, inp, hh + ilen, out, olen, B);
         a.a_off += (int64_t)hh * cv.cin;
         a.c_bstride = out_bs;
+        if (RG) {
+            a.a_rows = rg.alen(sin);
+            a.a_boff = rg.base(sin);
+            a.m_rows = olens;
+            a.c_boff = obase;
+        }
         return a;
     };
-    auto fl = [&](const GemmArgs& a) { return 2.0 * B * (double)a.M * a.N * a.K; };
-    auto by = [&](const GemmArgs& a) { return ((double)B * a.M * (a.a_rs + a.N) + (double)a.N * a.K) * 4; };
+    // (B a.M = the output rows of all items with equal counts; orows: a ragged step's)
+    auto fl = [&](const GemmArgs& a, double orows) { return 2.0 * (RG ? orows : (double)B * a.M) * a.N * a.K; };
+    auto by = [&](const GemmArgs& a, double orows) {
+        return ((RG ? orows : (double)B * a.M) * (a.a_rs + a.N) + (double)a.N * a.K) * 4;
+    };
     for (int si = 0; si < c.num_ratios; ++si) {
         const int r = enc_ratio(c, si);
         const bool last = si == c.num_ratios - 1;
@@ -4264,52 +4754,70 @@ static int encode_stream_pass(mimi_encode_stream* st, const float* dev_audio, in
         ra.hist = 2;
         ra.x_bstride = (HR + len) * C;
         ra.y_bstride = (r + len) * C;
+        const size_t sx = 1 + 2 * si;  // the stage of the block's input; its output is sx + 1, the down conv's sx + 2
+        if (RG) {
+            ra.ilen = rg.len(sx);
+            ra.ioff = rg.base(sx);
+            ra.yoff = rg.base(sx + 1);
+        }
         LAUNCH_TRY(launch_resblock(C, ra, s, &kname), "encoder resblock (history)");
         snprintf(nm, sizeof nm, "encs_res_s%d", si);
-        const double Hh = C / c.compress;
-        rec.mark(nm, 2.0 * B * len * (3.0 * C * Hh + Hh * C), (double)B * len * 2 * C * 4, kname);
+        const double Hh = C / c.compress, rrows = RG ? (double)(LY.st[sx].f * Sn) : (double)B * len;
+        rec.mark(nm, 2.0 * rrows * (3.0 * C * Hh + Hh * C), rrows * 2 * C * 4, kname);
         snprintf(nm, sizeof nm, "res%d_elu", si);
-        if ((rc = save_tap_strided(e, nm, ra.y, B, len, C, ra.y_bstride, s))) return rc;
+        if ((rc = tap_stage(nm, w.y[si], sx + 1))) return rc;
         // [r + len][C] -> [len / r][2 C], behind the next block's (the final conv's) carry rows
         const int64_t olen = len / r;
         const int hn = last ? HL : HR;
-        float* out = (last ? w.xl : w.x[si + 1]) + (int64_t)hn * 2 * C;
-        GemmArgs ad = conv(e->down[si], w.y[si], r, len, out, olen, (hn + olen) * 2 * C);
+        float* obuf = last ? w.xl : w.x[si + 1];
+        float* out = obuf + (int64_t)hn * 2 * C;
+        GemmArgs ad = conv(e->down[si], w.y[si], r, len, out, olen, (hn + olen) * 2 * C, sx + 1, RG ? rg.len(sx + 2) : nullptr,
+                           RG ? rg.base(sx + 2) : nullptr);
         LAUNCH_TRY(launch_gemm(last ? ROLE_DOWN_ELU : ROLE_DOWN, ad, s, &kname, PREC_F32), "down conv");
         snprintf(nm, sizeof nm, "encs_down_s%d", si);
-        rec.mark(nm, fl(ad), by(ad), kname);
+        rec.mark(nm, fl(ad, (double)(LY.st[sx + 2].f * Sn)), by(ad, (double)(LY.st[sx + 2].f * Sn)), kname);
         snprintf(nm, sizeof nm, last ? "down%d_elu" : "down%d", si);
-        if ((rc = save_tap_strided(e, nm, out, B, olen, 2 * C, (hn + olen) * 2 * C, s))) return rc;
+        if ((rc = tap_stage(nm, obuf, sx + 2))) return rc;
         C *= 2;
         len = olen;
     }
     if (len != R) return set_err(MIMI_ERR_STATE, "encode stream: %lld rows for %d frames", (long long)len, n);
-    GemmArgs af = conv(e->final_conv, w.xl, HL, R, w.t0, R, (int64_t)R * Hd);
+    // (a ragged step: the final conv's output is the packed flat rows, item i's at row 2 off[i])
+    GemmArgs af = conv(e->final_conv, w.xl, HL, R, w.t0, R, (int64_t)R * Hd, nc - 2, RG ? rg.len(nc - 2) : nullptr,
+                       RG ? rg.off2() : nullptr);
     LAUNCH_TRY(launch_gemm(ROLE_FINAL, af, s, &kname, PREC_F32), "final conv");
-    rec.mark("encs_final", fl(af), by(af), kname);
-    if ((rc = save_tap(e, "encoder", w.t0, B, R, Hd, s))) return rc;
+    rec.mark("encs_final", fl(af, (double)SR), by(af, (double)SR), kname);
+    if ((rc = tap_flat("encoder", w.t0, 2, Hd))) return rc;
 
     // ---- encoder transformer on the stream's rings ----
-    if ((rc = transformer_f32(e, e->xf, w.t0, w.t1, w.qkv, w.att, w.ff, (int64_t)B * R, B, R, "encs_", rec, s,
-                              stream_qkv_args(st, w.t1, w.qkv, B, R, slots != nullptr),
-                              stream_attention(st, w.qkv, w.att, B, R, pos0, tabs.pos, tabs.slot, "encs_", rec, s))))
+    if ((rc = transformer_f32(e, e->xf, w.t0, w.t1, w.qkv, w.att, w.ff, SR, RG ? 1 : B, RG ? SR : R, "encs_", rec, s,
+                              stream_qkv_args(st, w.t1, w.qkv, B, R, slots != nullptr, SR),
+                              stream_attention(st, w.qkv, w.att, B, R, pos0, tabs.pos, tabs.slot, "encs_", rec, s,
+                                               RG ? rg.len(nc - 1) : nullptr, RG ? rg.off2() : nullptr,
+                                               RG ? LY.frames.data() : nullptr))))
         return rc;
     // ---- downsample behind its carry (a slot at position 0: two copies of its first row) + projections + RVQ ----
-    LAUNCH_TRY(launch_stream_ds_rows(w.t0, w.dsin, B, R, Hd, 2 * pos0[0], tabs.pos, s, &kname), "downsample rows");
-    rec.mark("encs_ds_rows", 0, 2.0 * B * R * Hd * 4, kname);
-    GemmArgs ad = conv(e->ds, w.dsin, HD, R, w.dsout, n, (int64_t)n * Hd);
+    if (RG)  // (the replicate fill is per item: from its own position and its own first row)
+        LAUNCH_TRY(launch_stream_ds_rows_ragged(w.t0, w.dsin, B, R, Hd, tabs.pos, rg.len(nc - 1), rg.off2(),
+                                                rg.base(nc - 1), s, &kname),
+                   "downsample rows");
+    else
+        LAUNCH_TRY(launch_stream_ds_rows(w.t0, w.dsin, B, R, Hd, 2 * pos0[0], tabs.pos, s, &kname), "downsample rows");
+    rec.mark("encs_ds_rows", 0, 2.0 * SR * Hd * 4, kname);
+    GemmArgs ad = conv(e->ds, w.dsin, HD, R, w.dsout, n, (int64_t)n * Hd, nc - 1, RG ? rg.frames() : nullptr,
+                       RG ? rg.off1() : nullptr);
     LAUNCH_TRY(launch_gemm(ROLE_DOWNSAMPLE, ad, s, &kname, PREC_F32), "downsample");
-    rec.mark("encs_downsample", fl(ad), by(ad), kname);
-    if ((rc = save_tap(e, "downsample", w.dsout, B, n, Hd, s))) return rc;
-    GemmArgs ap = linear_args(w.dsout, (int64_t)B * n, Hd, e->inproj, 2 * Dq, w.proj);
+    rec.mark("encs_downsample", fl(ad, (double)Sn), by(ad, (double)Sn), kname);
+    if ((rc = tap_flat("downsample", w.dsout, 1, Hd))) return rc;
+    GemmArgs ap = linear_args(w.dsout, Sn, Hd, e->inproj, 2 * Dq, w.proj);
     LAUNCH_TRY(launch_gemm(ROLE_INPROJ, ap, s, &kname, PREC_F32), "input_proj");
-    rec.mark("encs_input_proj", 2.0 * B * n * Hd * 2 * Dq, ((double)B * n * (Hd + 2 * Dq) + 2.0 * Dq * Hd) * 4, kname);
-    if ((rc = save_tap(e, "proj", w.proj, B, n, 2 * Dq, s))) return rc;
+    rec.mark("encs_input_proj", 2.0 * Sn * Hd * 2 * Dq, ((double)Sn * (Hd + 2 * Dq) + 2.0 * Dq * Hd) * 4, kname);
+    if ((rc = tap_flat("proj", w.proj, 1, 2 * Dq))) return rc;
     {
         RvqArgs r{};
         r.work = w.rvq;
         r.proj = w.proj;
-        r.frames = (int64_t)B * n;
+        r.frames = Sn;
         r.D = c.codebook_dim;
         r.ncodes = c.codebook_size;
         r.levels = K;
@@ -4322,37 +4830,57 @@ static int encode_stream_pass(mimi_encode_stream* st, const float* dev_audio, in
         r.cb_emax = e->cb_emax;
         r.codes = dev_codes;
         r.frames_per_item = n;
+        if (RG) {  // the packed frames' codes go to the caller's padded [m][K][stride]; entries past an item's are left alone
+            r.code_map = rg.code_map();
+            r.code_stride = (int)LY.stride;
+        }
         r.form = e->rvq_form;
         r.chain = 0;  // the per-level kernels: nobody reads a give-up flag back here
         r.xcd_group_ok = e->rvq_xcd;
         LAUNCH_TRY(launch_rvq(r, s, &kname, nullptr, nullptr), "rvq");
-        rec.mark("encs_rvq", 2.0 * B * n * r.D * r.ncodes * K, (double)B * n * (2 * r.D + K) * 4, kname);
+        rec.mark("encs_rvq", 2.0 * Sn * r.D * r.ncodes * K, (double)Sn * (2 * r.D + K) * 4, kname);
     }
-    LAUNCH_TRY(carry(outc), "encode stream carry (out)");
+    LAUNCH_TRY(carry(outc, nc + 1), "encode stream carry (out)");
     rec.mark("encs_carry", 0, 0, kname);
     return MIMI_OK;
 }
 
 // One step over the m listed slots (slots == nullptr: all st->B in order, at one position: the lock-step pass).
 // Called with the engine mutex held and every argument checked but the slots' state.
+// frames (mimi_encode_stream_step_ragged; else null): item i advances by frames[i] <= n frames, the caller's rows hold n.
+// Counts that are all n make the slot step itself: frames is dropped here and nothing below knows the difference.
 static int encode_stream_step_locked(mimi_encode_stream* st, const int32_t* slots, int m, const float* dev_audio, int n,
-                                     int32_t* dev_codes, hipStream_t s) {
+                                     int32_t* dev_codes, hipStream_t s, const int32_t* frames = nullptr) {
     mimi_engine* e = st->e;
     int rc;
-    if ((rc = stream_step_check(st, "encode", slots, m, n))) return rc;
+    if (frames && std::all_of(frames, frames + m, [&](int32_t f) { return f == n; })) frames = nullptr;
+    if ((rc = stream_step_check(st, "encode", slots, m, n, frames))) return rc;
     if (st->F * n > 0x7fffffffLL)
         return set_err(MIMI_ERR_UNSUPPORTED, "encode stream: %d frames exceed the 32-bit row range", n);
+    StreamLayout LY;
+    plan_stream(stream_stages_encode(e->cfg), frames, m, n, &LY);
+    if (LY.rows(1) > 0x7fffffffLL || LY.rows(2) > 0x7fffffffLL)
+        return set_err(MIMI_ERR_UNSUPPORTED, "encode stream: %lld rows exceed the 32-bit row range", (long long)LY.rows(2));
     HIP_TRY(hipSetDevice(e->device));
-    if ((rc = ensure_dws(e, enc_stream_ws_layout(e, m, n).bytes))) return rc;  // (state untouched so far)
-    const EncStreamWs w = enc_stream_ws_layout(e, m, n);
+    if ((rc = ensure_dws(e, enc_stream_ws_layout(e->cfg, nullptr, m, LY.sum).bytes))) return rc;  // (state untouched so far)
+    const EncStreamWs w = enc_stream_ws_layout(e->cfg, e->dws, m, LY.sum);
+    // a ragged step's tables: built and checked before anything is enqueued or a slot is marked
+    StreamRag rg{};
+    int carry_most = 0;
+    if (LY.ragged && (rc = stream_rag_fill(st, LY, slots, st->rag_host, &carry_most, false, st->K))) return rc;
     std::vector<int64_t> pos0;  // frames
-    if ((rc = stream_step_upload(st, slots, m, n, &pos0, s))) return rc;
-    rc = encode_stream_pass(st, dev_audio, m, n, slots, pos0.data(), w, dev_codes, s);
+    if ((rc = stream_step_upload(st, slots, m, n, &pos0, s, frames))) return rc;
+    if (LY.ragged) {
+        const size_t bytes = stream_rag_map_at(LY.st.size(), 0, m) + (size_t)LY.sum * sizeof(int64_t);
+        HIP_TRY(hipMemcpyAsync(st->rag_dev, st->rag_host, bytes, hipMemcpyHostToDevice, s));
+        rg = StreamRag{st->rag_dev, LY.st.size(), 0, (size_t)m};
+    }
+    rc = encode_stream_pass(st, dev_audio, LY, rg, carry_most, slots, pos0.data(), w, dev_codes, s);
     // the workspace and the pinned images are free for the next call under the mutex, whatever its stream
     const hipError_t se = hipStreamSynchronize(s);
     if (rc) return rc;
     if (se != hipSuccess) return set_err(MIMI_ERR_HIP, "encode stream step: %s", hipGetErrorString(se));
-    stream_step_done(st, slots, m, n);
+    stream_step_done(st, slots, m, n, frames);
     return MIMI_OK;
 }
 
@@ -4378,6 +4906,38 @@ extern "C" int mimi_encode_stream_step_slots(mimi_encode_stream* st, const int32
     int rc;
     if ((rc = stream_check_slots(st, "encode", slots, m, n))) return rc;
     return encode_stream_step_locked(st, slots, m, dev_audio, n, dev_codes, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mimi_encode_stream_step_ragged(mimi_encode_stream* st, const int32_t* slots, const int32_t* frames,
+                                              int32_t m, int32_t max_frames, const float* dev_audio, int32_t* dev_codes,
+                                              void* stream) {
+    if (!st) return set_err(MIMI_ERR_INVALID_ARGUMENT, "null stream");
+    mimi_engine* e = st->e;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!slots || !frames || !dev_audio || !dev_codes)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "encode stream step: null argument");
+    int rc;
+    if ((rc = stream_check_slots(st, "encode", slots, m, max_frames, frames))) return rc;
+    return encode_stream_step_locked(st, slots, m, dev_audio, max_frames, dev_codes,
+                                     reinterpret_cast<hipStream_t>(stream), frames);
+}
+
+// the encode half of mimi_stream_step_layout (arguments checked there)
+static int encode_step_layout(const mimi_config& c, const int32_t* frames, int32_t m, int32_t max_frames,
+                              std::vector<StreamStage>* st, StreamLayout* L, std::vector<int64_t>* byte_offset,
+                              int64_t* bytes) {
+    if (c.residual_kernel_size < 1 || c.residual_kernel_size > 64 || c.downsample_kernel < c.downsample_stride ||
+        c.downsample_stride < 1 || c.downsample_kernel > 64)
+        return set_err(MIMI_ERR_INVALID_ARGUMENT, "stream step layout: a configuration field outside the range a stream takes");
+    *st = stream_stages_encode(c);
+    plan_stream(*st, frames, m, max_frames, L);
+    const EncStreamWs w = enc_stream_ws_layout(c, nullptr, m, L->sum);
+    const size_t nr = c.num_ratios;
+    byte_offset->assign(1, (int64_t)w.at[0]);  // conv 0's carry in; then x[s], y[s] ..., the final conv's, the downsample's
+    for (size_t j = 0; j < 2 * nr + 1; ++j) byte_offset->push_back((int64_t)w.at[2 + j]);
+    byte_offset->push_back((int64_t)w.at[2 + 2 * nr + 1 + 5]);
+    *bytes = (int64_t)w.bytes;
+    return MIMI_OK;
 }
 
 extern "C" void mimi_destroy(mimi_engine* e) {

@@ -490,6 +490,12 @@ static hipError_t dispatch_planes(int role, const GemmArgs& a, hipStream_t s) {
 
 static hipError_t dispatch(int role, const GemmArgs& a, hipStream_t s) {
     if (a.Ap) return dispatch_planes(role, a, s);
+    if (a.c_eoff) {
+        // a ragged stream step's up conv: packed items, each one's output at its own element offset (gemm_kernel.h RE)
+        if (!a.m_rows || !a.a_rows || !a.a_boff || a.c_boff || g_prec != PREC_F32 || a.R || role != ROLE_UPCONV)
+            return hipErrorInvalidValue;
+        return run_auto<false, PAD_ZERO, EPI_BIAS, 214>(a, s);
+    }
     if (a.m_rows || a.a_rows || a.a_boff || a.c_boff) {
         // packed ragged items on the fp32 kernel (the ragged decode pass): the role's instantiation with TAG + 100
         // (gemm_kernel.h RG).  a.M = the longest item's rows picks the tile; <64, 128> and <128, 128> run the same
@@ -500,6 +506,9 @@ static hipError_t dispatch(int role, const GemmArgs& a, hipStream_t s) {
             case ROLE_DOWN_ELU: return run_auto<false, PAD_ZERO, EPI_BIAS_ELU, 103>(a, s);
             case ROLE_QKV: return run<64, 128, 1, 2, 32, 1, false, false, PAD_ZERO, EPI_ROPE, 105>(a, s);
             case ROLE_UPCONV: return run_auto<false, PAD_ZERO, EPI_BIAS, 114>(a, s);
+            case ROLE_INPROJ: return run_auto<false, PAD_ZERO, EPI_NONE, 110>(a, s);  // (a ragged stream step)
+            case ROLE_FINAL: return run_auto<false, PAD_ZERO, EPI_BIAS_OUT, 104>(a, s);  // (a ragged encode-stream step)
+            case ROLE_DOWNSAMPLE: return run_auto<false, PAD_REPLICATE, EPI_NONE, 109>(a, s);
             default: return hipErrorInvalidValue;
         }
     }

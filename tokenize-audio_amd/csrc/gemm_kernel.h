@@ -72,7 +72,9 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs p) {
     // RoPE position are relative to that base, as alone.  A tile past the item's rows exits before any load.
     // (Grid order: an item's M tiles consecutive, as the uniform kernel.  The item fastest instead -- the same (M tile,
     // N tile) of consecutive items sharing a weight slice -- measured slower: CHANGELOG.)
+    // RE (TAG >= 200: the up convs of a ragged stream step): RG with item b's C at element c_eoff[b]
     constexpr bool RG = TAG >= 100;
+    constexpr bool RE = TAG >= 200;
     const int b = blockIdx.z;
     // NFAST: consecutive workgroups walk the N tiles of one M tile, so an activation tile is re-read by the
     // other N tiles while it is still in L2 / the Infinity Cache instead of one full pass over M later.
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs p) {
     }
 
     // ---- epilogue: lane holds col (lane&31), rows (r&3) + 8*(r>>2) + 4*(lane>>5) of each 32x32 tile
-    const long long cbo = RG ? (long long)p.c_boff[b] * p.ldc : (long long)b * p.c_bstride;
+    const long long cbo = RE ? p.c_eoff[b] : RG ? (long long)p.c_boff[b] * p.ldc : (long long)b * p.c_bstride;
     float* __restrict__ Cb = p.C + cbo;
     const float* __restrict__ Rb = p.R ? p.R + cbo : nullptr;
     const int rbase = m0 + wm * TM * 32 + 4 * (lane >> 5);

@@ -229,6 +229,9 @@ struct GemmArgs {
     // c_boff[b] of one [sum of rows][...] tensor instead of at b x a_bstride / c_bstride; FL_RAGGED kernels only)
     const int* a_boff;  // A: item b starts at element a_boff[b] * a_cin
     const int* c_boff;  // C / Cp / R: item b starts at row c_boff[b] (element c_boff[b] * ldc)
+    // packed items whose first C element is no multiple of ldc (TAG >= 200: a ragged stream step's up convs, whose
+    // [len][r Cout] output lands behind 2 carry rows of Cout): item b's C starts at element c_eoff[b]; c_boff unread
+    const long long* c_eoff;
     // EPI_ROPE over packed rows: the RoPE position of output row m (null: m itself)
     const int* rope_pos;
     // LayerNorm prologue (small-batch q/k/v and fc1 in f16x3, gemm_planes.h FL_LNA): A = LayerNorm(ln_x) (fp32, the
@@ -338,6 +341,10 @@ struct ResArgs {
     // with its 2 rows of history (real data, not zeros) right in front of them, and its output rows at y + b y_bstride
     int hist;
     long long x_bstride, y_bstride;
+    // a ragged step of a decode stream (fp32 resblock_hist_ragged_kernel): hist = 2 with ilen / ioff as the ragged form
+    // (the item's rows at row ioff[b] of the packed x, its 2 history rows in front of them) and yoff[b] the item's first
+    // row of y, which packs the next stage's [carry | chunk] blocks; x_bstride / y_bstride unused
+    const int* yoff;
 };
 hipError_t launch_resblock(int C, const ResArgs& a, hipStream_t s, const char** kname);
 // stage 0 + down conv 0 in one kernel (PREC_F16X3)
@@ -453,6 +460,9 @@ struct RvqArgs {
                             // rvq_chain; same codes)
     int xcd_group_ok;       // large grids: the slices of a frame tile on one XCD (engine option rvq_xcd; speed only)
     int xcd_group;          // (set by launch_rvq)
+    const long long* code_map;  // a ragged encode-stream step (else null): the frames are packed, frame f's level-0 code
+    int code_stride;            // goes to codes[code_map[f]], level l's code_stride further (the padded [m][K][stride]
+                                // layout; entries past an item's frames are left alone).  Device table, frames entries.
     int chain_fault;        // fault injection for the chain's give-up path (engine option rvq_chain_fault, tests only):
                             // 0 off, 1 a zero spin budget, 2 every sweep gives up at once
 };
@@ -492,6 +502,15 @@ hipError_t launch_upsample_dw_hist(const float* x, const float* w, float* y, int
                                    long long x_bstride, hipStream_t s);
 hipError_t launch_final_conv_hist(const float* x, const float* w, const float* bias, float* y, int batch, long long L,
                                   int C, int ksize, long long x_bstride, hipStream_t s);
+// History and ragged together (a ragged step of a decode stream: every item its own number of frames).  x holds the
+// packed [carry | chunk] blocks; the tables give each item's rows and the row of x its chunk starts at (the carry rows
+// right in front of it); the longest item sizes the grid.  upsample: y packed (item b's rows at 2 toff[b]); final
+// conv: y the caller's padded [B][Ls], samples past llen[b] untouched.  Per row the arithmetic of the forms above.
+hipError_t launch_upsample_dw_hist_ragged(const float* x, const float* w, float* y, int batch, long long max_T, int C,
+                                          const int* tlen, const int* toff, const int* xoff, hipStream_t s);
+hipError_t launch_final_conv_hist_ragged(const float* x, const float* w, const float* bias, float* y, int batch,
+                                         long long Ls, int C, int ksize, const int* llen, const int* loff,
+                                         long long max_llen, hipStream_t s);
 
 // Streamed decode (attn_stream.hip).  Each launcher serves both forms of its kernel body: with null tables the
 // lock-step kernel (every item's first row is absolute row pos0 >= 0, item b's rings and carries are b's), with
@@ -512,6 +531,17 @@ hipError_t launch_attention_stream(const float* qkv, const float* kring, const f
 hipError_t launch_attention_stream_append(const float* qkv, float* kring, float* vring, int batch, int R, int H, int D,
                                           int cap, long long pos0, const long long* pos_tab, const int* slot_tab,
                                           hipStream_t s, const char** kname = nullptr);
+// The ragged step (every listed slot its own number of frames; tables of `batch` entries, checked by the caller): item
+// b has rlen[b] rows at row roff[b] of the packed qkv / out, R = the longest item's rows.  A row's bits are those of the
+// slot form.
+hipError_t launch_attention_stream_ragged(const float* qkv, const float* kring, const float* vring, float* out,
+                                          int batch, int R, int H, int D, int window, int cap, const long long* pos_tab,
+                                          const int* slot_tab, const int* rlen, const int* roff, float scale,
+                                          hipStream_t s, const char** kname = nullptr);
+hipError_t launch_attention_stream_append_ragged(const float* qkv, float* kring, float* vring, int batch, int R, int H,
+                                                 int D, int cap, const long long* pos_tab, const int* slot_tab,
+                                                 const int* rlen, const int* roff, hipStream_t s,
+                                                 const char** kname = nullptr);
 // stream_carry_kernel: n strided copies in one launch; copy d moves `count` floats (a multiple of 4) per item from
 // src + b * src_bstride to dst + b * dst_bstride.  Source and destination never overlap.
 // slot_tab set (stream_carry_slots_kernel): the same with the stream's side of a copy (`state`: CARRY_STATE_SRC for
@@ -531,6 +561,11 @@ struct CarryTable {
 };
 hipError_t launch_stream_carry(const CarryTable& t, int batch, const int* slot_tab, hipStream_t s,
                                const char** kname = nullptr);
+// stream_carry_ragged_kernel: copy d moves cnt[d][b] floats from src + off[d][0][b] to dst + off[d][1][b] (device
+// tables [n][2][batch] int64 / [n][batch] int32 of element offsets and counts, multiples of 4; src_bstride, dst_bstride,
+// count and state of the CarryCopy unread); most = the largest count
+hipError_t launch_stream_carry_ragged(const CarryTable& t, int batch, const long long* off, const int* cnt, int most,
+                                      hipStream_t s, const char** kname = nullptr);
 
 // Streamed encode (engine.cpp "encode stream").
 // conv0_hist_kernel: launch_conv0 on a chunk of L >= 8 samples per item whose 6 samples of the past are the last ones
@@ -538,6 +573,16 @@ hipError_t launch_stream_carry(const CarryTable& t, int batch, const int* slot_t
 // samples to tail [batch][8].  Per output the arithmetic of conv0_kernel.
 hipError_t launch_conv0_hist(const float* x, long long L, int batch, const float* w, const float* b, float* y, int cout,
                              int ksize, long long y_bstride, const float* hist, float* tail, hipStream_t s);
+// the ragged step: x [batch][Ls] padded rows of which item b's first llen[b] samples are read, y rows at row yoff[b] of
+// the packed stage-0 blocks; max_L = the longest item's samples
+hipError_t launch_conv0_hist_ragged(const float* x, long long Ls, long long max_L, int batch, const float* w,
+                                    const float* b, float* y, int cout, int ksize, const float* hist, float* tail,
+                                    const int* llen, const int* yoff, hipStream_t s);
+// stream_ds_rows_ragged_kernel: item b's rlen[b] rows at row roff[b] of the packed src go behind the 2 carry rows of its
+// block at row doff[b] of dst; where pos_tab[b] == 0 the carry rows are copies of the item's own first row
+hipError_t launch_stream_ds_rows_ragged(const float* src, float* dst, int batch, int max_R, int C,
+                                        const long long* pos_tab, const int* rlen, const int* roff, const int* doff,
+                                        hipStream_t s, const char** kname = nullptr);
 // stream_ds_rows_kernel: src [batch][R][C] -> dst [batch][2 + R][C] rows 2 .., and where the item's first row is
 // absolute row 0 (pos0, or pos_tab[b] where pos_tab is set: stream_ds_rows_slots_kernel) dst rows 0, 1 = src row 0: the
 // downsample's replicate padding

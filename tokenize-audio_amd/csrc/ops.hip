@@ -18,10 +18,16 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // last ones of hist[b][8] -- the stream's carry, real data where the one-shot form pads with zeros -- its output rows
 // start at y + b * y_bstride (behind the stage-0 block's own carry rows), and the chunk's last 8 samples go to
 // tail[b][8], the next step's carry.  Per output the same fmaf chain in tap order, then + bias.
-template <int COUT, int KS, bool HS>
+// RG (with HS: a ragged step of an encode stream): item b's chunk is the first llen[b] samples of its padded row of Ls
+// samples (nothing past them is read: NaN there is harmless), its output rows start at row yoff[b] of y (the packed
+// stage-0 blocks); the grid covers the longest item and a workgroup past its item's samples exits before any load.
+template <int COUT, int KS, bool HS, bool RG = false>
 __device__ __forceinline__ void conv0_body(const float* __restrict__ x, long long L, const float* __restrict__ w,
                                            const float* __restrict__ bias, float* __restrict__ y, long long y_bstride,
-                                           const float* __restrict__ hist, float* __restrict__ tail) {
+                                           const float* __restrict__ hist, float* __restrict__ tail,
+                                           const int* __restrict__ llen = nullptr,
+                                           const int* __restrict__ yoff = nullptr, long long Ls = 0) {
+    static_assert(HS || !RG, "a ragged step is a stream step");
     constexpr int TT = 128;
     constexpr int CG = COUT / 4;        // channel groups of 4
     constexpr int TG = 256 / CG;        // time lanes
@@ -31,7 +37,11 @@ __device__ __forceinline__ void conv0_body(const float* __restrict__ x, long lon
     __shared__ float bs[COUT];
     const int b = blockIdx.y;
     const long long t0 = (long long)blockIdx.x * TT;
-    const float* xb = x + (long long)b * L;
+    if constexpr (RG) {
+        L = llen[b];
+        if (t0 >= L) return;
+    }
+    const float* xb = x + (long long)b * (RG ? Ls : L);
     for (int i = threadIdx.x; i < TT + KS - 1; i += 256) {
         const long long t = t0 - (KS - 1) + i;
         float v = (t >= 0 && t < L) ? xb[t] : 0.0f;
@@ -52,7 +62,7 @@ __device__ __forceinline__ void conv0_body(const float* __restrict__ x, long lon
     __syncthreads();
     const int cg = threadIdx.x % CG;
     const int tl = threadIdx.x / CG;
-    float* yb = y + (HS ? (long long)b * y_bstride : (long long)b * L * COUT);
+    float* yb = y + (RG ? (long long)yoff[b] * COUT : HS ? (long long)b * y_bstride : (long long)b * L * COUT);
     for (int tt = tl; tt < TT; tt += TG) {
         const long long t = t0 + tt;
         if (t >= L) break;
@@ -82,6 +92,28 @@ __global__ __launch_bounds__(256) void conv0_hist_kernel(const float* __restrict
                                                          float* __restrict__ y, long long y_bstride,
                                                          const float* __restrict__ hist, float* __restrict__ tail) {
     conv0_body<COUT, KS, true>(x, L, w, bias, y, y_bstride, hist, tail);
+}
+
+template <int COUT, int KS>
+__global__ __launch_bounds__(256) void conv0_hist_ragged_kernel(const float* __restrict__ x, long long Ls,
+                                                                const float* __restrict__ w,
+                                                                const float* __restrict__ bias, float* __restrict__ y,
+                                                                const float* __restrict__ hist, float* __restrict__ tail,
+                                                                const int* __restrict__ llen,
+                                                                const int* __restrict__ yoff) {
+    conv0_body<COUT, KS, true, true>(x, 0, w, bias, y, 0, hist, tail, llen, yoff, Ls);
+}
+
+// x [batch][Ls] padded; max_L = the longest item's samples (the grid); every llen[b] >= 8 and <= Ls (the caller's check)
+hipError_t launch_conv0_hist_ragged(const float* x, long long Ls, long long max_L, int batch, const float* w,
+                                    const float* b, float* y, int cout, int ksize, const float* hist, float* tail,
+                                    const int* llen, const int* yoff, hipStream_t s) {
+    if (cout != 64 || ksize != 7 || max_L < 8 || max_L > Ls || batch <= 0 || batch > 65535 ||
+        (max_L + 127) / 128 > 0x7fffffffLL || !x || !w || !b || !y || !hist || !tail || !llen || !yoff)
+        return hipErrorInvalidValue;
+    dim3 grid((unsigned)((max_L + 127) / 128), batch);
+    hipLaunchKernelGGL((conv0_hist_ragged_kernel<64, 7>), grid, dim3(256), 0, s, x, Ls, w, b, y, hist, tail, llen, yoff);
+    return hipGetLastError();
 }
 
 hipError_t launch_conv0(const float* x, long long L, int batch, const float* w, const float* b, float* y,
@@ -1500,7 +1532,9 @@ __device__ __forceinline__ bool rvq_valid(const RvqArgs& p, long long f) {
 
 __device__ __forceinline__ void rvq_store_code(const RvqArgs& p, int level, long long f, int ix) {
     int32_t* codes = io_pointer(p.codes_ref, p.codes);
-    if (p.frames_per_item > 0) {
+    if (p.code_map) {  // a ragged stream step: packed frame f -> its place in the caller's padded [m][K][code_stride]
+        codes[p.code_map[f] + (long long)level * p.code_stride] = ix;
+    } else if (p.frames_per_item > 0) {
         const long long bb = f / p.frames_per_item, t = f % p.frames_per_item;
         codes[(bb * p.levels + level) * p.frames_per_item + t] = ix;
     } else {

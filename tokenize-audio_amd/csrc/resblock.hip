@@ -90,7 +90,7 @@ __device__ __forceinline__ void store_y_block(const ResArgs& p, float* stg, cons
 template <int C, int BM, bool WINDOW, bool FIRST, int W1M, int W1N, int W2M, int W2N, int NP, bool RG, bool HS = false>
 __device__ __forceinline__ void resblock_body(const ResArgs& p) {
     static_assert(!(RG && FIRST), "ragged blocks read x");
-    static_assert(!(HS && (RG || FIRST)), "history blocks are uniform and read x");
+    static_assert(!(HS && FIRST), "history blocks read x");
     constexpr long long PAD0 = HS ? -2 : 0;  // the first row that exists
     constexpr int H = C / 2;
     constexpr int K1 = 3 * C;
@@ -124,8 +124,11 @@ __device__ __forceinline__ void resblock_body(const ResArgs& p) {
     const int b = blockIdx.y;
     const long long T = RG ? (long long)p.ilen[b] : p.T;
     if (RG && m0 >= T) return;
-    const long long xoff = HS ? (long long)b * p.x_bstride
-                              : RG ? (long long)p.ioff[b] * C : (long long)b * T * C;  // the item's first element of x / y
+    // RG and HS together (a ragged step of a decode stream): the item's rows at row p.ioff[b] of the packed x with its
+    // 2 history rows in front of them, its output rows at row p.yoff[b] of y
+    const long long xoff = RG   ? (long long)p.ioff[b] * C
+                           : HS ? (long long)b * p.x_bstride
+                                : (long long)b * T * C;  // the item's first element of x / y
     const float* __restrict__ xb = p.x + xoff;
 
     // ---------------- GEMM1: h = ELU(x) (*) W3 ----------------
@@ -293,7 +296,7 @@ __device__ __forceinline__ void resblock_body(const ResArgs& p) {
     }
 
     // ---------------- GEMM2: y = ELU(x + b1 + h . W1^T), NP columns per pass ----------------
-    const long long ybase = HS ? (long long)b * p.y_bstride : xoff;
+    const long long ybase = HS ? (RG ? (long long)p.yoff[b] * C : (long long)b * p.y_bstride) : xoff;
     float ymx = 0.0f;  // max|y| (fp16 planes: the engine's range check)
     for (int n0 = 0; n0 < C; n0 += NP) {
         auto load2 = [&](int k0) {
@@ -380,7 +383,10 @@ template <int C, int BM, bool WINDOW, int W1M, int W1N, int W2M, int W2N, int NP
 __global__ __launch_bounds__(256) void resblock_hist_kernel(ResArgs p) {
     resblock_body<C, BM, WINDOW, false, W1M, W1N, W2M, W2N, NP, false, true>(p);
 }
-
+template <int C, int BM, bool WINDOW, int W1M, int W1N, int W2M, int W2N, int NP>
+__global__ __launch_bounds__(256) void resblock_hist_ragged_kernel(ResArgs p) {
+    resblock_body<C, BM, WINDOW, false, W1M, W1N, W2M, W2N, NP, true, true>(p);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Stage 0, wave-autonomous: conv0 (1 -> 64, k7) + residual block (64 -> 32 -> 64) + ELU, one WAVE per 32 rows.
@@ -1067,8 +1073,33 @@ static hipError_t run_res_hist(const ResArgs& a, hipStream_t s, const char** kna
     return hipGetLastError();
 }
 
+// a ragged step of a decode stream (a.hist = 2 with a.ilen / a.ioff / a.yoff; a.T = the longest item's rows sizes the
+// grid): the fp32 block of the same tile
+template <int C, int BM, bool WINDOW, int W1M, int W1N, int W2M, int W2N, int NP>
+static hipError_t run_res_hist_ragged(const ResArgs& a, hipStream_t s, const char** kname) {
+    static thread_local char name[160];
+    if (!name[0])
+        snprintf(name, sizeof(name), "mimi::resblock_hist_ragged_kernel<%d, %d, %s, %d, %d, %d, %d, %d>", C, BM,
+                 WINDOW ? "true" : "false", W1M, W1N, W2M, W2N, NP);
+    if (kname) *kname = name;
+    dim3 grid((unsigned)((a.T + BM - 1) / BM), a.batch);
+    hipLaunchKernelGGL((resblock_hist_ragged_kernel<C, BM, WINDOW, W1M, W1N, W2M, W2N, NP>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_resblock(int C, const ResArgs& a, hipStream_t s, const char** kname) {
     if (a.T <= 0 || a.batch <= 0) return hipErrorInvalidValue;
+    if (a.hist && a.yoff) {
+        if (a.hist != 2 || !a.ioff || !a.ilen || a.audio || a.wh16 || a.yns != 0 || !a.x || !a.y || a.batch > 65535)
+            return hipErrorInvalidValue;
+        switch (C) {
+            case 64: return run_res_hist_ragged<64, 128, true, 4, 1, 4, 1, 64>(a, s, kname);
+            case 128: return run_res_hist_ragged<128, 64, true, 2, 2, 2, 2, 128>(a, s, kname);
+            case 256: return run_res_hist_ragged<256, 64, false, 2, 2, 2, 2, 128>(a, s, kname);
+            case 512: return run_res_hist_ragged<512, 32, false, 1, 4, 1, 4, 256>(a, s, kname);
+            default: return hipErrorInvalidValue;
+        }
+    }
     if (a.hist) {
         if (a.hist != 2 || a.ioff || a.ilen || a.audio || a.wh16 || a.yns != 0 || !a.x || !a.y || a.batch > 65535 ||
             a.x_bstride < (a.T + 2) * C || a.y_bstride < a.T * C || a.x_bstride % 4 || a.y_bstride % 4)

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "mimi_decode_stream_create", "mimi_decode_stream_step", "mimi_decode_stream_reset", "mimi_decode_stream_position",
     "mimi_decode_stream_state_bytes", "mimi_decode_stream_destroy",
     "mimi_decode_stream_step_slots", "mimi_decode_stream_reset_slot", "mimi_decode_stream_slot_position",
+    "mimi_decode_stream_step_ragged", "mimi_stream_step_layout", "mimi_encode_stream_step_ragged",
     "mimi_encode_stream_create", "mimi_encode_stream_step", "mimi_encode_stream_step_slots", "mimi_encode_stream_reset",
     "mimi_encode_stream_reset_slot", "mimi_encode_stream_position", "mimi_encode_stream_slot_position",
     "mimi_encode_stream_state_bytes", "mimi_encode_stream_destroy", "mimi_frame_samples_cfg",
@@ -45,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "mimi_bpe_model_set_spellings", "mimi_bpe_decode_plan", "mimi_bpe_decode_write",
 )
 CREATE_DECODE = 1  # MIMI_CREATE_DECODE
+STREAM_DECODE, STREAM_ENCODE, STREAM_MAX_STAGES = 0, 1, 16  # MIMI_STREAM_*
 RESAMPLE_MAX_TAPS = 65536  # MIMI_RESAMPLE_MAX_TAPS
 BPE_ENCODE_LDS_MAX_SYMBOLS = 8192  # MIMI_BPE_ENCODE_LDS_MAX_SYMBOLS
 BPE_WORDS_MAX_RUN = 64  # MIMI_BPE_WORDS_MAX_RUN
@@ -185,11 +187,19 @@ def _declare(lib):
         "mimi_decode_stream_state_bytes": (c.c_int64, [vp]),
         "mimi_decode_stream_destroy": (None, [vp]),
         "mimi_decode_stream_step_slots": (c.c_int, [vp, c.POINTER(c.c_int32), c.c_int32, vp, c.c_int32, vp, vp]),
+        "mimi_decode_stream_step_ragged": (c.c_int, [vp, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.c_int32,
+                                                    c.c_int32, vp, vp, vp]),
+        "mimi_stream_step_layout": (c.c_int, [c.POINTER(MimiConfigC), c.c_int32, c.POINTER(c.c_int32), c.c_int32,
+                                             c.c_int32, c.c_int32, c.POINTER(c.c_int32), c.POINTER(c.c_int32),
+                                             c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(c.c_int64),
+                                             c.POINTER(c.c_int64), c.POINTER(c.c_int64), c.POINTER(c.c_int64)]),
         "mimi_decode_stream_reset_slot": (c.c_int, [vp, c.c_int32]),
         "mimi_decode_stream_slot_position": (c.c_int64, [vp, c.c_int32]),
         "mimi_encode_stream_create": (c.c_int, [vp, c.c_int32, c.c_int32, c.c_int32, c.POINTER(vp)]),
         "mimi_encode_stream_step": (c.c_int, [vp, vp, c.c_int32, vp, vp]),
         "mimi_encode_stream_step_slots": (c.c_int, [vp, c.POINTER(c.c_int32), c.c_int32, vp, c.c_int32, vp, vp]),
+        "mimi_encode_stream_step_ragged": (c.c_int, [vp, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.c_int32,
+                                                    c.c_int32, vp, vp, vp]),
         "mimi_encode_stream_reset": (c.c_int, [vp]),
         "mimi_encode_stream_reset_slot": (c.c_int, [vp, c.c_int32]),
         "mimi_encode_stream_position": (c.c_int64, [vp]),

@@ -242,12 +242,18 @@ class DecodeStream(_Stream):
     _direction = "decode"
 
     def step(self, codes: torch.Tensor, out: Optional[torch.Tensor] = None,
-             slots: Optional[Sequence[int]] = None) -> torch.Tensor:
+             slots: Optional[Sequence[int]] = None, frames: Optional[Sequence[int]] = None) -> torch.Tensor:
         """The next ``n`` frames: int64 / int32 codes ``[B, K, n]`` on any device -> float32 ``[B, 1, 1920 n]`` on the
         model's device (``out`` if given).  With ``slots`` (``m`` distinct ints in ``[0, batch)``, any order) only those
         slots advance: ``codes`` is ``[m, K, n]``, item ``i`` the next frames of slot ``slots[i]``, the result
         ``[m, 1, 1920 n]``.  ``ValueError`` for ``n`` outside ``[1, max_step_frames]`` and a bad slot list (the state is
-        untouched) and for a code outside ``[0, codebook_size)`` (the slots of that call then refuse until ``reset``)."""
+        untouched) and for a code outside ``[0, codebook_size)`` (the slots of that call then refuse until ``reset``).
+
+        With ``frames`` (one int per item, each in ``[1, n]``) item ``i`` advances by its own ``frames[i]`` frames:
+        ``codes`` is padded, ``[m, K, n]`` with columns past ``frames[i]`` never read, and so is the result, ``[m, 1,
+        1920 n]`` -- zero past ``1920 frames[i]`` samples when this call allocates it, left untouched there in a
+        caller's ``out``.  Without ``slots`` the items are slots ``0 .. batch - 1``.  Bad ``frames`` raise
+        ``ValueError`` with the state untouched."""
         m = self._model
         self._handle()
         if not torch.is_tensor(codes):
@@ -258,13 +264,25 @@ class DecodeStream(_Stream):
         n = int(codes.shape[2])
         if n < 1 or n > self.max_step_frames:
             raise ValueError(f"a step takes 1 .. {self.max_step_frames} frames, got {n}")
+        if frames is not None:
+            frames = [int(x) for x in frames]
+            if len(frames) != items or min(frames) < 1 or max(frames) > n:
+                raise ValueError(f"frames must be {items} counts in [1, {n}], got {frames}")
         L = m.get_decoded_length(n)
         if out is None:
-            out = torch.empty((items, 1, L), dtype=torch.float32, device=m.device)
+            out = (torch.empty if frames is None else torch.zeros)((items, 1, L), dtype=torch.float32, device=m.device)
         elif (tuple(out.shape) != (items, 1, L) or out.dtype != torch.float32 or out.device != m.device
               or not out.is_contiguous()):
             raise ValueError(f"out must be a contiguous float32 [{items}, 1, {L}] tensor on {m.device}")
-        self._step(slots, codes.to(device=m.device, dtype=torch.int32).contiguous(), n, out)
+        codes = codes.to(device=m.device, dtype=torch.int32).contiguous()
+        if frames is None:
+            self._step(slots, codes, n, out)
+        else:
+            if slots is None:
+                slots = list(range(self.batch))
+            i32 = ctypes.c_int32 * items
+            self._call("step_ragged", self._handle(), i32(*slots), i32(*frames), items, n,
+                       ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(out.data_ptr()), m._stream())
         return out
 
 
@@ -287,12 +305,18 @@ class EncodeStream(_Stream):
         super().__init__(model, batch, num_quantizers, max_step_frames)
 
     def step(self, audio: torch.Tensor, slots: Optional[Sequence[int]] = None,
-             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+             out: Optional[torch.Tensor] = None, frames: Optional[Sequence[int]] = None) -> torch.Tensor:
         """The next ``n`` frames: float32 audio ``[B, F n]`` or ``[B, 1, F n]`` (``F = frame_samples``) on any device ->
         int32 codes ``[B, K, n]`` on the model's device (``out`` if given).  With ``slots`` (``m`` distinct ints in
         ``[0, batch)``, any order) only those slots advance: ``audio`` holds ``m`` items, item ``i`` the next frames of
         slot ``slots[i]``, the result is ``[m, K, n]``.  ``ValueError`` for a length that is not ``1 ..
-        max_step_frames`` whole frames and for a bad slot list or ``out`` (the state is untouched)."""
+        max_step_frames`` whole frames and for a bad slot list or ``out`` (the state is untouched).
+
+        With ``frames`` (one int per item, each in ``[1, n]``) item ``i`` advances by its own ``frames[i]`` frames:
+        ``audio`` is padded, ``[m, F n]`` with samples past ``F frames[i]`` never read (NaN there is harmless), and so
+        is the result, ``[m, K, n]`` -- zero past ``frames[i]`` when this call allocates it, left untouched there in a
+        caller's ``out``.  Without ``slots`` the items are slots ``0 .. batch - 1``.  Bad ``frames`` raise
+        ``ValueError`` with the state untouched."""
         m = self._model
         self._handle()
         if not torch.is_tensor(audio):
@@ -307,8 +331,23 @@ class EncodeStream(_Stream):
         if L % F or not 1 <= L // F <= self.max_step_frames:
             raise ValueError(f"a step takes 1 .. {self.max_step_frames} whole frames of {F} samples, got {L} samples")
         n = L // F
+        if frames is not None:
+            frames = [int(x) for x in frames]
+            if len(frames) != items or min(frames) < 1 or max(frames) > n:
+                raise ValueError(f"frames must be {items} counts in [1, {n}], got {frames}")
+        fresh = out is None
         out = m._out(items, self.num_quantizers, n, out)
-        self._step(slots, audio.to(device=m.device, dtype=torch.float32).contiguous(), n, out)
+        audio = audio.to(device=m.device, dtype=torch.float32).contiguous()
+        if frames is None:
+            self._step(slots, audio, n, out)
+        else:
+            if fresh:
+                out.zero_()
+            if slots is None:
+                slots = list(range(self.batch))
+            i32 = ctypes.c_int32 * items
+            self._call("step_ragged", self._handle(), i32(*slots), i32(*frames), items, n,
+                       ctypes.c_void_p(audio.data_ptr()), ctypes.c_void_p(out.data_ptr()), m._stream())
         return out
 
 
