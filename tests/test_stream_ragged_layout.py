@@ -13,7 +13,16 @@ from mimi_hip import _lib
 from mimi_hip.config import MimiConfig
 
 S = _lib.STREAM_MAX_STAGES
-COUNTS = ([1], [7, 1, 3], [1, 1, 12], [3, 3, 3, 3], [12] * 5, [2, 11], [1, 2, 4, 1, 2, 4, 4, 1])
+# (the last: the big step of tests/stream_scale_ref.py at m = 129 -- item j is session 13 j + 16 mod 129 with
+# 1 + (5 i mod 7) frames -- written out here so that this file stays host-only; tests/test_stream_scale_ref.py holds
+# the schedule to the same expression)
+SCALE = [1 + (5 * ((13 * j + 16) % 129)) % 7 for j in range(129)]
+assert sum(SCALE) == 515
+COUNTS = ([1], [7, 1, 3], [1, 1, 12], [3, 3, 3, 3], [12] * 5, [2, 11], [1, 2, 4, 1, 2, 4, 4, 1], SCALE)
+
+
+def count_id(frames):
+    return str(frames) if len(frames) < 16 else f"{len(frames)}items{sum(frames)}frames"
 
 
 def layout(frames, nmax=None, direction=_lib.STREAM_DECODE, cfg=None, taps=0, m=None, tweak=None):
@@ -66,7 +75,7 @@ DIRECTIONS = [(_lib.STREAM_DECODE, decode_stages), (_lib.STREAM_ENCODE, encode_s
 
 
 @pytest.mark.parametrize("direction,stages_of", DIRECTIONS, ids=["decode", "encode"])
-@pytest.mark.parametrize("frames", COUNTS, ids=str)
+@pytest.mark.parametrize("frames", COUNTS, ids=count_id)
 def test_tables_are_the_stated_layout(frames, direction, stages_of):
     cfg = MimiConfig()
     rc, stages, first, count, ws = layout(frames, direction=direction)
@@ -79,7 +88,7 @@ def test_tables_are_the_stated_layout(frames, direction, stages_of):
 
 
 @pytest.mark.parametrize("direction", [_lib.STREAM_DECODE, _lib.STREAM_ENCODE], ids=["decode", "encode"])
-@pytest.mark.parametrize("frames", COUNTS, ids=str)
+@pytest.mark.parametrize("frames", COUNTS, ids=count_id)
 def test_blocks_are_disjoint_in_order_and_aligned(frames, direction):
     rc, stages, first, count, ws = layout(frames, direction=direction)
     assert rc == 0
