@@ -725,6 +725,58 @@ int mimi_bpe_decode_write(mimi_bpe_model* m, int32_t* dev_codes, int64_t item_st
                           int64_t max_frames, void* stream);
 
 /*
+ * Codec-BPE decoding chunk by chunk: a pool of `slots` sessions, each with its own filter state in device memory;
+ * a step takes a few new token ids for any subset of the slots and writes the whole frames those ids complete, laid
+ * out as mimi_decode_stream_step_ragged takes them (mimi_hip/bpe.py IdStream drives it).  The rules above are causal,
+ * so this is exact: per slot, with K = num_codebooks, and for each character (alphabet index idx, cb = idx /
+ * codebook_size) that the slot's new ids spell, in order:
+ *     fresh (no character since the reset): expected = cb, owed = (K - cb) % K
+ *     cb != expected: dropped;  else expected = (expected + 1) % K and, if owed > 0, --owed and dropped;
+ *     else the code idx - npend * codebook_size joins the npend pending ones; K pending codes are emitted as a frame.
+ * After any sequence of steps the frames a slot has emitted are mimi_bpe_decode_plan / _write's (and
+ * Encoder.decode_ids') of all the ids it was fed since its reset, whatever the split into steps and whatever the
+ * other slots were fed.  A reset is also how a session ends: the pending partial frame is discarded, which is the
+ * batch form's end drop.
+ *
+ * mimi_bpe_decode_stream_create: needs mimi_bpe_model_set_spellings (else MIMI_ERR_STATE) and records Lmax, the
+ * longest spelling; num_codebooks > 16 returns MIMI_ERR_UNSUPPORTED (a filter state map is 16 nibbles), as does
+ * max_step_ids * Lmax of 2^31 or more.  slots >= 1; 1 <= max_step_ids <= 2^20.  Device memory: 3 + K int32 per slot,
+ * plus 32 bytes per slot of step bookkeeping.
+ * mimi_bpe_decode_stream_max_frames: host only; (K - 1 + ids * Lmax) / K, the most frames an item that brings `ids`
+ * ids can complete (-1 for a NULL stream or negative ids).
+ * mimi_bpe_decode_stream_step: item i is slot slots[i] (host, m distinct slots in any order, 1 <= m <= slots) and
+ * brings counts[i] ids (host, 0 <= counts[i] <= max_step_ids) from dev_ids + i * ids_row_stride (device int32; ids
+ * past an item's count are never read).  Writes frames_out[i] (host) whole frames to dev_codes[i][k][t], t <
+ * frames_out[i] (device int32 [m][K][max_frames]); columns past an item's frames are never written.  max_frames must
+ * be at least max_frames(the largest count).  One kernel launch on `stream`, which the call synchronises to read the
+ * frame counts back through a pinned buffer the stream owns.  Argument errors (a slot list that is not distinct or in
+ * range, a count out of range, max_frames too small, NULL pointers) return MIMI_ERR_INVALID_ARGUMENT with every slot
+ * untouched.  An id outside [0, n_tokens) (checked on the device before any table load) returns
+ * MIMI_ERR_INVALID_ARGUMENT; the outputs are undefined and the slots listed in that call then refuse with
+ * MIMI_ERR_STATE until they are reset -- the rule mimi_decode_stream_step has for a bad code.  Spellings replaced on
+ * the model after the stream was made: MIMI_ERR_STATE.
+ * mimi_bpe_decode_stream_reset / _reset_slot: all slots / one slot back to fresh (host only: the next step of the
+ * slot ignores its device record).
+ * mimi_bpe_decode_stream_slot_pending: host only; the codes pending in the slot's partial frame, 0 .. K - 1, or -1 for
+ * a fresh slot (-2 for a NULL stream or a slot out of range).
+ *
+ * Lifetime and locking: the stream has its own mutex (one step at a time) and holds the model's while it launches
+ * and until the step has finished, because mimi_bpe_model_set_spellings frees the tables the kernel reads; so a step
+ * is serialised with the model's encode and decode calls.  A stream must be destroyed before its model.
+ */
+typedef struct mimi_bpe_decode_stream mimi_bpe_decode_stream;
+int mimi_bpe_decode_stream_create(mimi_bpe_model* m, int32_t slots, int32_t max_step_ids,
+                                  mimi_bpe_decode_stream** out);
+int64_t mimi_bpe_decode_stream_max_frames(const mimi_bpe_decode_stream* st, int32_t ids);
+int mimi_bpe_decode_stream_step(mimi_bpe_decode_stream* st, const int32_t* slots, const int32_t* counts, int32_t m,
+                                const int32_t* dev_ids, int64_t ids_row_stride, int32_t* dev_codes,
+                                int32_t max_frames, int32_t* frames_out, void* stream);
+int mimi_bpe_decode_stream_reset(mimi_bpe_decode_stream* st);
+int mimi_bpe_decode_stream_reset_slot(mimi_bpe_decode_stream* st, int32_t slot);
+int32_t mimi_bpe_decode_stream_slot_pending(mimi_bpe_decode_stream* st, int32_t slot);
+void mimi_bpe_decode_stream_destroy(mimi_bpe_decode_stream* st);
+
+/*
  * Diagnostic: the fp16 plane split the kernels use (two v_fma_mix per value: hi = fp16(v s), lo = fp16(v s - hi))
  * against the conversion form it replaces, on npairs value pairs of dev_in (device f32 [2 npairs], s a power of two):
  * dev_out (device u32 [npairs][4]) = the kernels' (hi, lo) words and the conversion form's (hi, lo) words.  Tests

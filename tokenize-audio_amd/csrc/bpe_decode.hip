@@ -30,76 +30,28 @@
 #include <vector>
 
 #include "bpe_model.h"
+#include "bpe_scan.h"
 
 namespace {
 
 using mimi::bpe::fail;
-typedef unsigned long long u64;
+// the operators, the workgroup scan and the binary search: bpe_scan.h (shared with bpe_decode_stream.hip)
+using mimi::bpe::AddOp;
+using mimi::bpe::block_exclusive;
+using mimi::bpe::char_map;
+using mimi::bpe::find_in;
+using mimi::bpe::kMaxK;
+using mimi::bpe::MapOp;
+using mimi::bpe::u64;
 
-constexpr int kThreads = 256;
+constexpr int kThreads = mimi::bpe::kScanThreads;
 constexpr int kTile = MIMI_BPE_DECODE_SCAN_TILE;
 constexpr int kItems = kTile / kThreads;  // rows of kThreads positions per tile
-constexpr int kMaxK = 16;                 // nibbles of a u64
 static_assert(kTile % kThreads == 0 && kThreads == 256, "tile layout");
 
 // info word of a character: alphabet index (17 bits) | codebook << 17 (4 bits) | first of its sequence << 21 | keep << 22
 constexpr int kCbShift = 17, kFirstShift = 21, kKeepShift = 22;
 constexpr unsigned kIdxMask = (1u << kCbShift) - 1;
-
-// ---- the two operators ---------------------------------------------------------------------------------------
-struct AddOp {
-    __device__ __forceinline__ u64 identity() const { return 0; }
-    __device__ __forceinline__ u64 combine(u64 earlier, u64 later) const { return earlier + later; }
-};
-
-constexpr u64 kIdentityMap = 0xfedcba9876543210ull;
-
-struct MapOp {
-    int K;
-    __device__ __forceinline__ u64 identity() const { return kIdentityMap; }
-    // (later o earlier)(e) = later(earlier(e)); entries at and above K stay the identity's
-    __device__ __forceinline__ u64 combine(u64 earlier, u64 later) const {
-        u64 r = kIdentityMap;
-        for (int e = 0; e < K; ++e) {
-            const unsigned mid = (unsigned)(earlier >> (4 * e)) & 15u;
-            const u64 to = (later >> (4 * mid)) & 15ull;
-            r = (r & ~(15ull << (4 * e))) | (to << (4 * e));
-        }
-        return r;
-    }
-};
-
-// the map of one character of codebook cb: the first of a sequence sends every state to (cb + 1) % K
-__device__ __forceinline__ u64 char_map(unsigned cb, bool first, int K) {
-    const u64 next = (u64)((cb + 1) % (unsigned)K);
-    if (first) return next * 0x1111111111111111ull;
-    return (kIdentityMap & ~(15ull << (4 * cb))) | (next << (4 * cb));
-}
-
-// exclusive scan of one value per thread over the workgroup, in thread order; total = all of them.  wtot: 4 words
-template <typename Op>
-__device__ __forceinline__ u64 block_exclusive(const Op& op, u64 v, u64* wtot, u64& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 x = v;  // inclusive over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 y = __shfl_up(x, o);
-        if (lane >= o) x = op.combine(y, x);
-    }
-    const u64 before = __shfl_up(x, 1);
-    if (lane == 63) wtot[wave] = x;
-    __syncthreads();
-    u64 base = op.identity(), all = op.identity();
-#pragma unroll
-    for (int i = 0; i < kThreads / 64; ++i) {
-        const u64 s = wtot[i];
-        if (i < wave) base = op.combine(base, s);
-        all = op.combine(all, s);
-    }
-    __syncthreads();  // wtot is reused by the next call
-    total = all;
-    return lane == 0 ? base : op.combine(base, before);
-}
 
 // pass 1: partials[tile] = the tile's values combined in position order (row by row: the operator need not commute)
 template <typename Op, typename Src>
@@ -149,17 +101,6 @@ __global__ __launch_bounds__(kThreads) void scan_apply_kernel(Op op, Src src, Si
         if (p < n) sink((int)p, op.combine(carry, e));
         carry = op.combine(carry, total);
     }
-}
-
-// the last s in [0, n) with pos[s] <= p, for pos[0] <= p < pos[n] (empty entries are skipped)
-__device__ __forceinline__ int find_in(const int* pos, int n, int p) {
-    int lo = 0, hi = n;  // pos[lo] <= p < pos[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pos[mid] <= p) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // ---- value sources and sinks ---------------------------------------------------------------------------------
@@ -405,6 +346,7 @@ extern "C" int mimi_bpe_model_set_spellings(mimi_bpe_model* m, const int64_t* sp
     if (m->spell_idx) (void)hipFree(m->spell_idx);
     m->spell_off = dev_off;
     m->spell_idx = dev_idx;
+    ++m->spell_version;
     return MIMI_OK;
 }
 

@@ -1,5 +1,6 @@
 // The device BPE model shared by bpe_encode.hip (merge table, merge kernels, host-word entry), bpe_words.hip
-// (device word model, device-to-device entry) and bpe_decode.hip (ids back to codes).
+// (device word model, device-to-device entry), bpe_decode.hip (ids back to codes) and bpe_decode_stream.hip (the same,
+// chunk by chunk per slot).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -72,6 +73,7 @@ struct mimi_bpe_model {
     // the last mimi_bpe_decode_plan and what mimi_bpe_decode_write needs of it.  Any other call clears plan_valid
     int* spell_off = nullptr;
     int* spell_idx = nullptr;
+    int64_t spell_version = 0;  // counts mimi_bpe_model_set_spellings calls: a decode stream serves the tables it was made on
     mimi::bpe::Buffer dec_seq_ids, dec_id_start, dec_cpos, dec_info, dec_rank, dec_begin, dec_frames, dec_partials,
         dec_ctl;
     bool plan_valid = false;

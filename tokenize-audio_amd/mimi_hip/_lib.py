@@ -44,6 +44,9 @@ EXPORTED_SYMBOLS = (
     "mimi_bpe_model_set_alphabet", "mimi_bpe_encode_codes",
     "mimi_bpe_create_opts", "mimi_bpe_info", "mimi_bpe_read_pairs", "mimi_bpe_read_words",
     "mimi_bpe_model_set_spellings", "mimi_bpe_decode_plan", "mimi_bpe_decode_write",
+    "mimi_bpe_decode_stream_create", "mimi_bpe_decode_stream_max_frames", "mimi_bpe_decode_stream_step",
+    "mimi_bpe_decode_stream_reset", "mimi_bpe_decode_stream_reset_slot", "mimi_bpe_decode_stream_slot_pending",
+    "mimi_bpe_decode_stream_destroy",
 )
 CREATE_DECODE = 1  # MIMI_CREATE_DECODE
 STREAM_DECODE, STREAM_ENCODE, STREAM_MAX_STAGES = 0, 1, 16  # MIMI_STREAM_*
@@ -165,6 +168,14 @@ def _declare(lib):
         "mimi_bpe_model_set_spellings": (c.c_int, [vp, vp, vp]),
         "mimi_bpe_decode_plan": (c.c_int, [vp, vp, vp, c.c_int64, vp, vp]),
         "mimi_bpe_decode_write": (c.c_int, [vp, vp, c.c_int64, c.c_int64, c.c_int64, vp]),
+        "mimi_bpe_decode_stream_create": (c.c_int, [vp, c.c_int32, c.c_int32, c.POINTER(vp)]),
+        "mimi_bpe_decode_stream_max_frames": (c.c_int64, [vp, c.c_int32]),
+        "mimi_bpe_decode_stream_step": (c.c_int, [vp, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.c_int32, vp,
+                                                 c.c_int64, vp, c.c_int32, c.POINTER(c.c_int32), vp]),
+        "mimi_bpe_decode_stream_reset": (c.c_int, [vp]),
+        "mimi_bpe_decode_stream_reset_slot": (c.c_int, [vp, c.c_int32]),
+        "mimi_bpe_decode_stream_slot_pending": (c.c_int32, [vp, c.c_int32]),
+        "mimi_bpe_decode_stream_destroy": (None, [vp]),
         "mimi_flac_info": (c.c_int, [vp, c.c_int64, c.POINTER(c.c_int32), c.POINTER(c.c_int32),
                                      c.POINTER(c.c_int32), c.POINTER(c.c_int64)]),
         "mimi_flac_decode": (c.c_int, [vp, c.c_int64, vp, c.c_int64, c.POINTER(c.c_int64)]),

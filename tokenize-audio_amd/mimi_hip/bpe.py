@@ -43,6 +43,7 @@ import json
 import os
 import time
 import warnings
+import weakref
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -473,6 +474,7 @@ class Encoder:
         # from the merges on first use
         self._spell: Optional[Tuple[np.ndarray, np.ndarray]] = None
         self._spell_on_device = False
+        self._streams = weakref.WeakSet()  # open IdStreams: closed before the device model
         if spellings is not None:
             if len(spellings) != self.n_tokens:
                 raise ValueError(f"{len(spellings)} spellings for {self.n_tokens} tokens")
@@ -517,6 +519,8 @@ class Encoder:
         return h
 
     def close(self) -> None:
+        for st in list(getattr(self, "_streams", ())):
+            st.close()
         if getattr(self, "_h", None) is not None and self._h:
             self._lib.mimi_bpe_model_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -975,3 +979,152 @@ class Encoder:
             h = codes.cpu().numpy().astype(np.int64)
             return [np.ascontiguousarray(h[i, :, :int(frames[i])]) for i in range(n_seq)]
         return codes, frames
+
+    def decode_stream(self, slots: int, max_step_ids: int) -> "IdStream":
+        """An ``IdStream`` of ``slots`` sessions whose steps bring at most ``max_step_ids`` ids per slot: token ids ->
+        codes chunk by chunk, the filter state of every session in device memory.  ``NotImplementedError`` for more
+        than 16 codebooks (the device filter's state map is 16 nibbles; ``decode_ids`` has no such limit)."""
+        return IdStream(self, slots, max_step_ids)
+
+
+class IdStream:
+    """Streaming ``Encoder.decode_device`` (``Encoder.decode_stream``; ``mimi_bpe_decode_stream_*``,
+    ``bpe_decode_stream.hip``): ``slots`` sessions, each with its own filter state in device memory.  ``step`` takes a
+    few new token ids for any subset of the slots and returns the whole frames those ids complete, laid out as
+    ``DecodeStream.step(codes, slots=, frames=)`` takes them.  ``decode_ids``' rules are causal, so after any sequence
+    of steps the frames a slot has emitted, end to end, equal ``decode_ids([every id it was fed since its reset])[0]``
+    -- whatever the split into steps and whatever the other slots were fed; the partial last frame stays pending
+    (``pending``) until later ids complete it, and ``reset(slot)``, which is also how a session ends, discards it.
+    One kernel launch and one synchronisation per step.  A context manager; ``close()`` frees the state (closing the
+    encoder closes its streams).  The other direction, codes -> ids chunk by chunk, is not provided: BPE merges are
+    not prefix-stable."""
+
+    def __init__(self, encoder: "Encoder", slots: int, max_step_ids: int):
+        self._enc, self.slots, self.max_step_ids = encoder, int(slots), int(max_step_ids)
+        self.num_codebooks = encoder.num_codebooks
+        self._h = None
+        if self.slots < 1 or self.max_step_ids < 1:
+            raise ValueError(f"a stream has at least 1 slot and takes at least 1 id per step, got {slots}, {max_step_ids}")
+        if self.num_codebooks > 16:
+            raise NotImplementedError(f"{self.num_codebooks} codebooks: the device filter packs at most 16 "
+                                      f"(decode_ids has no such limit)")
+        h = ctypes.c_void_p()
+        self._call("create", encoder._decode_model(), self.slots, self.max_step_ids, ctypes.byref(h))
+        self._h = h
+        encoder._streams.add(self)
+
+    def _call(self, name: str, *args):
+        """``mimi_bpe_decode_stream_<name>(*args)``; an invalid argument (status 1) is a ``ValueError``."""
+        from . import _lib
+        try:
+            _lib.check(getattr(self._enc._lib, f"mimi_bpe_decode_stream_{name}")(*args))
+        except _lib.MimiHipError as err:
+            if err.status == 1:
+                raise ValueError(str(err)) from None
+            raise
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError("this IdStream is closed")
+        return self._h
+
+    def max_frames(self, ids: int) -> int:
+        """The most frames an item that brings ``ids`` ids can complete: ``(K - 1 + ids * Lmax) // K``, ``Lmax`` the
+        longest spelling."""
+        if ids < 0:
+            raise ValueError(f"ids must be at least 0, got {ids}")
+        return int(self._enc._lib.mimi_bpe_decode_stream_max_frames(self._handle(), int(ids)))
+
+    @property
+    def pending(self) -> List[int]:
+        """Per slot: the codes waiting in its partial frame, ``0 .. K - 1``, or ``-1`` for a fresh slot (no character
+        since its reset)."""
+        h = self._handle()
+        return [int(self._enc._lib.mimi_bpe_decode_stream_slot_pending(h, b)) for b in range(self.slots)]
+
+    def reset(self, slot: Optional[int] = None):
+        """All slots, or only ``slot``, back to fresh: the pending partial frame is discarded and what follows equals
+        a new stream (``ValueError`` for a slot outside ``[0, slots)``)."""
+        if slot is None:
+            self._call("reset", self._handle())
+        else:
+            self._call("reset_slot", self._handle(), int(slot))
+
+    def step(self, ids, slots: Optional[Sequence[int]] = None, counts: Optional[Sequence[int]] = None, out=None):
+        """New ids: a CUDA int32 / int64 tensor ``[m, L]``, padded; item ``i`` is slot ``slots[i]`` (``m`` distinct
+        ints in ``[0, slots)``, any order; default: slots ``0 .. slots - 1``) and brings ``counts[i]`` ids, ``0 ..
+        min(L, max_step_ids)`` (default ``L``); ids past an item's count are never read.  Returns ``(codes, frames)``:
+        ``frames`` a host list, the whole frames each item completed, ``codes`` int32 ``[m, K, max(frames)]`` on the
+        device (``max(frames)`` may be 0), item ``i``'s frames in ``codes[i, :, :frames[i]]`` -- zero past them in a
+        tensor made here; with ``out`` (contiguous int32 CUDA ``[m, K, >= max_frames(max(counts))]``) ``codes`` is a
+        view of it and nothing past an item's frames is written.  Runs on the current stream and synchronises it.
+        Argument errors raise ``ValueError`` before any device call, the state untouched.  An id outside ``[0,
+        n_tokens)`` is a ``ValueError`` too (checked on the device); the slots of that call then refuse until
+        ``reset``."""
+        import torch
+        h = self._handle()
+        K = self.num_codebooks
+        if not isinstance(ids, torch.Tensor) or not ids.is_cuda:
+            raise ValueError("ids must be a CUDA torch.Tensor")
+        if ids.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"ids must be int32 or int64, not {ids.dtype}")
+        if ids.device.index != self._enc.device:
+            raise ValueError(f"ids are on {ids.device}, the encoder on device {self._enc.device}")
+        if slots is None:
+            slots = list(range(self.slots))
+        else:
+            slots = [int(x) for x in slots]
+            if not 1 <= len(slots) <= self.slots:
+                raise ValueError(f"a step lists 1 .. {self.slots} slots, got {len(slots)}")
+            if min(slots) < 0 or max(slots) >= self.slots or len(set(slots)) != len(slots):
+                raise ValueError(f"slots must be distinct and in [0, {self.slots}), got {slots}")
+        m = len(slots)
+        if ids.dim() != 2 or ids.shape[0] != m:
+            raise ValueError(f"ids must be [{m}, L], got {tuple(ids.shape)}")
+        L = int(ids.shape[1])
+        top = min(L, self.max_step_ids)
+        if counts is None:
+            counts = [L] * m
+        else:
+            counts = [int(x) for x in (counts.tolist() if hasattr(counts, "tolist") else counts)]
+        if len(counts) != m or min(counts) < 0 or max(counts) > top:
+            raise ValueError(f"counts must be {m} counts in [0, {top}], got {counts}")
+        cap = self.max_frames(max(counts))
+        if out is not None:
+            if (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.dim() != 3
+                    or out.device != ids.device or out.shape[0] != m or out.shape[1] != K or out.shape[2] < cap
+                    or not out.is_contiguous()):
+                raise ValueError(f"out must be a contiguous int32 [{m}, {K}, >= {cap}] tensor on {ids.device}")
+        with torch.cuda.device(ids.device):
+            if ids.dtype != torch.int32:  # (an id beyond int32 stays outside [0, n_tokens))
+                ids = ids.clamp(-1, 0x7fffffff).to(torch.int32)
+            if not ids.is_contiguous():
+                ids = ids.contiguous()
+            codes = torch.zeros((m, K, cap), dtype=torch.int32, device=ids.device) if out is None else out
+            i32 = ctypes.c_int32 * m
+            frames = i32()
+            s = torch.cuda.current_stream(ids.device).cuda_stream
+            self._call("step", h, i32(*slots), i32(*counts), m, ctypes.c_void_p(ids.data_ptr()) if L else None,
+                       L, ctypes.c_void_p(codes.data_ptr()) if codes.shape[2] else None,
+                       codes.shape[2], frames, ctypes.c_void_p(int(s)) if s else None)
+        frames = list(frames)
+        return codes[:, :, :max(frames)], frames
+
+    def close(self):
+        h, self._h = self._h, None
+        if h is not None and self._enc._h:
+            self._enc._lib.mimi_bpe_decode_stream_destroy(h)
+        self._enc._streams.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass

@@ -174,3 +174,81 @@ def ids_to_audio(ids, seq_offsets, encoder, mimi_model, max_batch_frames: int = 
         frames += T
     flush()
     return out
+
+
+class IdsToAudioStream:
+    """BPE token ids -> samples chunk by chunk, nothing leaving the device in between: an ``IdStream``
+    (``encoder.decode_stream``, ids -> the whole frames they complete) in front of a ``DecodeStream``
+    (``mimi_model.decode_stream``, frames -> samples), ``batch`` slots each, slot ``b`` of one feeding slot ``b`` of the
+    other.  ``encoder``: a ``bpe.Encoder`` whose ``num_codebooks`` is the decode stream's ``num_quantizers`` and whose
+    ``codebook_size`` is the model's; ``mimi_model`` is built with ``decode=True``.  A slot's samples, end to end, are
+    bitwise those of a ``batch=1`` ``DecodeStream`` stepped over ``encoder.decode_ids`` of everything the slot was fed
+    since its reset, whatever the split into steps and whatever its neighbours do.  A context manager; ``close()``
+    closes both streams."""
+
+    def __init__(self, encoder, mimi_model, batch: int, max_step_ids: int, max_step_frames: int = 16):
+        if encoder.codebook_size != mimi_model.config.codebook_size:
+            raise ValueError(f"the encoder has codebooks of {encoder.codebook_size} codes, the model of "
+                             f"{mimi_model.config.codebook_size}")
+        self.batch = int(batch)
+        self.ids = encoder.decode_stream(batch, max_step_ids)
+        try:
+            self.audio = mimi_model.decode_stream(batch, num_quantizers=encoder.num_codebooks,
+                                                  max_step_frames=max_step_frames)
+        except Exception:
+            self.ids.close()
+            raise
+        self.frame_samples = int(mimi_model.get_decoded_length(1))
+        self._device = mimi_model.device
+        self.last_frames: List[int] = []
+
+    @property
+    def positions(self) -> List[int]:
+        """Frames each slot has emitted since its reset (the decode stream's positions)."""
+        return self.audio.positions
+
+    @property
+    def pending(self) -> List[int]:
+        """Codes waiting in each slot's partial frame (``IdStream.pending``)."""
+        return self.ids.pending
+
+    def step(self, ids, slots: Optional[Sequence[int]] = None, counts: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
+        """``IdStream.step(ids, slots, counts)``, then the items that completed at least one frame go through
+        ``DecodeStream.step(codes, slots=, frames=)`` in column windows of at most ``max_step_frames`` frames; a
+        window leaves out the items that have no frame left by then.  Returns one float32 device tensor ``[1920
+        frames_i]`` per item, empty for an item that completed no frame; ``last_frames`` holds the ``frames_i``.
+        Errors are those of the two steps; an id step that raises leaves the decode stream untouched."""
+        codes, frames = self.ids.step(ids, slots=slots, counts=counts)
+        slots = list(range(self.batch)) if slots is None else [int(x) for x in slots]
+        F, W = self.frame_samples, self.audio.max_step_frames
+        out = [torch.empty(F * f, dtype=torch.float32, device=self._device) for f in frames]
+        at = 0
+        while True:
+            sel = [i for i, f in enumerate(frames) if f > at]
+            if not sel:
+                break
+            n = [min(W, frames[i] - at) for i in sel]
+            rows = codes if len(sel) == len(frames) else codes[sel]
+            audio = self.audio.step(rows[:, :, at:at + max(n)], slots=[slots[i] for i in sel], frames=n)
+            for j, i in enumerate(sel):
+                out[i][F * at:F * (at + n[j])] = audio[j, 0, :F * n[j]]
+            at += max(n)
+        self.last_frames = list(frames)
+        return out
+
+    def reset(self, slot: Optional[int] = None):
+        """Both streams back to fresh, all slots or one: the pending partial frame is discarded, the next samples are
+        those of a new session."""
+        self.ids.reset(slot)
+        self.audio.reset(slot)
+
+    def close(self):
+        self.ids.close()
+        self.audio.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
